@@ -21,9 +21,17 @@ default is 20 sets, so that the READ-ONLY inputs alone (29.4 MB per set) are
 (with SURVEY.md §8d's 8 sets the 235 MB of inputs stay cache resident: that
 protocol, and the one-set cache-resident launch, are reported next to the
 headline, labelled, never as `value`).
-The K steps are captured into one HIP graph; the graph is replayed R times so
-that the timed region is >= --min-ms (1 s: long enough for the driver's
-GPU-activity sampling to see it); `steps` stays K, `config.replays` = R.
+The timed region is exactly K steps: they are captured into HIP graphs of at
+most STEPS_PER_GRAPH steps (one graph of the K steps up to that size), and
+each graph is replayed once per chunk of the K steps (`config.replays`).
+`ms_per_step` is the host time of the timed region over K.
+
+A plain run measures only that headline.  `--full` adds everything else the
+line used to carry: the kernel-only roofline pass, the other buffer-set
+protocols, the copy bandwidth and stream floor, the training-step and epoch
+blocks, the secondary workloads and the CPU baseline.  `--dump-outputs DIR`
+writes what the last timed step returned (see `dump_outputs`), so that two
+builds can be compared output for output on the same seeded inputs.
 `--dry-run-cpu` executes the rank logic of this file (process group, replay
 agreement, barriers, max over ranks, rank-0 print) under gloo on the CPU with
 a stub in place of the kernels - tests/test_distributed_cpu.py runs it with
@@ -41,6 +49,10 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+# the timed steps are replayed from graphs of at most this many steps: a long
+# run neither captures nor instantiates one graph of all its steps
+STEPS_PER_GRAPH = 1000
+DUMP_BYTES = 64 * 2**20   # --dump-outputs writes at most this much
 QUAD_BYTES_PER_TRAJ = {  # state0 + actions + ref(pos,vel) + dL/dactions
     "base": lambda H: 48 + 16 * H + 24 * H + 16 * H,
     "grad_state0": 48,
@@ -61,8 +73,8 @@ def parse():
                          "the fast path); soa: planes [C][B]; aos: the "
                          "reference's row-major tensors")
     ap.add_argument("--min-ms", type=float, default=1000.0,
-                    help="replay the K-step graph until the timed region is "
-                         "at least this long")
+                    help="with --full: replay the kernel-only roofline graph until "
+                         "its timed region is at least this long")
     ap.add_argument("--sets", type=int, default=20,
                     help="rotating buffer sets of the headline (20: the read-only "
                          "inputs alone are 588 MB > 2 x the Infinity Cache)")
@@ -77,7 +89,8 @@ def parse():
                          "one captured HIP graph of the K steps")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the headline launches (for the rocprofv3 pass whose "
+                    help="with --full: only the headline launches and their "
+                         "kernel-only pass (for the rocprofv3 pass whose "
                          "per-kernel average must not mix protocols)")
     ap.add_argument("--dry-run-cpu", action="store_true",
                     help="rank logic only, gloo on the CPU, stub kernels")
@@ -87,7 +100,17 @@ def parse():
                     help="steps of the secondary full-training-step "
                          "measurement (0 disables it)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline as well (roofline "
+                         "passes, other protocols, training steps, secondaries, CPU "
+                         "baseline); the options above that select among those "
+                         "apply only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the outputs of the last timed step to DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def make_sets(args, rank, dev, nsets=None, first=0):
@@ -1184,11 +1207,31 @@ def headline_fields(args, world, nsteps, elapsed, replays, nset):
             "input_bytes_all_sets": nset * B * (48 + 40 * H),
             "grad_state0": bool(args.grad_state0),
             "loss_mode": args.loss_mode,
-            "launch": "python" if args.no_graph else "hip-graph replay of the K steps",
+            "launch": "python" if args.no_graph else (
+                f"hip-graph replays of the K steps, <= {STEPS_PER_GRAPH} steps per graph"),
             "replays": replays, "timed_steps": nsteps,
             "parallelism": f"batch-sharded x{world}, no data-path collective",
         },
     }
+
+
+def dump_outputs(path, outs, loss_mode):
+    """What a caller of the timed launch receives from its last step - the loss
+    (unless --loss-mode none, whose launches leave it unwritten), dL/dactions
+    and, with --grad-state0, dL/dstate0, in the layout of the launch - as
+    float32 `<path>/<name>.npy`.  An output larger than its share of DUMP_BYTES
+    is written as a fixed sample (seed 0) of its flattened elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    names = ["grad_actions", "grad_state0"] + (["loss"] if loss_mode != "none" else [])
+    arrays = {k: outs[k] for k in names if outs.get(k) is not None}
+    share = DUMP_BYTES // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > share:
+            pick = np.random.default_rng(0).choice(a.size, share // 4, replace=False)
+            a = a.reshape(-1)[np.sort(pick)]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def dry_run_cpu(args, dist, rank, world):
@@ -1416,7 +1459,7 @@ def main():
         kplans = [F.RolloutPlan("quad", *s, args.dt, dyn.params,
                                 layout=args.layout,
                                 want_grad_state0=args.grad_state0,
-                                loss_mode="none") for s in sets]
+                                loss_mode="none") for s in sets] if args.full else None
 
     def run_steps(n):
         """n steps; with deferred losses step i's launch also reduces step
@@ -1451,44 +1494,67 @@ def main():
     with torch.cuda.stream(side):
         run_steps(args.warmup)
     torch.cuda.synchronize()
-    g_steps = graph_of(run_steps, args.steps)
-    g_kernel = graph_of(run_kernel_only, args.steps)
+    # the K timed steps as graph replays of `per_graph` steps and one of the rest
+    per_graph = min(args.steps, STEPS_PER_GRAPH)
+    chunks = [per_graph] * (args.steps // per_graph)
+    if args.steps % per_graph:
+        chunks.append(args.steps % per_graph)
+    g_steps = {n: graph_of(run_steps, n) for n in set(chunks)}
 
-    def timed(fn, n, graph, replays):
-        """(host seconds, HIP-event ms) for `replays` x n steps, bracketed by
-        barrier + synchronize on both sides."""
+    def timed(fn, chunks, graphs):
+        """(host seconds, HIP-event ms) for the steps of `chunks` - per entry n
+        the graph of n steps replayed once, or fn(n) without graphs - bracketed
+        by barrier + synchronize on both sides."""
         e0 = torch.cuda.Event(enable_timing=True)
         e1 = torch.cuda.Event(enable_timing=True)
         barrier()
         t0 = time.perf_counter()
         with torch.cuda.stream(side):
             e0.record()
-            for _ in range(replays):
-                if graph is not None:
-                    graph.replay()
+            for n in chunks:
+                if graphs[n] is not None:
+                    graphs[n].replay()
                 else:
                     fn(n)
             e1.record()
         barrier()
         return time.perf_counter() - t0, e0.elapsed_time(e1)
 
-    # one untimed pass (graph upload, clocks) that also sizes the region
-    _, probe_ms = timed(run_steps, args.steps, g_steps, 1)
-    replays = max(1, int(-(-args.min_ms // max(probe_ms, 1e-3))))
-    replays = agree_replays(replays, dist, dev)
-    elapsed, ev_ms = timed(run_steps, args.steps, g_steps, replays)
+    # one untimed replay of every graph (graph upload, clocks)
+    timed(run_steps, sorted(g_steps), g_steps)
+    elapsed, ev_ms = timed(run_steps, chunks, g_steps)
     elapsed = max_over_ranks(elapsed, dist, dev)
+    if args.dump_outputs and rank == 0:
+        # the plan the last timed step ran (run_steps starts every chunk at set 0)
+        dump_outputs(args.dump_outputs, plans[(chunks[-1] - 1) % nset].out,
+                     args.loss_mode)
     loss_check = float(plans[0].out["loss"].item())
-    nsteps = args.steps * replays
+    nsteps = args.steps
+    out = headline_fields(args, world, nsteps, elapsed, len(chunks), nset)
+    out["ms_per_step_hip_events"] = ev_ms / nsteps
+    out["loss_check"] = loss_check
+    if not args.full:
+        gc.enable()
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(out))
+        return
 
     # roofline pass: the same rollout launches alone (no loss reduction),
     # bracketed by one HIP-event pair on the launch stream -> average launch
     # duration of the dominant kernel including the kernel-to-kernel boundary
-    # (a per-launch event pair would add ~2.5 us of its own to a ~8 us kernel)
+    # (a per-launch event pair would add ~2.5 us of its own to a ~8 us kernel);
+    # graphs of `per_graph` launches replayed until the region is >= --min-ms
+    replays = max(1, int(-(-args.min_ms // max(ev_ms * per_graph / nsteps, 1e-3))))
+    replays = agree_replays(replays, dist, dev)
     with torch.cuda.stream(side):
         run_kernel_only(min(args.warmup, 10))
-    _, k_ms = timed(run_kernel_only, args.steps, g_kernel, replays)
-    kernel_ms = k_ms / nsteps
+    torch.cuda.synchronize()
+    g_kernel = {per_graph: graph_of(run_kernel_only, per_graph)}
+    _, k_ms = timed(run_kernel_only, [per_graph] * replays, g_kernel)
+    kernel_ms = k_ms / (per_graph * replays)
 
     def events_over(launches):
         """average launch duration over a SUBSET of the buffer sets"""
@@ -1544,10 +1610,10 @@ def main():
                 with torch.cuda.stream(side):
                     run_two_chains(4)
                 torch.cuda.synchronize()
-                g_two = graph_of(run_two_chains, args.steps)
+                g_two = {per_graph: graph_of(run_two_chains, per_graph)}
                 o_replays = max(1, replays // 10)
-                _, o_ms = timed(run_two_chains, args.steps, g_two, o_replays)
-                overlap_ms = o_ms / (args.steps * o_replays)
+                _, o_ms = timed(run_two_chains, [per_graph] * o_replays, g_two)
+                overlap_ms = o_ms / (per_graph * o_replays)
                 del g_two
             except Exception:        # informational only
                 overlap_ms = None
@@ -1559,8 +1625,6 @@ def main():
     algo_bytes = B * bytes_per_traj
     achieved = algo_bytes / (kernel_ms * 1e-3) / 1e9
     traffic, traffic_note = load_pmc_traffic(args)
-    out = headline_fields(args, world, nsteps, elapsed, replays, nset)
-    out["ms_per_step_hip_events"] = ev_ms / nsteps
     out["roofline"] = {
         "bound": "hbm",
         "kernel": {"packed": "quad_rollout_rows_kernel",
@@ -1581,7 +1645,6 @@ def main():
         "buffer_sets": nset,
         "other_protocols": other_protocols,
     }
-    out["loss_check"] = loss_check
     if overlap_ms is not None:
         out["overlapped_launches"] = {
             "streams": 2, "ms_per_step": overlap_ms,

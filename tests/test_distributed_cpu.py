@@ -176,6 +176,11 @@ def _ar_steps(lo, hi, graphed=False, split=None, new_buffers_on_rank=None):
         return loss.detach(), views, flat
     orig = F.quad_mlp_rollout_grads
     F.quad_mlp_rollout_grads = oracle_grads
+    # the trainer captures its graphed step wherever torch sees a GPU; these are
+    # CPU tensors, so the GPU is hidden from it and the step stays emulated on
+    # every machine (`not g.capture` below)
+    cuda_available = torch.cuda.is_available
+    torch.cuda.is_available = lambda: False
     try:
         class Dyn:           # analytic simulator as far as the trainer can tell
             params = object()
@@ -220,6 +225,7 @@ def _ar_steps(lo, hi, graphed=False, split=None, new_buffers_on_rank=None):
         return losses, {k: v.numpy() for k, v in t.net.state_dict().items()}
     finally:
         F.quad_mlp_rollout_grads = orig
+        torch.cuda.is_available = cuda_available
 
 
 def _worker(rank, world, port, out_dir):

@@ -969,6 +969,34 @@ def test_wing_dataset_prepare_data_and_self_play_slots():
     assert torch.equal(ds.states[8 + 5], d["state0"][29])    # self-play part kept
 
 
+def test_bench_dump_outputs_writes_float32_within_the_size_cap(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: the outputs a caller of the timed launch
+    receives, float32, one `<name>.npy` each; an output beyond its share of the
+    cap is a fixed sample (the same on every run); `--steps` below 1 is refused."""
+    import subprocess
+    import sys
+    import bench
+    ga = torch.arange(10 * 64 * 4, dtype=torch.float32).reshape(10, 64, 4)
+    outs = dict(loss=torch.tensor([3.5]), loss_partials=torch.ones(8), grad_actions=ga,
+                grad_state0=None, states=None)
+    bench.dump_outputs(str(tmp_path / "a"), outs, "deferred")
+    assert sorted(os.listdir(tmp_path / "a")) == ["grad_actions.npy", "loss.npy"]
+    got = np.load(tmp_path / "a" / "grad_actions.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, ga.numpy())
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [3.5]
+    bench.dump_outputs(str(tmp_path / "n"), outs, "none")      # no loss is computed
+    assert os.listdir(tmp_path / "n") == ["grad_actions.npy"]
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1024)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), outs, "deferred")
+    b = np.load(tmp_path / "b" / "grad_actions.npy")
+    assert b.nbytes == 512 and np.array_equal(b, np.load(tmp_path / "c" / "grad_actions.npy"))
+    assert np.all(np.diff(b) > 0) and np.isin(b, ga.numpy().ravel()).all()
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "0"],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr
+
+
 def test_committed_pmc_counters_belong_to_the_committed_kernel_sources():
     """bench.py reports `roofline.traffic` (and the fixed-wing VALU fraction)
     only when profiles/pmc_traffic.json was taken on the kernel sources it

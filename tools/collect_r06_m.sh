@@ -2,7 +2,7 @@
 export TMPDIR=/tmp
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out/r06m; rm -rf $O; mkdir -p $O
-python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
 python - <<'PY'
 import json
 d=json.loads([l for l in open("gpurun_out/r06m/bench.json") if l.startswith("{")][-1])

@@ -5,7 +5,7 @@ set -x
 export TMPDIR=/tmp
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out/r06; mkdir -p $O
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
 rm -f $O/run_epoch.jsonl
 for m in concurrent autoregressive LSTM; do
   timeout 300 python tools/time_run_epoch.py $m graph 32 >> $O/run_epoch.jsonl 2>/dev/null

@@ -1,6 +1,6 @@
 """bench.py's trainer-step block for ONE mode in a process of its own:
     python tools/time_bench_probe.py LSTM [--train-steps 400]
-The default bench run takes this block after the headline loops and the other
+`bench.py --full` takes this block after the headline loops and the other
 modes' blocks; this is the same block without that history (allocator state,
 live graphs), to tell a process effect from a step effect."""
 import json, os, sys, torch
