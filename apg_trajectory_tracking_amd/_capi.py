@@ -177,42 +177,26 @@ SIGNATURES = {
     "apg_quad_features_fwd": [_P, _I, _I, _P, _P],
     "apg_quad_features_bwd": [_P, _P, _I, _I, _P, _P],
     "apg_quad_lstm_rollout_fwd": [
-        _P, _P, _P, _P, _F, ctypes.POINTER(ApgQuadParams),
-        ctypes.POINTER(ApgLstmPolicy), _I, _I, _P, _P, _P, _P, _P, _P, _P, _P,
-        _P],
+        ctypes.POINTER(ApgBatchRows), _P, _P, _P, _P, _F, ctypes.POINTER(ApgQuadParams), _P,
+        _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
     "apg_quad_lstm_workspace_floats": [],
     "apg_quad_lstm_loss_partials_count": [_I],
     "apg_quad_lstm_rollout_bwd": [
-        _P, _P, _P, _P, _I, _P, _P, _P, _F, ctypes.POINTER(ApgQuadParams),
-        ctypes.POINTER(ApgQuadLossWeights), ctypes.POINTER(ApgLstmPolicy),
-        _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+        ctypes.POINTER(ApgBatchRows), _P, _P, _P, _P, _I, _P, _P, _P, _F,
+        ctypes.POINTER(ApgQuadParams), ctypes.POINTER(ApgQuadLossWeights), _P,
+        _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "apg_quad_lstm_cot_amax_floats": [_I],
     "apg_quad_lstm_tables_floats": [_I],
     "apg_quad_lstm_pack_tables": [ctypes.POINTER(ApgLstmPolicy), _P, _P, _P],
-    "apg_quad_lstm_rollout_fwd_packed": [
-        _P, _P, _P, _P, _F, ctypes.POINTER(ApgQuadParams), _P, _I, _I,
-        _P, _P, _P, _P, _P, _P, _P, _P],
-    "apg_quad_lstm_rollout_bwd_packed": [
-        _P, _P, _P, _P, _I, _P, _P, _P, _F, ctypes.POINTER(ApgQuadParams),
-        ctypes.POINTER(ApgQuadLossWeights), _P,
-        _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "apg_quad_lstm_step_tail": [ctypes.POINTER(ApgLstmStepTail), _P],
-    "apg_quad_lstm_rollout_fwd_rows": [
-        ctypes.POINTER(ApgBatchRows), _P, _P, _F, ctypes.POINTER(ApgQuadParams), _P, _I, _I,
-        _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-    "apg_quad_lstm_rollout_bwd_rows": [
-        ctypes.POINTER(ApgBatchRows), _I, _P, _P, _P, _P, _P, _P, _F,
-        ctypes.POINTER(ApgQuadParams), ctypes.POINTER(ApgQuadLossWeights), _P,
-        _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "apg_quad_lstm_conv_wgrad_partials_floats": [_I],
     "apg_quad_lstm_conv_wgrad": [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P],
     "apg_quad_lstm_gate_wgrad_partials_floats": [_I],
     "apg_quad_lstm_wgrads": [
-        _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.POINTER(ApgLstmPolicy), _P, _I, _I,
+        _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I,
         _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.POINTER(ApgLstmStepTail), _P],
     "apg_quad_lstm_gate_wgrad": [
-        _P, _P, _P, _P, _P, _P, _P, ctypes.POINTER(ApgLstmPolicy), _P, _I, _I,
-        _P, _P, _P, _P, _P, _P],
+        _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P],
     "apg_quad_mlp_rollout_fwd": [
         _P, _P, _F, ctypes.POINTER(ApgQuadParams),
         ctypes.POINTER(ApgMlpPolicy), _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
@@ -220,9 +204,8 @@ SIGNATURES = {
         _P, _P, _F, ctypes.POINTER(ApgQuadParams),
         ctypes.POINTER(ApgMlpPolicy), _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
     "apg_quad_lstm_rollout_fwd_inplace_ref": [
-        _P, _P, _P, _P, _F, ctypes.POINTER(ApgQuadParams),
-        ctypes.POINTER(ApgLstmPolicy), _I, _I, _P, _P, _P, _P, _P, _P, _P, _P,
-        _P],
+        _P, _P, _P, _P, _F, ctypes.POINTER(ApgQuadParams), _P, _I, _I,
+        _P, _P, _P, _P, _P, _P, _P, _P],
     "apg_quad_mlp_workspace_floats": [],
     "apg_quad_mlp_loss_partials_count": [_I],
     "apg_quad_mlp_step_workspace_floats": [],

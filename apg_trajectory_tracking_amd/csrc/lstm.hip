@@ -159,7 +159,7 @@ struct FwdArgs {
   const float *state0, *in_ref, *h0, *c0;
   float *states, *actions, *x, *gates, *hc, *hnew;
   unsigned *mask;        // [5][N] relu bits of the conv outputs
-  const float *tables;   // packed operand tables (lstm_pack_fwd16_kernel)
+  const float *tables;   // forward operand tables (apg_quad_lstm_pack_tables)
   QuadConst c;
   int B;
   // ROWS: the minibatch is named by row numbers of the whole data set's tensors
@@ -168,6 +168,7 @@ struct FwdArgs {
   // WRITES the state0 / in_ref planes its followers read (no gather pass)
   const long long *index;
   const float *r_state0, *r_in_ref;
+  long long n_rows;
   unsigned bytes_state0, bytes_in_ref;   // n_rows x ld x 4
   int ld_state0, ld_in_ref;
 };
@@ -206,15 +207,15 @@ __global__ __launch_bounds__(kThreads) void lstm_rollout_fwd_kernel(FwdArgs A) {
   const unsigned vb_lo = st_lo ? vb : kDead;
   const unsigned vb_u = live ? vb + (hi ? 4u * pitchB : 0u) : kDead;  // unit r + 4 hi
 
-  // ROWS: the lane's data-set row (range-checked buffers: a row number beyond
-  // the data set reads zeros); the planes of what it reads are this sweep's output
+  // ROWS: the lane's data-set row (a row number outside the data set reads
+  // zeros); the planes of what it reads are this sweep's output
   const Planes Rs0(A.r_state0, 1, ROWS ? A.bytes_state0 : 0u);
   const Planes Rin(A.r_in_ref, 1, ROWS ? A.bytes_in_ref : 0u);
   unsigned vr_s = kDead, vr_in = kDead;
   if (ROWS && live) {
-    const unsigned rown = (APG_LF_KNOCKOUT & 2) ? (unsigned)b : (unsigned)A.index[b];
-    vr_s = rown * (unsigned)A.ld_state0 * 4u;
-    vr_in = rown * (unsigned)A.ld_in_ref * 4u + (hi ? 16u : 0u);   // column + 4 hi
+    const long long rown = (APG_LF_KNOCKOUT & 2) ? (long long)b : A.index[b];
+    vr_s = row_offset(rown, A.n_rows, A.ld_state0);
+    vr_in = row_offset(rown, A.n_rows, A.ld_in_ref, hi ? 4 : 0);   // column 4 hi
   }
   // reference row r, columns 4 hi .. + 4 of the lane's trajectory (ROWS: 20
   // contiguous bytes of its data-set row as 16 + 4, and their planes for the
@@ -644,9 +645,6 @@ __device__ __forceinline__ void pack_bwd16(const PackArgs &A, int tid, int T) {
                        p.conv_w[ch * 27 + q * 3 + 2];
   }
 }
-__global__ __launch_bounds__(256) void lstm_pack_bwd16_kernel(PackArgs A) {
-  pack_bwd16(A, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
-}
 // both table sets in one launch (the first blocks the forward tables)
 __global__ __launch_bounds__(256) void lstm_pack_both_kernel(PackArgs F, PackArgs R, int fwd_blocks) {
   if ((int)blockIdx.x < fwd_blocks)
@@ -830,6 +828,7 @@ struct BwdArgs {
   // ROWS: ref [n][>= H][ref_cols] of the whole data set, read through `index`
   const long long *index;
   const float *r_ref;
+  long long n_rows;
   unsigned bytes_ref;
   int ld_ref;
 };
@@ -855,8 +854,7 @@ __global__ __launch_bounds__(kThreads) void lstm_rollout_bwd_kernel(BwdArgs A) {
   const Planes Pdz(A.d_zout, 4, pitchN), Pdc(A.d_conv, kConvPlanes, pitchB);
   const unsigned vb = live ? (unsigned)b * 4u : kDead;
   const Planes Rrf(A.r_ref, 1, ROWS ? A.bytes_ref : 0u);
-  const unsigned vr_ref =
-      ROWS && live ? (unsigned)A.index[b] * (unsigned)A.ld_ref * 4u : kDead;
+  const unsigned vr_ref = ROWS && live ? row_offset(A.index[b], A.n_rows, A.ld_ref) : kDead;
 
   float lam[12], dh[4], dc[4];
 #pragma unroll
@@ -1134,7 +1132,7 @@ struct GwArgs {
   const float *acts;      // [39][N]: features | h_prev, c_prev | h_new
   const float *d_gates, *d_zout;
   const float *cot_amax;  // [groups][2] (lstm_rollout_bwd_kernel)
-  const float *tables;    // forward tables (lstm_pack_fwd16_kernel)
+  const float *tables;    // forward tables (apg_quad_lstm_pack_tables)
   float *partials;        // [workgroups][kGwPart]
   int B;
 };
@@ -1737,10 +1735,8 @@ __global__ __launch_bounds__(256) void lstm_wgrad_reduce_kernel(GwReduceArgs G, 
   else conv_wgrad_reduce_body<true>(C, blockIdx.x - kGwReduceBlocks, U);
 }
 
-// pol NULL: the caller holds packed tables instead of the parameters
-int check_lstm(const ApgQuadParams *params, const ApgLstmPolicy *pol, int B, int H,
-               bool packed = false) {
-  if (!params || (!pol && !packed)) { set_error("params / policy is NULL"); return APG_ERR_ARG; }
+int check_lstm(const ApgQuadParams *params, int B, int H) {
+  if (!params) { set_error("params is NULL"); return APG_ERR_ARG; }
   if (B < 0) { set_error("B must be >= 0 (got %d)", B); return APG_ERR_ARG; }
   if ((long long)B * kH * 4 * kNX >= (1ll << 32) - 64) {
     set_error("B too large for 32-bit plane offsets (max %d); split the batch",
@@ -1751,8 +1747,13 @@ int check_lstm(const ApgQuadParams *params, const ApgLstmPolicy *pol, int B, int
     set_error("the fused LSTM rollout is built for horizon %d (got %d)", kH, H);
     return APG_ERR_ARG;
   }
-  if (pol && (!pol->conv_w || !pol->conv_b || !pol->w_ih || !pol->w_hh || !pol->b_ih ||
-              !pol->b_hh || !pol->w_out || !pol->b_out)) {
+  return APG_OK;
+}
+
+int check_policy(const ApgLstmPolicy *pol) {
+  if (!pol) { set_error("policy is NULL"); return APG_ERR_ARG; }
+  if (!pol->conv_w || !pol->conv_b || !pol->w_ih || !pol->w_hh || !pol->b_ih || !pol->b_hh ||
+      !pol->w_out || !pol->b_out) {
     set_error("policy weight pointer is NULL");
     return APG_ERR_ARG;
   }
@@ -1775,10 +1776,8 @@ int apg_quad_lstm_loss_partials_count(int B) {
   return B <= 0 ? 0 : ((B + kTrajPerBlock - 1) / kTrajPerBlock) * (kThreads / kWave);
 }
 
-// `policy` given: its tables are packed into `workspace` first; NULL: `workspace`
-// holds them already (apg_quad_lstm_pack_tables / apg_quad_lstm_step_tail)
-// rows given: the `_rows` entry points - state0 / in_ref (forward) and ref
-// (reverse) are read through rows->index; `state0`, `in_ref` are then OUTPUTS
+// rows given: state0 / in_ref (forward) and ref (reverse) are read through
+// rows->index; `state0`, `in_ref` are then OUTPUTS
 static int check_rows(const ApgBatchRows *rows, int B, int H, int ref_cols, bool reverse) {
   if (B > 0 && (!rows->index || (reverse ? !rows->ref : (!rows->state0 || !rows->in_ref)))) {
     set_error("rows: NULL index / tensor");
@@ -1799,18 +1798,16 @@ static int check_rows(const ApgBatchRows *rows, int B, int H, int ref_cols, bool
 }
 
 static int lstm_fwd(const ApgBatchRows *rows, const float *state0, const float *in_ref,
-                    const float *h0,
-                    const float *c0, float dt, const ApgQuadParams *params,
-                    const ApgLstmPolicy *policy, int B, int H, float *states,
-                    float *actions, float *x, float *gates, float *hc, float *hnew,
-                    unsigned *relu_mask, float *workspace, apg_stream_t stream,
-                    bool legacy_inplace_ref = false) {
-  if (int e = check_lstm(params, policy, B, H, true)) return e;
+                    const float *h0, const float *c0, float dt, const ApgQuadParams *params,
+                    const float *tables_fwd, int B, int H, float *states, float *actions,
+                    float *x, float *gates, float *hc, float *hnew, unsigned *relu_mask,
+                    apg_stream_t stream, bool legacy_inplace_ref) {
+  if (int e = check_lstm(params, B, H)) return e;
   if (rows)
     if (int e = check_rows(rows, B, H, 0, false)) return e;
   if (B == 0) return APG_OK;
   if (!state0 || !in_ref || !h0 || !c0 || !states || !actions || !x || !gates ||
-      !hc || !hnew || !relu_mask || !workspace) {
+      !hc || !hnew || !relu_mask || !tables_fwd) {
     set_error("NULL buffer");
     return APG_ERR_ARG;
   }
@@ -1819,24 +1816,19 @@ static int lstm_fwd(const ApgBatchRows *rows, const float *state0, const float *
   A.states = states, A.actions = actions, A.x = x, A.gates = gates, A.hc = hc;
   A.hnew = hnew;
   A.mask = relu_mask;
-  A.tables = workspace;
+  A.tables = tables_fwd;
   A.c = make_const(*params, dt);
   A.B = B;
-  A.index = nullptr, A.r_state0 = A.r_in_ref = nullptr;
+  A.index = nullptr, A.r_state0 = A.r_in_ref = nullptr, A.n_rows = 0;
   A.bytes_state0 = A.bytes_in_ref = 0u, A.ld_state0 = A.ld_in_ref = 0;
   if (rows) {
     A.index = rows->index, A.r_state0 = rows->state0, A.r_in_ref = rows->in_ref;
+    A.n_rows = rows->n_rows;
     A.ld_state0 = rows->ld_state0, A.ld_in_ref = rows->ld_in_ref;
     A.bytes_state0 = (unsigned)(rows->n_rows * (long long)rows->ld_state0 * 4);
     A.bytes_in_ref = (unsigned)(rows->n_rows * (long long)rows->ld_in_ref * 4);
   }
   hipStream_t st = (hipStream_t)stream;
-  if (policy) {
-    PackArgs P;
-    P.pol = *policy, P.dst = workspace;
-    hipLaunchKernelGGL(lstm_pack_fwd16_kernel, dim3((kFwd16Lds + 255) / 256), dim3(256),
-                       0, st, P);
-  }
   const dim3 grid((B + kTrajPerBlock - 1) / kTrajPerBlock);
   if (legacy_inplace_ref)
     hipLaunchKernelGGL((lstm_rollout_fwd_kernel<false, true>), grid, dim3(kThreads),
@@ -1850,54 +1842,34 @@ static int lstm_fwd(const ApgBatchRows *rows, const float *state0, const float *
   return check_launch("quad_lstm_rollout_fwd");
 }
 
-int apg_quad_lstm_rollout_fwd(const float *state0, const float *in_ref,
+int apg_quad_lstm_rollout_fwd(const ApgBatchRows *rows, const float *state0, const float *in_ref,
                               const float *h0, const float *c0, float dt,
-                              const ApgQuadParams *params,
-                              const ApgLstmPolicy *policy, int B, int H,
-                              float *states, float *actions, float *x,
-                              float *gates, float *hc, float *hnew,
-                              unsigned *relu_mask, float *workspace,
-                              apg_stream_t stream) {
-  if (!policy) { set_error("policy is NULL"); return APG_ERR_ARG; }
-  return lstm_fwd(nullptr, state0, in_ref, h0, c0, dt, params, policy, B, H, states, actions, x,
-                  gates,
-                  hc, hnew, relu_mask, workspace, stream);
+                              const ApgQuadParams *params, const float *tables_fwd, int B, int H,
+                              float *states, float *actions, float *x, float *gates, float *hc,
+                              float *hnew, unsigned *relu_mask, apg_stream_t stream) {
+  return lstm_fwd(rows, state0, in_ref, h0, c0, dt, params, tables_fwd, B, H, states, actions, x,
+                  gates, hc, hnew, relu_mask, stream, false);
 }
 
 int apg_quad_lstm_rollout_fwd_inplace_ref(const float *state0, const float *in_ref,
                                           const float *h0, const float *c0, float dt,
-                                          const ApgQuadParams *params,
-                                          const ApgLstmPolicy *policy, int B, int H,
-                                          float *states, float *actions, float *x,
+                                          const ApgQuadParams *params, const float *tables_fwd,
+                                          int B, int H, float *states, float *actions, float *x,
                                           float *gates, float *hc, float *hnew,
-                                          unsigned *relu_mask, float *workspace,
-                                          apg_stream_t stream) {
-  if (!policy) { set_error("policy is NULL"); return APG_ERR_ARG; }
-  return lstm_fwd(nullptr, state0, in_ref, h0, c0, dt, params, policy, B, H, states, actions, x,
-                  gates, hc, hnew, relu_mask, workspace, stream, true);
+                                          unsigned *relu_mask, apg_stream_t stream) {
+  return lstm_fwd(nullptr, state0, in_ref, h0, c0, dt, params, tables_fwd, B, H, states, actions,
+                  x, gates, hc, hnew, relu_mask, stream, true);
 }
 
-int apg_quad_lstm_rollout_fwd_packed(const float *state0, const float *in_ref,
-                                     const float *h0, const float *c0, float dt,
-                                     const ApgQuadParams *params, const float *tables_fwd,
-                                     int B, int H, float *states, float *actions, float *x,
-                                     float *gates, float *hc, float *hnew,
-                                     unsigned *relu_mask, apg_stream_t stream) {
-  return lstm_fwd(nullptr, state0, in_ref, h0, c0, dt, params, nullptr, B, H, states, actions, x,
-                  gates,
-                  hc, hnew, relu_mask, const_cast<float *>(tables_fwd), stream);
-}
-
-static int lstm_bwd(const ApgBatchRows *rows, const float *state0, const float *states,
-                    const float *actions,
-                    const float *ref, int ref_cols, const unsigned *relu_mask,
-                    const float *gates, const float *hc, float dt,
-                    const ApgQuadParams *params, const ApgQuadLossWeights *weights,
-                    const ApgLstmPolicy *policy, int B, int H, float *loss_partials,
-                    float *loss, float *d_gates, float *d_zout, float *d_conv,
-                    float *grad_state0, float *grad_h0, float *grad_c0, float *cot_amax,
-                    float *workspace, apg_stream_t stream) {
-  if (int e = check_lstm(params, policy, B, H, true)) return e;
+int apg_quad_lstm_rollout_bwd(const ApgBatchRows *rows, const float *state0, const float *states,
+                              const float *actions, const float *ref, int ref_cols,
+                              const unsigned *relu_mask, const float *gates, const float *hc,
+                              float dt, const ApgQuadParams *params,
+                              const ApgQuadLossWeights *weights, const float *tables_bwd, int B,
+                              int H, float *loss_partials, float *loss, float *d_gates,
+                              float *d_zout, float *d_conv, float *grad_state0, float *grad_h0,
+                              float *grad_c0, float *cot_amax, apg_stream_t stream) {
+  if (int e = check_lstm(params, B, H)) return e;
   if (!weights) { set_error("weights is NULL"); return APG_ERR_ARG; }
   if (ref_cols != 9 && ref_cols != 6) {
     set_error("ref_cols must be 9 or 6");
@@ -1912,31 +1884,26 @@ static int lstm_bwd(const ApgBatchRows *rows, const float *state0, const float *
     return APG_OK;
   }
   if (!state0 || !states || !actions || (!ref && !rows) || !relu_mask || !gates || !hc ||
-      !loss_partials || !d_gates || !d_zout || !d_conv || !workspace) {
+      !loss_partials || !d_gates || !d_zout || !d_conv || !tables_bwd) {
     set_error("NULL buffer");
     return APG_ERR_ARG;
   }
   BwdArgs A;
-  A.state0 = state0, A.states = states, A.actions = actions, A.ref = ref;
+  A.state0 = state0, A.states = states, A.actions = actions, A.ref = rows ? nullptr : ref;
   A.mask = relu_mask, A.gates = gates, A.hc = hc;
   A.loss_partials = loss_partials, A.d_gates = d_gates, A.d_zout = d_zout;
   A.d_conv = d_conv, A.grad_state0 = grad_state0, A.grad_h0 = grad_h0;
   A.grad_c0 = grad_c0;
   A.cot_amax = cot_amax;
-  A.tables = workspace;
+  A.tables = tables_bwd;
   A.c = make_const(*params, dt);
   A.w = *weights;
   A.B = B, A.ref_cols = ref_cols, A.vel_col = ref_cols == 9 ? 6 : 3;
-  A.index = nullptr, A.r_ref = nullptr, A.bytes_ref = 0u, A.ld_ref = 0;
+  A.index = nullptr, A.r_ref = nullptr, A.n_rows = 0, A.bytes_ref = 0u, A.ld_ref = 0;
   if (rows) {
-    A.index = rows->index, A.r_ref = rows->ref, A.ld_ref = rows->ld_ref;
+    A.index = rows->index, A.r_ref = rows->ref, A.n_rows = rows->n_rows;
+    A.ld_ref = rows->ld_ref;
     A.bytes_ref = (unsigned)(rows->n_rows * (long long)rows->ld_ref * 4);
-  }
-  if (policy) {
-    PackArgs P;
-    P.pol = *policy, P.dst = workspace;
-    hipLaunchKernelGGL(lstm_pack_bwd16_kernel, dim3((kBwd16Lds + 255) / 256), dim3(256),
-                       0, st, P);
   }
   const int blocks = (B + kTrajPerBlock - 1) / kTrajPerBlock;
   if (rows)
@@ -1949,38 +1916,6 @@ static int lstm_bwd(const ApgBatchRows *rows, const float *state0, const float *
   if (loss)
     return launch_reduce_partials(loss_partials, blocks * (kThreads / kWave), loss, st);
   return APG_OK;
-}
-
-int apg_quad_lstm_rollout_bwd(const float *state0, const float *states,
-                              const float *actions, const float *ref,
-                              int ref_cols, const unsigned *relu_mask,
-                              const float *gates, const float *hc, float dt,
-                              const ApgQuadParams *params,
-                              const ApgQuadLossWeights *weights,
-                              const ApgLstmPolicy *policy, int B, int H,
-                              float *loss_partials, float *loss, float *d_gates,
-                              float *d_zout, float *d_conv, float *grad_state0,
-                              float *grad_h0, float *grad_c0, float *cot_amax,
-                              float *workspace, apg_stream_t stream) {
-  if (!policy) { set_error("policy is NULL"); return APG_ERR_ARG; }
-  return lstm_bwd(nullptr, state0, states, actions, ref, ref_cols, relu_mask, gates, hc, dt,
-                  params, weights, policy, B, H, loss_partials, loss, d_gates, d_zout, d_conv,
-                  grad_state0, grad_h0, grad_c0, cot_amax, workspace, stream);
-}
-
-int apg_quad_lstm_rollout_bwd_packed(const float *state0, const float *states,
-                                     const float *actions, const float *ref, int ref_cols,
-                                     const unsigned *relu_mask, const float *gates,
-                                     const float *hc, float dt, const ApgQuadParams *params,
-                                     const ApgQuadLossWeights *weights,
-                                     const float *tables_bwd, int B, int H,
-                                     float *loss_partials, float *loss, float *d_gates,
-                                     float *d_zout, float *d_conv, float *grad_state0,
-                                     float *grad_h0, float *grad_c0, float *cot_amax,
-                                     apg_stream_t stream) {
-  return lstm_bwd(nullptr, state0, states, actions, ref, ref_cols, relu_mask, gates, hc, dt,
-                  params, weights, nullptr, B, H, loss_partials, loss, d_gates, d_zout, d_conv,
-                  grad_state0, grad_h0, grad_c0, cot_amax, const_cast<float *>(tables_bwd), stream);
 }
 
 static int gw_blocks(int B) {
@@ -1998,8 +1933,7 @@ int apg_quad_lstm_gate_wgrad_partials_floats(int B) {
 // back, chunks 0: nothing to add up)
 static int gate_wgrad_impl(const float *state0, const float *states, const float *in_ref,
                            const float *acts, const float *d_gates, const float *d_zout,
-                           const float *cot_amax, const ApgLstmPolicy *policy,
-                           float *tables_fwd, int B, int H,
+                           const float *cot_amax, const float *tables_fwd, int B, int H,
                            float *partials, float *ih_hh, float *b_ih, float *w_out,
                            float *b_out, apg_stream_t stream, apg::GwReduceArgs *defer) {
   using namespace apg;
@@ -2030,17 +1964,6 @@ static int gate_wgrad_impl(const float *state0, const float *states, const float
     set_error("apg_quad_lstm_gate_wgrad: NULL buffer");
     return APG_ERR_ARG;
   }
-  if (policy) {
-    if (!policy->conv_w || !policy->conv_b || !policy->w_ih || !policy->w_hh ||
-        !policy->b_ih || !policy->b_hh || !policy->w_out || !policy->b_out) {
-      set_error("policy weight pointer is NULL");
-      return APG_ERR_ARG;
-    }
-    PackArgs P;
-    P.pol = *policy, P.dst = tables_fwd;
-    hipLaunchKernelGGL(lstm_pack_fwd16_kernel, dim3((kFwd16Lds + 255) / 256), dim3(256), 0, st,
-                       P);
-  }
   GwArgs A;
   A.state0 = state0, A.states = states, A.in_ref = in_ref, A.acts = acts;
   A.d_gates = d_gates, A.d_zout = d_zout, A.cot_amax = cot_amax;
@@ -2070,40 +1993,11 @@ static int gate_wgrad_impl(const float *state0, const float *states, const float
 
 int apg_quad_lstm_gate_wgrad(const float *state0, const float *states, const float *in_ref,
                              const float *acts, const float *d_gates, const float *d_zout,
-                             const float *cot_amax, const ApgLstmPolicy *policy,
-                             float *tables_fwd, int B, int H,
+                             const float *cot_amax, const float *tables_fwd, int B, int H,
                              float *partials, float *ih_hh, float *b_ih, float *w_out,
                              float *b_out, apg_stream_t stream) {
-  return gate_wgrad_impl(state0, states, in_ref, acts, d_gates, d_zout, cot_amax, policy,
-                         tables_fwd, B, H, partials, ih_hh, b_ih, w_out, b_out, stream,
-                         nullptr);
-}
-
-int apg_quad_lstm_rollout_fwd_rows(const ApgBatchRows *rows, const float *h0, const float *c0,
-                                   float dt, const ApgQuadParams *params,
-                                   const float *tables_fwd, int B, int H, float *state0,
-                                   float *in_ref, float *states, float *actions, float *x,
-                                   float *gates, float *hc, float *hnew, unsigned *relu_mask,
-                                   apg_stream_t stream) {
-  if (!rows) { set_error("rows is NULL"); return APG_ERR_ARG; }
-  return lstm_fwd(rows, state0, in_ref, h0, c0, dt, params, nullptr, B, H, states, actions, x,
-                  gates, hc, hnew, relu_mask, const_cast<float *>(tables_fwd), stream);
-}
-
-int apg_quad_lstm_rollout_bwd_rows(const ApgBatchRows *rows, int ref_cols, const float *state0,
-                                   const float *states, const float *actions,
-                                   const unsigned *relu_mask, const float *gates,
-                                   const float *hc, float dt, const ApgQuadParams *params,
-                                   const ApgQuadLossWeights *weights, const float *tables_bwd,
-                                   int B, int H, float *loss_partials, float *loss,
-                                   float *d_gates, float *d_zout, float *d_conv,
-                                   float *grad_state0, float *grad_h0, float *grad_c0,
-                                   float *cot_amax, apg_stream_t stream) {
-  if (!rows) { set_error("rows is NULL"); return APG_ERR_ARG; }
-  return lstm_bwd(rows, state0, states, actions, nullptr, ref_cols, relu_mask, gates, hc, dt,
-                  params, weights, nullptr, B, H, loss_partials, loss, d_gates, d_zout, d_conv,
-                  grad_state0, grad_h0, grad_c0, cot_amax, const_cast<float *>(tables_bwd),
-                  stream);
+  return gate_wgrad_impl(state0, states, in_ref, acts, d_gates, d_zout, cot_amax, tables_fwd, B,
+                         H, partials, ih_hh, b_ih, w_out, b_out, stream, nullptr);
 }
 
 int apg_quad_lstm_conv_wgrad_partials_floats(int B) {
@@ -2173,9 +2067,8 @@ int apg_quad_lstm_conv_wgrad(const float *d_conv, const float *in_ref, const flo
 int apg_quad_lstm_wgrads(const float *state0, const float *states, const float *in_ref,
                          const float *acts, const float *d_gates, const float *d_zout,
                          const float *cot_amax, const float *d_conv, const float *st_all,
-                         const ApgLstmPolicy *policy, float *tables_fwd, int B, int H,
-                         float *gate_partials, float *conv_partials, float *ih_hh, float *b_ih,
-                         float *w_out, float *b_out, float *conv_w, float *conv_pos,
+                         const float *tables_fwd, int B, int H, float *gate_partials,
+                         float *conv_partials, float *ih_hh, float *b_ih, float *w_out, float *b_out, float *conv_w, float *conv_pos,
                          float *conv_b, const ApgLstmStepTail *finish, apg_stream_t stream) {
   using namespace apg;
   GwReduceArgs G;
@@ -2203,7 +2096,7 @@ int apg_quad_lstm_wgrads(const float *state0, const float *states, const float *
     U.on = 1, U.update = t.update != 0, U.lr = t.lr, U.momentum = t.momentum;
     U.grad = t.grad, U.param = t.param, U.mom = t.mom;
   }
-  if (int e = gate_wgrad_impl(state0, states, in_ref, acts, d_gates, d_zout, cot_amax, policy,
+  if (int e = gate_wgrad_impl(state0, states, in_ref, acts, d_gates, d_zout, cot_amax,
                               tables_fwd, B, H, gate_partials, ih_hh, b_ih, w_out, b_out, stream,
                               &G))
     return e;
@@ -2226,13 +2119,9 @@ int apg_quad_lstm_tables_floats(int reverse) { return reverse ? kBwd16Lds : kFwd
 
 int apg_quad_lstm_pack_tables(const ApgLstmPolicy *policy, float *tables_fwd,
                               float *tables_bwd, apg_stream_t stream) {
-  if (!policy || !tables_fwd || !tables_bwd) {
+  if (int e = check_policy(policy)) return e;
+  if (!tables_fwd || !tables_bwd) {
     set_error("apg_quad_lstm_pack_tables: NULL argument");
-    return APG_ERR_ARG;
-  }
-  if (!policy->conv_w || !policy->conv_b || !policy->w_ih || !policy->w_hh || !policy->b_ih ||
-      !policy->b_hh || !policy->w_out || !policy->b_out) {
-    set_error("policy weight pointer is NULL");
     return APG_ERR_ARG;
   }
   PackArgs F, R;
@@ -2313,7 +2202,8 @@ int apg_quad_lstm_closed_loop_env(const float *traj, int L, const float *h0, con
                                   float thresh_stable, int test_time, float *div, int *steps,
                                   float *drone, float *actions, float *start_states,
                                   float *workspace, apg_stream_t stream) {
-  if (int e = check_lstm(params, policy, B, H)) return e;
+  if (int e = check_lstm(params, B, H)) return e;
+  if (int e = check_policy(policy)) return e;
   if (learnt && (!learnt->linear_at || !learnt->w1 || !learnt->b1 || !learnt->w2 ||
                  !learnt->b2)) {
     set_error("learnt simulator: weight pointer is NULL");

@@ -323,6 +323,7 @@ struct WgArgs {
   // through the batch's index (the forward kernel then writes no planes of them)
   const long long *index;
   const float *r_feat, *r_in_ref;
+  long long n_rows;
   int ld_feat, ld_in_ref;
   unsigned bytes_feat, bytes_in_ref;
 };

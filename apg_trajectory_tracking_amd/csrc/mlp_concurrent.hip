@@ -364,8 +364,10 @@ __global__ __launch_bounds__(kThreads) void mlp_concurrent_bwd_tm_kernel(WgArgs 
       // load each, a half-wave on 32 consecutive floats of ONE row.  The wave's
       // 32 row numbers: one per lane, handed around by v_readlane.
       const int bw = b0 + wave * 32 + row;
-      const unsigned r_ = (unsigned)A.index[bw < B ? bw : B - 1];
-      const unsigned rf = r_ * (unsigned)A.ld_feat, ri = r_ * (unsigned)A.ld_in_ref;
+      // (byte offsets of the rows, kDead: a row number outside the data set)
+      const long long r_ = A.index[bw < B ? bw : B - 1];
+      const unsigned rf = row_offset(r_, A.n_rows, A.ld_feat);
+      const unsigned ri = row_offset(r_, A.n_rows, A.ld_in_ref);
       const auto sf = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(A.r_feat), 0,
                                                         (int)A.bytes_feat, 0x00020000);
       const auto si = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(A.r_in_ref), 0,
@@ -378,7 +380,8 @@ __global__ __launch_bounds__(kThreads) void mlp_concurrent_bwd_tm_kernel(WgArgs 
           for (int c = 0; c < 4; ++c) {
             const unsigned a0 = (unsigned)__builtin_amdgcn_readlane((int)rbase, c + 8 * g),
                            a1 = (unsigned)__builtin_amdgcn_readlane((int)rbase, c + 8 * g + 4);
-            const unsigned off = on ? ((hi ? a1 : a0) + (unsigned)col) * 4u : kDead;
+            const unsigned a = hi ? a1 : a0;
+            const unsigned off = on && a != kDead ? a + 4u * (unsigned)col : kDead;
             v[4 * g + c] = __builtin_bit_cast(
                 float, __builtin_amdgcn_raw_buffer_load_b32(rs, (int)off, 0, APG_PLANES_LD_AUX));
           }
@@ -711,9 +714,9 @@ int concurrent_train_step(
   A.c = make_const(*params, dt);
   A.w = *weights;
   A.B = B, A.ref_cols = ref_cols, A.vel_col = ref_cols == 9 ? 6 : 3;
-  A.index = nullptr, A.o_feat = A.o_in_ref = nullptr, A.win16 = 0;
+  A.index = nullptr, A.n_rows = 0, A.o_feat = A.o_in_ref = nullptr, A.win16 = 0;
   if (rows) {
-    A.index = rows->index;
+    A.index = rows->index, A.n_rows = rows->n_rows;
     A.o_feat = acts + pFeat * plane, A.o_in_ref = acts + pInr * plane;
     A.feat = rows->normed, A.in_ref = rows->in_ref, A.state0 = rows->state0, A.ref = rows->ref;
     A.ld_feat = rows->ld_normed, A.ld_in_ref = rows->ld_in_ref;
@@ -783,7 +786,7 @@ int concurrent_train_step(
   WgArgs W;
   W.acts = acts, W.mask = relu_mask, W.d_zout = d_zout, W.part = partials;
   W.tables = workspace + kCfLds, W.B = B, W.xmax = A.xmax;
-  W.index = nullptr, W.r_feat = W.r_in_ref = nullptr;
+  W.index = nullptr, W.r_feat = W.r_in_ref = nullptr, W.n_rows = 0;
   if (rows && B % kTrajPerBlock) {
     // A ragged last workgroup reads its dead trajectories' x^T entries past the
     // end of a plane - the head of the next plane: finite numbers, times a zero
@@ -796,6 +799,7 @@ int concurrent_train_step(
   }
   if (rows) {
     W.index = rows->index, W.r_feat = rows->normed, W.r_in_ref = rows->in_ref;
+    W.n_rows = rows->n_rows;
     W.ld_feat = A.ld_feat, W.ld_in_ref = A.ld_in_ref;
     W.bytes_feat = A.bytes_feat, W.bytes_in_ref = A.bytes_in_ref;
     hipLaunchKernelGGL(mlp_concurrent_bwd_tm_kernel<true>, dim3(blocks), dim3(kThreads), kLdsAll,

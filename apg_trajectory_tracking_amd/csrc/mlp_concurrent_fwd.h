@@ -38,6 +38,7 @@ struct ConcArgs {
   // and `index` [B] names this batch's rows; the feature and window planes the
   // reverse kernel reads are written to o_feat [15][B] / o_in_ref [90][B]
   const long long *index;
+  long long n_rows;
   float *o_feat, *o_in_ref;
   int ld_feat, ld_in_ref, ld_state0, ld_ref;
   int win16;   // the window rows start on 16-byte boundaries (gather_windows16_issue)
@@ -77,8 +78,8 @@ static_assert(kCfRowsLds * 4 <= 160 * 1024, "LDS");
 // the windows of the workgroup's 256 rows, 16 bytes per lane: element e = 64 n +
 // lane of [256][23] is chunk e % 23 of row e / 23
 __device__ __forceinline__ void gather_windows16_issue(float *dst, const int *rows,
-                                                       const float *base, unsigned bytes,
-                                                       int ld) {
+                                                       long long n_rows, const float *base,
+                                                       unsigned bytes, int ld) {
   typedef __attribute__((address_space(3))) void *lds_ptr_t;
   const auto r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base), 0, (int)bytes,
                                                    0x00020000);
@@ -90,7 +91,7 @@ __device__ __forceinline__ void gather_windows16_issue(float *dst, const int *ro
     // (the last chunk of a row ends 2 floats past the window: the row's own next
     // columns, or - last row of a data set whose rows are exactly the window -
     // out of range: zeros)
-    const unsigned voff = ((unsigned)rows[t] * (unsigned)ld + 4u * (unsigned)c) * 4u;
+    const unsigned voff = row_offset(rows[t], n_rows, ld, 4 * c);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_t)(dst + n * 256), 16, (int)voff, 0,
                                              0, 0);
   }
@@ -109,21 +110,27 @@ __global__ __launch_bounds__(kThreads) void mlp_concurrent_fwd_kernel(ConcArgs A
   extern __shared__ __attribute__((aligned(16))) float lds[];
   if (ROWS) {
     const int t = threadIdx.x, b_ = blockIdx.x * kTrajPerBlock + t;
-    // (a dead trajectory reads the batch's last row: finite data, never stored)
-    if (t < kTrajPerBlock)
-      reinterpret_cast<int *>(lds + zRows)[t] =
-          (APG_CF_KNOCKOUT & 16) ? (t & 7)
-          : (APG_CF_KNOCKOUT & 1) ? (b_ < A.B ? b_ : A.B - 1) : (int)A.index[b_ < A.B ? b_ : A.B - 1];
+    // (a dead trajectory reads the batch's last row: finite data, never stored;
+    // a row number outside the data set is kept as -1 / n_rows: the gathers'
+    // row_offset reads zeros for it)
+    if (t < kTrajPerBlock) {
+      const long long r = (APG_CF_KNOCKOUT & 16) ? (t & 7)
+                          : (APG_CF_KNOCKOUT & 1) ? (b_ < A.B ? b_ : A.B - 1)
+                                                  : A.index[b_ < A.B ? b_ : A.B - 1];
+      reinterpret_cast<int *>(lds + zRows)[t] = (int)(r < 0 ? -1 : r > A.n_rows ? A.n_rows : r);
+    }
     __syncthreads();
     const int *rows = reinterpret_cast<const int *>(lds + zRows);
     if (!(APG_CF_KNOCKOUT & 8)) {
     if (A.win16)
-      gather_windows16_issue(lds + zWin, rows, A.in_ref, A.bytes_in_ref, A.ld_in_ref);
+      gather_windows16_issue(lds + zWin, rows, A.n_rows, A.in_ref, A.bytes_in_ref, A.ld_in_ref);
     else
-      gather_rows_issue<kWinRow>(lds + zWin, rows, A.in_ref, A.bytes_in_ref, A.ld_in_ref,
-                                 kH * kRD);
-    gather_rows_issue<kRowPadF>(lds + zFeat, rows, A.feat, A.bytes_feat, A.ld_feat, kNF);
-    gather_rows_issue<kRowPadS>(lds + zS0, rows, A.state0, A.bytes_state0, A.ld_state0, 12);
+      gather_rows_issue<kWinRow>(lds + zWin, rows, A.n_rows, A.in_ref, A.bytes_in_ref,
+                                 A.ld_in_ref, kH * kRD);
+    gather_rows_issue<kRowPadF>(lds + zFeat, rows, A.n_rows, A.feat, A.bytes_feat, A.ld_feat,
+                                kNF);
+    gather_rows_issue<kRowPadS>(lds + zS0, rows, A.n_rows, A.state0, A.bytes_state0,
+                                A.ld_state0, 12);
     }
     fill_lds_issue(lds, A.tables, zWin);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -340,8 +347,8 @@ __global__ __launch_bounds__(kThreads) void mlp_concurrent_fwd_kernel(ConcArgs A
     // the tables are dead: the reference rows land over them while the rollout runs
     __syncthreads();
     if (!(APG_CF_KNOCKOUT & (4 | 8)))
-    gather_rows_issue<kRowPadW>(lds + zRef, reinterpret_cast<const int *>(lds + zRows), A.ref,
-                                A.bytes_ref, A.ld_ref, kH * A.ref_cols);
+    gather_rows_issue<kRowPadW>(lds + zRef, reinterpret_cast<const int *>(lds + zRows),
+                                A.n_rows, A.ref, A.bytes_ref, A.ld_ref, kH * A.ref_cols);
 #pragma unroll
     for (int i = 0; i < 12; ++i) s[i] = lds[zS0 + tl * kRowPadS + i];
   } else {

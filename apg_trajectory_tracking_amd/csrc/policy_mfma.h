@@ -19,6 +19,16 @@ namespace apg {
 
 constexpr unsigned kDead = 0xFFFFFFFCu;  // buffer offset beyond any tensor
 
+// Data-set rows named by 64-bit row numbers (ApgBatchRows.index): the byte offset
+// of column `col` (< ld) of row `idx` of a float32 tensor [n_rows][ld], or kDead
+// for a row number outside [0, n_rows) - a buffer load there reads zeros.  The
+// offset is formed in 32 bits only for a row in range (the host keeps the tensor
+// below 4 GiB): a negative or huge row number could wrap onto a valid row.
+__device__ __forceinline__ unsigned row_offset(long long idx, long long n_rows, int ld,
+                                               int col = 0) {
+  return idx < 0 || idx >= n_rows ? kDead : ((unsigned)idx * (unsigned)ld + (unsigned)col) * 4u;
+}
+
 // cache policy of the plane stores / loads (tuning knobs: experiment builds)
 #if !defined(APG_EXPERIMENT_BUILD) &&                                          \
     (defined(APG_PLANES_ST_AUX) || defined(APG_PLANES_LD_AUX))
@@ -168,10 +178,10 @@ __device__ __forceinline__ void fill_lds(float *lds, const float *src, int float
 // bank conflicts) by direct-to-LDS loads - one wave instruction moves 64
 // consecutive floats of that image, i.e. pieces of at most two source rows: a few
 // cache lines per instruction, where a lane-per-trajectory load touches 64.
-// rows: the workgroup's 256 source row numbers (LDS); R <= P columns are read,
-// the pad columns get zeros (offset kDead).
+// rows: the workgroup's 256 source row numbers (LDS; one outside [0, n_rows) reads
+// zeros); R <= P columns are read, the pad columns get zeros (offset kDead).
 template <int P>
-__device__ __forceinline__ void gather_rows_issue(float *dst, const int *rows,
+__device__ __forceinline__ void gather_rows_issue(float *dst, const int *rows, long long n_rows,
                                                   const float *base, unsigned bytes, int ld,
                                                   int R) {
   typedef __attribute__((address_space(3))) void *lds_ptr_t;
@@ -182,8 +192,7 @@ __device__ __forceinline__ void gather_rows_issue(float *dst, const int *rows,
   const int waves = blockDim.x >> 6;
   for (int n = wave; n < 4 * P; n += waves) {      // 256 P / 64 instructions
     const int e = n * 64 + lane, t = e / P, j = e - t * P;
-    const unsigned voff =
-        j < R ? ((unsigned)rows[t] * (unsigned)ld + (unsigned)j) * 4u : kDead;
+    const unsigned voff = j < R ? row_offset(rows[t], n_rows, ld, j) : kDead;
     __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_t)(dst + n * 64), 4, (int)voff, 0, 0,
                                              0);
   }

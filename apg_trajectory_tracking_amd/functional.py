@@ -1120,8 +1120,8 @@ def _conv_diag_problems(cv, refbuf, B, H, w_out, b_out):
 
 def _lstm_batch_rows(state0, in_ref, ref, index, H):
     """Round 6: with resident tables and a row index the LSTM sweeps read the data
-    set's tensors through the index themselves (apg_quad_lstm_rollout_fwd_rows /
-    _bwd_rows) instead of a gather pass.  Returns the ApgBatchRows of an indexed
+    set's tensors through the index themselves (the `rows` argument of
+    apg_quad_lstm_rollout_fwd / _bwd) instead of a gather pass.  Returns the ApgBatchRows of an indexed
     LSTM minibatch, or None where the tensors are not what the kernels read in
     place (then the gather pass runs)."""
     ok = lambda t: (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
@@ -1211,30 +1211,20 @@ class _QuadLstmRolloutLoss(torch.autograd.Function):
         gates = new(32, N)
         relu_mask = torch.empty(5, N, dtype=torch.int32, device=dev)
         st = stream_of(s0)
-        # resident operand tables (round 6, the trainers' step): packed once, kept
-        # current by the step's tail - the sweeps launch nothing but themselves
+        # the sweeps' operand tables: resident (round 6, the trainers' step: packed
+        # once, kept current by the step's tail) or packed for this call alone
         tables = getattr(ctx, "lstm_tables", None)
-        if tables is not None:
+        resident = tables is not None
+        if resident:
             tables.ensure(list(pw.values()), pol, st)
-        if rows is not None:
-            check(lib().apg_quad_lstm_rollout_fwd_rows(
-                ctypes.byref(rows), ptr(h0s), ptr(c0s), float(dt), ctypes.byref(params),
-                ptr(tables.fwd), B, H, ptr(s0), ptr(inr), ptr(states), ptr(actions), ptr(x),
-                ptr(gates), ptr(hc), ptr(hnew), relu_mask.data_ptr(), st),
-                "apg_quad_lstm_rollout_fwd_rows")
-        elif tables is not None:
-            check(lib().apg_quad_lstm_rollout_fwd_packed(
-                ptr(s0), ptr(inr), ptr(h0s), ptr(c0s), float(dt),
-                ctypes.byref(params), ptr(tables.fwd), B, H, ptr(states),
-                ptr(actions), ptr(x), ptr(gates), ptr(hc), ptr(hnew),
-                relu_mask.data_ptr(), st), "apg_quad_lstm_rollout_fwd_packed")
         else:
-            ws = new(lib().apg_quad_lstm_workspace_floats())
-            check(lib().apg_quad_lstm_rollout_fwd(
-                ptr(s0), ptr(inr), ptr(h0s), ptr(c0s), float(dt),
-                ctypes.byref(params), ctypes.byref(pol), B, H, ptr(states),
-                ptr(actions), ptr(x), ptr(gates), ptr(hc), ptr(hnew),
-                relu_mask.data_ptr(), ptr(ws), st), "apg_quad_lstm_rollout_fwd")
+            tables = LstmResidentTables(dev)
+            tables.pack(pol, st)
+        rows_p = None if rows is None else ctypes.byref(rows)
+        check(lib().apg_quad_lstm_rollout_fwd(
+            rows_p, ptr(s0), ptr(inr), ptr(h0s), ptr(c0s), float(dt), ctypes.byref(params),
+            ptr(tables.fwd), B, H, ptr(states), ptr(actions), ptr(x), ptr(gates), ptr(hc),
+            ptr(hnew), relu_mask.data_ptr(), st), "apg_quad_lstm_rollout_fwd")
         partials = new(max(1, lib().apg_quad_lstm_loss_partials_count(B)))
         loss = new(1)
         d_gates, d_zout, d_conv = new(32, N), new(4, N), new(_CONV_DIAG_PLANES, B)
@@ -1243,32 +1233,18 @@ class _QuadLstmRolloutLoss(torch.autograd.Function):
         g_s0 = new(12, B) if ctx.needs_input_grad[0] else None
         g_h0 = new(8, B) if ctx.needs_input_grad[3] else None
         g_c0 = new(8, B) if ctx.needs_input_grad[4] else None
-        if rows is not None:
-            check(lib().apg_quad_lstm_rollout_bwd_rows(
-                ctypes.byref(rows), ref.shape[2], ptr(s0), ptr(states), ptr(actions),
-                relu_mask.data_ptr(), ptr(gates), ptr(hc), float(dt), ctypes.byref(params),
-                ctypes.byref(weights), ptr(tables.bwd), B, H, ptr(partials), None,
-                ptr(d_gates), ptr(d_zout), ptr(d_conv), ptr(g_s0), ptr(g_h0), ptr(g_c0),
-                ptr(cot_amax), st), "apg_quad_lstm_rollout_bwd_rows")
+        # (resident tables: loss = NULL, the step's tail sums the partials)
+        check(lib().apg_quad_lstm_rollout_bwd(
+            rows_p, ptr(s0), ptr(states), ptr(actions), ptr(rf),
+            ref.shape[2] if rows is not None else rf.shape[1], relu_mask.data_ptr(),
+            ptr(gates), ptr(hc), float(dt), ctypes.byref(params), ctypes.byref(weights),
+            ptr(tables.bwd), B, H, ptr(partials), None if resident else ptr(loss),
+            ptr(d_gates), ptr(d_zout), ptr(d_conv), ptr(g_s0), ptr(g_h0), ptr(g_c0),
+            ptr(cot_amax), st), "apg_quad_lstm_rollout_bwd")
+        if resident:
             ctx.lstm_tail = (partials, loss, pw)
-        elif tables is not None:
-            # (loss = NULL: the step's tail sums the partials)
-            check(lib().apg_quad_lstm_rollout_bwd_packed(
-                ptr(s0), ptr(states), ptr(actions), ptr(rf), rf.shape[1],
-                relu_mask.data_ptr(), ptr(gates), ptr(hc), float(dt),
-                ctypes.byref(params), ctypes.byref(weights), ptr(tables.bwd), B, H,
-                ptr(partials), None, ptr(d_gates), ptr(d_zout), ptr(d_conv), ptr(g_s0),
-                ptr(g_h0), ptr(g_c0), ptr(cot_amax), st), "apg_quad_lstm_rollout_bwd_packed")
-            ctx.lstm_tail = (partials, loss, pw)
-        else:
-            check(lib().apg_quad_lstm_rollout_bwd(
-                ptr(s0), ptr(states), ptr(actions), ptr(rf), rf.shape[1],
-                relu_mask.data_ptr(), ptr(gates), ptr(hc), float(dt),
-                ctypes.byref(params),
-                ctypes.byref(weights), ctypes.byref(pol), B, H, ptr(partials),
-                ptr(loss), ptr(d_gates), ptr(d_zout), ptr(d_conv), ptr(g_s0),
-                ptr(g_h0), ptr(g_c0), ptr(cot_amax), ptr(ws), st), "apg_quad_lstm_rollout_bwd")
-        ctx.save_for_backward(refbuf, acts, d_gates, d_zout, d_conv, cot_amax, *pw.values())
+        ctx.save_for_backward(refbuf, acts, d_gates, d_zout, d_conv, cot_amax, *pw.values(),
+                              tables.fwd)
         ctx.input_grads = (g_s0, g_h0, g_c0)
         ctx.mark_non_differentiable(states, actions)
         ctx.dims = (B, H)
@@ -1292,7 +1268,8 @@ class LstmResidentTables:
     were made from (in-place version counter and storage address of the eight
     tensors), refreshed by apg_quad_lstm_step_tail after its update.  A write
     through `p.data` is not seen: `invalidate()` (TrainBase.run_epoch calls it at
-    the start of every epoch), as for the concurrent step's plan."""
+    the start of every epoch), as for the concurrent step's plan.  A caller
+    without resident tables makes a pair of its own and calls pack() once."""
 
     def __init__(self, dev):
         n = lib().apg_quad_lstm_tables_floats
@@ -1305,14 +1282,16 @@ class LstmResidentTables:
     def _key(tensors):
         return [(t._version, t.data_ptr()) for t in tensors]
 
+    def pack(self, pol, st):
+        check(lib().apg_quad_lstm_pack_tables(ctypes.byref(pol), ptr(self.fwd), ptr(self.bwd),
+                                              st), "apg_quad_lstm_pack_tables")
+        self.packs += 1
+
     def ensure(self, tensors, pol, st):
         key = self._key(tensors)
         # (a replayed graph runs no Python: a captured step always packs)
         if key != self.key or torch.cuda.is_current_stream_capturing():
-            check(lib().apg_quad_lstm_pack_tables(ctypes.byref(pol), ptr(self.fwd),
-                                                  ptr(self.bwd), st),
-                  "apg_quad_lstm_pack_tables")
-            self.packs += 1
+            self.pack(pol, st)
             self.key = key
 
     def refreshed(self, tensors):
@@ -1342,13 +1321,15 @@ def _lstm_param_grads(saved, dims, tail=None):
     """Weight gradients of the fused LSTM unroll from the saved planes: two
     trajectory-major kernels (gate / head weights with the conv inputs recomputed,
     conv weights from the diagonal sums); every gradient is a contiguous view of
-    one flat buffer (returned first), keyed by LSTM_NEW parameter name.
+    one flat buffer (returned first), keyed by LSTM_NEW parameter name; the
+    gate products read the forward tables the sweeps used (saved last).
     tail = (partials, loss, {C name: parameter}, tables, update): what follows
     the products is ONE launch (apg_quad_lstm_step_tail: gradients into place,
     momentum SGD if `update` = (lr, momentum, {parameter name: buffer}), the next
     step's tables, the loss) instead of three elementwise launches, the
     optimizer's, the loss reduction and two table packs."""
     refbuf, acts, d_gates, d_zout, d_conv, cot_amax = saved[:6]
+    tables_fwd = saved[14]
     B, H = dims
     dev = acts.device
     flat, gr = _flat_grads(dev, {
@@ -1360,14 +1341,6 @@ def _lstm_param_grads(saved, dims, tail=None):
     # h_new^T: ONE kernel that recomputes the conv part of x (round 6); the conv
     # weights' own gradient: two segmented products over the window planes
     st_all = refbuf[2 * H * 9:]
-    if tail is not None and tail[3] is not None:
-        pol, tab = None, tail[3].fwd          # resident tables (current: ensure())
-    else:
-        pw8 = dict(zip(("conv_w", "conv_b", "w_ih", "w_hh", "b_ih", "b_hh", "w_out",
-                        "b_out"), saved[6:14]))
-        pol = ctypes.byref(_capi.ApgLstmPolicy(**{k: ptr(v) for k, v in pw8.items()}))
-        tab = torch.empty(lib().apg_quad_lstm_workspace_floats(), dtype=torch.float32,
-                          device=dev)
     scratch = torch.empty(max(1, lib().apg_quad_lstm_gate_wgrad_partials_floats(B)),
                           dtype=torch.float32, device=dev)
     # the conv weights' gradient from the diagonal sums: one kernel over the planes
@@ -1399,7 +1372,7 @@ def _lstm_param_grads(saved, dims, tail=None):
             t.mom = G(**{c: ptr(bufs[n]) for c, n in names.items()})
     check(lib().apg_quad_lstm_wgrads(
         ptr(st_all[:12]), ptr(st_all[12:]), ptr(refbuf[:2 * H * 9]), ptr(acts),
-        ptr(d_gates), ptr(d_zout), ptr(cot_amax), ptr(d_conv), ptr(st_all), pol, ptr(tab),
+        ptr(d_gates), ptr(d_zout), ptr(cot_amax), ptr(d_conv), ptr(st_all), ptr(tables_fwd),
         B, H, ptr(scratch), ptr(scratch_c), ptr(ih_hh),
         ptr(gr["lstm.bias_ih"]), ptr(gr["fc_out.weight"]), ptr(gr["fc_out.bias"]),
         ptr(gr["conv_ref.weight"]), ptr(conv_pos), ptr(gr["conv_ref.bias"]),
@@ -1587,11 +1560,12 @@ def quad_recurrent_forward_inplace_ref(net, state0, in_ref, dt, params, h0=None,
                 map(ptr, pw))))
             require_device(s0, inr, h0s, c0s, *pw)
             x, gates, hc, hnew = new(15, N), new(32, N), new(16, N), new(8, N)
-            ws = new(lib().apg_quad_lstm_workspace_floats())
+            tables = LstmResidentTables(dev)
+            tables.pack(pol, st)
             check(lib().apg_quad_lstm_rollout_fwd_inplace_ref(
                 ptr(s0), ptr(inr), ptr(h0s), ptr(c0s), float(dt), ctypes.byref(params),
-                ctypes.byref(pol), B, H, ptr(states), ptr(actions), ptr(x), ptr(gates),
-                ptr(hc), ptr(hnew), mask.data_ptr(), ptr(ws), st),
+                ptr(tables.fwd), B, H, ptr(states), ptr(actions), ptr(x), ptr(gates),
+                ptr(hc), ptr(hnew), mask.data_ptr(), st),
                 "apg_quad_lstm_rollout_fwd_inplace_ref")
         else:
             names = ("w_s", "b_s", "conv_w", "conv_b", "w_1", "b_1", "w_2", "b_2", "w_3",

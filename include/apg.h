@@ -228,6 +228,18 @@ typedef struct ApgLstmPolicy {
  * conv on the matrix cores (one wave = 32 trajectories), hidden / cell state
  * and the sliding window in registers.
  * SoA only:  state0 [12][B], in_ref [2H][9][B], h0 / c0 [8][B].
+ * tables_fwd: the forward operand tables (apg_quad_lstm_pack_tables /
+ * apg_quad_lstm_step_tail, below); the sweep launches nothing but itself.
+ * rows: NULL - state0 and in_ref are the input planes.  Given - the minibatch is
+ * named by ROW NUMBERS of the whole data set's tensors (TrainBase.run_epoch's
+ * batch selection, scripts/train_base.py:191-194: `batch = data[index]`) and no
+ * gather pass runs: the sweep reads rows->state0 [n_rows][ld >= 12] and
+ * rows->in_ref [n_rows][ld >= 2H x 9] through rows->index [B] and WRITES their
+ * planes to state0 / in_ref for its followers (the reverse sweep,
+ * apg_quad_lstm_gate_wgrad, the conv-weight products); the reverse sweep reads
+ * rows->ref [n_rows][ld >= H x ref_cols] the same way instead of `ref`.  A row
+ * number outside [0, n_rows) reads zeros.  (rows->normed and rows->running_loss
+ * are not used.)
  * Outputs (caller-allocated, N = H*B, plane index = step*B + trajectory):
  *   states [H][12][B], actions [H][4][B],
  *   x [15][N]    the state features (LSTM inputs 0..14; round 6: the 160
@@ -235,16 +247,14 @@ typedef struct ApgLstmPolicy {
  *                recomputes them from the window for the weight gradient),
  *   gates [32][N] activated gates (i, f, g, o), hc [16][N] = h_prev, c_prev,
  *   hnew [8][N], relu_mask [5][N] (bit ch*8+pos = conv output > 0).
- * `workspace`: apg_quad_lstm_workspace_floats() floats of scratch (weights in
- * operand order); forward and reverse call may share it (same stream). */
+ * apg_quad_lstm_workspace_floats(): the scratch of the closed loop (below). */
+struct ApgBatchRows;
 int apg_quad_lstm_workspace_floats(void);
-int apg_quad_lstm_rollout_fwd(const float *state0, const float *in_ref,
-                              const float *h0, const float *c0, float dt,
-                              const ApgQuadParams *params,
-                              const ApgLstmPolicy *policy, int B, int H,
-                              float *states, float *actions, float *x,
-                              float *gates, float *hc, float *hnew,
-                              unsigned *relu_mask, float *workspace,
+int apg_quad_lstm_rollout_fwd(const struct ApgBatchRows *rows, const float *state0,
+                              const float *in_ref, const float *h0, const float *c0, float dt,
+                              const ApgQuadParams *params, const float *tables_fwd, int B,
+                              int H, float *states, float *actions, float *x, float *gates,
+                              float *hc, float *hnew, unsigned *relu_mask,
                               apg_stream_t stream);
 
 /* SURVEY.md 8a A4 `legacy_inplace_ref`: the same forward sweep with the loop of
@@ -256,16 +266,16 @@ int apg_quad_lstm_rollout_fwd(const float *state0, const float *in_ref,
  * the autoregressive-MLP counterpart. */
 int apg_quad_lstm_rollout_fwd_inplace_ref(const float *state0, const float *in_ref,
                                           const float *h0, const float *c0, float dt,
-                                          const ApgQuadParams *params,
-                                          const ApgLstmPolicy *policy, int B, int H,
-                                          float *states, float *actions, float *x,
+                                          const ApgQuadParams *params, const float *tables_fwd,
+                                          int B, int H, float *states, float *actions, float *x,
                                           float *gates, float *hc, float *hnew,
-                                          unsigned *relu_mask, float *workspace,
-                                          apg_stream_t stream);
+                                          unsigned *relu_mask, apg_stream_t stream);
 
 /* Reverse sweep (BPTT) of the above + quad_mpc_loss on ref[:, :H]
- * (scripts/train_drone.py:159-168).  ref [H][ref_cols][B].  Writes the loss
- * (loss_partials: apg_quad_lstm_loss_partials_count(B) floats) and the
+ * (scripts/train_drone.py:159-168).  ref [H][ref_cols][B] (read only when `rows`
+ * is NULL; rows: as for the forward sweep); tables_bwd: the reverse operand
+ * tables.  Writes the loss (loss_partials: apg_quad_lstm_loss_partials_count(B)
+ * floats; loss NULL: the partials are left for apg_quad_lstm_step_tail) and the
  * cotangent planes from which the host forms the weight gradients:
  *   d_gates [32][N] (gate pre-activations), d_zout [4][N] (head
  *   pre-activations), d_conv [720][B]: the conv pre-activation cotangents
@@ -287,17 +297,14 @@ int apg_quad_lstm_rollout_fwd_inplace_ref(const float *state0, const float *in_r
  *   dconv_b[ch] = sum_{k,n} P[ch][k][n]. */
 int apg_quad_lstm_loss_partials_count(int B);
 int apg_quad_lstm_cot_amax_floats(int B);
-int apg_quad_lstm_rollout_bwd(const float *state0, const float *states,
-                              const float *actions, const float *ref,
-                              int ref_cols, const unsigned *relu_mask,
-                              const float *gates, const float *hc, float dt,
-                              const ApgQuadParams *params,
-                              const ApgQuadLossWeights *weights,
-                              const ApgLstmPolicy *policy, int B, int H,
-                              float *loss_partials, float *loss, float *d_gates,
-                              float *d_zout, float *d_conv, float *grad_state0,
-                              float *grad_h0, float *grad_c0, float *cot_amax,
-                              float *workspace, apg_stream_t stream);
+int apg_quad_lstm_rollout_bwd(const struct ApgBatchRows *rows, const float *state0,
+                              const float *states, const float *actions, const float *ref,
+                              int ref_cols, const unsigned *relu_mask, const float *gates,
+                              const float *hc, float dt, const ApgQuadParams *params,
+                              const ApgQuadLossWeights *weights, const float *tables_bwd, int B,
+                              int H, float *loss_partials, float *loss, float *d_gates,
+                              float *d_zout, float *d_conv, float *grad_state0, float *grad_h0,
+                              float *grad_c0, float *cot_amax, apg_stream_t stream);
 
 /* Round 6: the gate and head weight gradients of the LSTM unroll from the
  * cotangent planes of the reverse sweep - what `loss.backward()` leaves in
@@ -312,18 +319,14 @@ int apg_quad_lstm_rollout_bwd(const float *state0, const float *states,
  *   state0 [12][B], states [H][12][B], in_ref [2H][9][B] as for the sweeps;
  *   acts [39][N] = x (15) | hc (16) | hnew (8) of apg_quad_lstm_rollout_fwd as
  *   ONE buffer; d_gates [32][N], d_zout [4][N], cot_amax of
- *   apg_quad_lstm_rollout_bwd.
- *   `policy` given: its forward tables are packed into `tables_fwd`
- *   (apg_quad_lstm_workspace_floats() floats) first; NULL: `tables_fwd` holds them
- *   (apg_quad_lstm_pack_tables / apg_quad_lstm_step_tail).
+ *   apg_quad_lstm_rollout_bwd; tables_fwd: the forward sweep's tables.
  *   partials: apg_quad_lstm_gate_wgrad_partials_floats(B) floats of scratch.
  * Outputs: ih_hh [32][183] = [dW_ih | dW_hh], b_ih [32] (= db_hh),
  *   w_out [4][8], b_out [4]. */
 int apg_quad_lstm_gate_wgrad_partials_floats(int B);
 int apg_quad_lstm_gate_wgrad(const float *state0, const float *states, const float *in_ref,
                              const float *acts, const float *d_gates, const float *d_zout,
-                             const float *cot_amax, const ApgLstmPolicy *policy,
-                             float *tables_fwd, int B, int H,
+                             const float *cot_amax, const float *tables_fwd, int B, int H,
                              float *partials, float *ih_hh, float *b_ih, float *w_out,
                              float *b_out, apg_stream_t stream);
 
@@ -359,10 +362,10 @@ struct ApgLstmStepTail;
 int apg_quad_lstm_wgrads(const float *state0, const float *states, const float *in_ref,
                          const float *acts, const float *d_gates, const float *d_zout,
                          const float *cot_amax, const float *d_conv, const float *st_all,
-                         const ApgLstmPolicy *policy, float *tables_fwd, int B, int H,
-                         float *gate_partials, float *conv_partials, float *ih_hh, float *b_ih,
-                         float *w_out, float *b_out, float *conv_w, float *conv_pos,
-                         float *conv_b, const struct ApgLstmStepTail *finish,
+                         const float *tables_fwd, int B, int H, float *gate_partials,
+                         float *conv_partials, float *ih_hh, float *b_ih, float *w_out,
+                         float *b_out, float *conv_w, float *conv_pos, float *conv_b,
+                         const struct ApgLstmStepTail *finish,
                          apg_stream_t stream);
 
 /* The LSTM training step without its small launches (round 6; the loop body of
@@ -370,28 +373,10 @@ int apg_quad_lstm_wgrads(const float *state0, const float *states, const float *
  * optimizer.step()).  The operand tables of the two sweeps live in caller-owned
  * buffers (apg_quad_lstm_tables_floats(0 | 1) floats) that apg_quad_lstm_pack_tables
  * fills from the parameters in ONE launch and apg_quad_lstm_step_tail refreshes
- * after its update: the `_packed` sweeps take the tables instead of the
- * parameters and launch nothing but themselves (loss may be NULL: the tail
- * reduces the partials). */
+ * after its update. */
 int apg_quad_lstm_tables_floats(int reverse);
 int apg_quad_lstm_pack_tables(const ApgLstmPolicy *policy, float *tables_fwd,
                               float *tables_bwd, apg_stream_t stream);
-int apg_quad_lstm_rollout_fwd_packed(const float *state0, const float *in_ref,
-                                     const float *h0, const float *c0, float dt,
-                                     const ApgQuadParams *params, const float *tables_fwd,
-                                     int B, int H, float *states, float *actions, float *x,
-                                     float *gates, float *hc, float *hnew,
-                                     unsigned *relu_mask, apg_stream_t stream);
-int apg_quad_lstm_rollout_bwd_packed(const float *state0, const float *states,
-                                     const float *actions, const float *ref, int ref_cols,
-                                     const unsigned *relu_mask, const float *gates,
-                                     const float *hc, float dt, const ApgQuadParams *params,
-                                     const ApgQuadLossWeights *weights,
-                                     const float *tables_bwd, int B, int H,
-                                     float *loss_partials, float *loss, float *d_gates,
-                                     float *d_zout, float *d_conv, float *grad_state0,
-                                     float *grad_h0, float *grad_c0, float *cot_amax,
-                                     apg_stream_t stream);
 /* What follows the weight-gradient products of the step, in one launch of one
  * workgroup: the gradients into their tensors (conv_ref.weight = grad.conv_w as
  * the window product left it minus the position part conv_pos [20][3];
@@ -606,32 +591,6 @@ int apg_quad_mlp_concurrent_train_step_rows(
     float *acts, unsigned *relu_mask, float *d_zout, float *loss_partials, float *loss,
     const ApgMlpPolicyGrads *grads, float *states, float *workspace, float *partials,
     const ApgMlpSgdUpdate *update, const ApgStepEvents *events, apg_stream_t stream);
-
-/* Round 6: the LSTM sweeps on a minibatch named by ROW NUMBERS of the whole data
- * set's tensors (TrainBase.run_epoch's batch selection,
- * scripts/train_base.py:191-194: `batch = data[index]`) - no gather pass.  The
- * forward sweep reads rows->state0 [n][ld >= 12] and rows->in_ref [n][ld >= 2H x 9]
- * through rows->index [B] (range-checked: a row number beyond n_rows reads zeros)
- * and WRITES their planes state0 [12][B], in_ref [2H][9][B] for its followers
- * (the reverse sweep, apg_quad_lstm_gate_wgrad, the conv-weight products); the
- * reverse sweep reads rows->ref [n][ld >= H x ref_cols] the same way.  Packed
- * tables only; everything else as apg_quad_lstm_rollout_fwd_packed / _bwd_packed.
- * (rows->normed, rows->running_loss are not used.) */
-int apg_quad_lstm_rollout_fwd_rows(const ApgBatchRows *rows, const float *h0, const float *c0,
-                                   float dt, const ApgQuadParams *params,
-                                   const float *tables_fwd, int B, int H, float *state0,
-                                   float *in_ref, float *states, float *actions, float *x,
-                                   float *gates, float *hc, float *hnew, unsigned *relu_mask,
-                                   apg_stream_t stream);
-int apg_quad_lstm_rollout_bwd_rows(const ApgBatchRows *rows, int ref_cols, const float *state0,
-                                   const float *states, const float *actions,
-                                   const unsigned *relu_mask, const float *gates,
-                                   const float *hc, float dt, const ApgQuadParams *params,
-                                   const ApgQuadLossWeights *weights, const float *tables_bwd,
-                                   int B, int H, float *loss_partials, float *loss,
-                                   float *d_gates, float *d_zout, float *d_conv,
-                                   float *grad_state0, float *grad_h0, float *grad_c0,
-                                   float *cot_amax, apg_stream_t stream);
 
 /* The AUTOREGRESSIVE training step in one call (round 5; configs[2] per rank):
  * TrainDrone.train_recurrent_model's unroll, loss and loss.backward()

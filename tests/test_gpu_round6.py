@@ -320,7 +320,7 @@ def test_config2_eight_shards_summed_equal_the_whole_batch(dev):
 
 
 @pytest.mark.parametrize("B", [37, 1000, 4100])
-def test_lstm_gate_weight_gradients_recompute_the_conv_inputs(dev, B):
+def test_lstm_gate_weight_gradients_recompute_the_conv_inputs_from_packed_tables(dev, B):
     """apg_quad_lstm_gate_wgrad (round 6): [dW_ih | dW_hh], db, dW_out, db_out of
     LSTM_NEW (neural_control/models/rnn.py:35-51; `loss.backward()` of
     scripts/train_base.py:200-204) from the reverse sweep's cotangent planes with
@@ -405,13 +405,15 @@ def test_lstm_gate_weight_gradients_recompute_the_conv_inputs(dev, B):
                    ctx.saved_tensors[6:14]))
     pol = ctypes.byref(ApgLstmPolicy(**{k: ptr(v) for k, v in pw8.items()}))
     new = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=dev)
-    tab = new(lib().apg_quad_lstm_workspace_floats())
+    tab, tab_bwd = (new(lib().apg_quad_lstm_tables_floats(r)) for r in (0, 1))
+    check(lib().apg_quad_lstm_pack_tables(pol, ptr(tab), ptr(tab_bwd), stream_of(acts)),
+          "pack_tables")
     st = refbuf[2 * H * 9:]
     ih_hh, b_ih, w_out, b_out = new(32, 183), new(32), new(4, 8), new(4)
     conv_w, conv_pos, conv_b = new(20, 27), new(20, 3), new(20)
     check(lib().apg_quad_lstm_gate_wgrad(
         ptr(st[:12]), ptr(st[12:]), ptr(refbuf[:2 * H * 9]), ptr(acts), ptr(d_gates),
-        ptr(d_zout), ptr(cot_amax), pol, ptr(tab), B, H,
+        ptr(d_zout), ptr(cot_amax), ptr(tab), B, H,
         ptr(new(max(1, lib().apg_quad_lstm_gate_wgrad_partials_floats(B)))),
         ptr(ih_hh), ptr(b_ih), ptr(w_out), ptr(b_out), stream_of(acts)), "gate_wgrad")
     check(lib().apg_quad_lstm_conv_wgrad(
@@ -427,7 +429,7 @@ def test_lstm_gate_weight_gradients_recompute_the_conv_inputs(dev, B):
     assert torch.equal(cw, gr["conv_ref.weight"])
 
 
-def test_lstm_wgrads_finish_argument_checks(dev):
+def test_lstm_wgrads_tables_only_finish_argument_checks(dev):
     """apg_quad_lstm_wgrads(finish = ...): the tensors the sum launch would write
     are checked before anything is launched - gradients always, parameters and
     momentum buffers when the update is asked for; a finish with B = 0 is an
@@ -439,7 +441,7 @@ def test_lstm_wgrads_finish_argument_checks(dev):
     full = G(**{n: ptr(buf) for n, _ in G._fields_})
     part = G(**{n: ptr(buf) for n, _ in G._fields_ if n != "w_hh"})
     call = lambda t, B=64: lib().apg_quad_lstm_wgrads(
-        *([None] * 9), None, None, B, 10, *([None] * 9), ctypes.byref(t), None)
+        *([None] * 9), None, B, 10, *([None] * 9), ctypes.byref(t), None)
     err = lambda: lib().apg_last_error_string().decode()
     assert call(_capi.ApgLstmStepTail(grad=part)) != 0 and "gradient" in err()
     assert call(_capi.ApgLstmStepTail(grad=full, update=1, param=full)) != 0
@@ -448,7 +450,7 @@ def test_lstm_wgrads_finish_argument_checks(dev):
     t = _capi.ApgLstmStepTail(grad=full, update=1, param=full, mom=full)
     out = [torch.zeros(32 * 183, device=dev) for _ in range(7)]
     rc = lib().apg_quad_lstm_wgrads(
-        *([None] * 9), None, None, 0, 10, None, None, *[ptr(o) for o in out],
+        *([None] * 9), None, 0, 10, None, None, *[ptr(o) for o in out],
         ctypes.byref(t), None)
     assert rc != 0 and "B > 0" in err()
 
@@ -457,7 +459,7 @@ def test_lstm_wgrads_finish_argument_checks(dev):
 def test_lstm_sweeps_read_the_batch_rows_through_the_index(dev, B, ref_cols):
     """TrainBase.run_epoch's batch selection (scripts/train_base.py:191-194:
     `batch = data[index]`) inside the LSTM sweeps (round 6:
-    apg_quad_lstm_rollout_fwd_rows / _bwd_rows): loss, every parameter gradient
+    the `rows` argument of apg_quad_lstm_rollout_fwd / _bwd): loss, every parameter gradient
     and the rollout equal the gather pass + plane sweeps TO THE BIT - the same
     numbers reach the same arithmetic - for a shuffled index with repeated rows
     out of a larger data set, ragged batches, both reference layouts."""
@@ -484,6 +486,52 @@ def test_lstm_sweeps_read_the_batch_rows_through_the_index(dev, B, ref_cols):
     assert torch.equal(out[0][0], out[1][0])
     assert torch.equal(out[0][1][:-1], out[1][1][:-1])
     assert torch.isfinite(out[1][1][:-1]).all() and out[1][1][:-1].abs().max() > 0
+
+
+@pytest.mark.parametrize("mode", ["lstm", "concurrent"])
+def test_rows_outside_the_data_set_read_zeros(dev, mode):
+    """include/apg.h: a row number outside [0, n_rows) reads zeros - also one
+    whose 32-bit byte offset would wrap onto a valid row (row * ld * 4 past 2^32,
+    or the int64 cut to 32 bits).  The rows step (LSTM sweeps, concurrent MLP
+    step) with such an index against the same step on the data set with one
+    all-zero row appended and the bad entries naming that row: loss and every
+    gradient bit for bit."""
+    from apg_trajectory_tracking_amd import functional as F, synthetic
+    from apg_trajectory_tracking_amd.dataset import state_preprocessing
+    from apg_trajectory_tracking_amd.dynamics.quad_dynamics_flightmare import (
+        FlightmareDynamics)
+    from apg_trajectory_tracking_amd.models.hutter_model import Net
+    from apg_trajectory_tracking_amd.models.rnn import LSTM_NEW
+    B = 1000
+    n = 2 * B + 17
+    d = synthetic.quad_polynomial_batch(n, H, DT, seed=7, ref_length=20)
+    st, inr, rf = (d[k].to(dev).contiguous() for k in ("state0", "in_ref", "ref"))
+    with torch.no_grad():
+        normed = state_preprocessing(st).contiguous()
+    g = torch.Generator().manual_seed(7)
+    index = torch.randint(0, n, (B,), generator=g)
+    remapped = index.clone()
+    for i, v in {3: -1, 100: n, 300: (1 << 30) + 5, 600: (1 << 32) + 7, 999: -(1 << 40)}.items():
+        index[i], remapped[i] = v, n
+    h0, c0 = (torch.randn(B, 8, generator=g).to(dev) for _ in range(2))
+    pad = lambda t: torch.cat((t, t.new_zeros((1,) + t.shape[1:])))
+    params = FlightmareDynamics().params
+    out = []
+    for data, idx in (((normed, st, inr, rf), index),
+                      (tuple(pad(t) for t in (normed, st, inr, rf)), remapped)):
+        torch.manual_seed(1)
+        if mode == "lstm":
+            net = LSTM_NEW(15, H, 9, 4, conv=1).to(dev)
+            loss, _, flat = F.quad_lstm_rollout_grads(net, *data[1:], DT, params, h0, c0,
+                                                      index=idx.to(dev))
+        else:
+            net = Net(15, H, 9, 4 * H, conv=1).to(dev)
+            plan = F.QuadConcurrentStepPlan(net, None, DT, params, rows=(*data, B))
+            loss, flat = plan.launch(index=idx.to(dev)), plan.flat
+        out.append((loss.clone(), flat[:-1].clone()))
+    assert torch.equal(out[0][0], out[1][0]) and torch.isfinite(out[0][0])
+    assert torch.equal(out[0][1], out[1][1])
+    assert torch.isfinite(out[0][1]).all() and out[0][1].abs().max() > 0
 
 
 @pytest.mark.parametrize("mode", ["ar", "lstm"])
