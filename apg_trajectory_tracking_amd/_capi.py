@@ -151,6 +151,11 @@ class ApgCartpoleParams(ctypes.Structure):
         "gravity")]
 
 
+class ApgCartpolePolicy(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in (
+        "w0", "b0", "w1", "b1", "w2", "b2", "w3", "b3", "w_out", "b_out")]
+
+
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 _F = ctypes.c_float
@@ -300,6 +305,10 @@ SIGNATURES = {
         _P, _P, _P, _P],
     "apg_cartpole_rollout_fwd": [_P, _P, _F, ctypes.POINTER(ApgCartpoleParams),
                                  _I, _I, _I, _P, _P],
+    "apg_cartpole_policy_workspace_floats": [],
+    "apg_cartpole_mlp_closed_loop": [
+        _P, _F, ctypes.POINTER(ApgCartpoleParams), ctypes.POINTER(ApgCartpolePolicy),
+        _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P],
     "apg_reduce_loss_partials": [_P, _I, _P, _P],
     "apg_loss_partials_count": [_I],
     "apg_stream_copy": [_P, _P, ctypes.c_longlong, _P],

@@ -3,6 +3,8 @@ sit on the hot path: `state_preprocessing` (dataset.py:207-220, called inside
 the autoregressive / LSTM loop at scripts/train_drone.py:144) and whole-tensor
 training sets that replace the per-sample DataLoader collate
 (scripts/train_base.py:132-137) - see `TensorBatches`."""
+import math
+
 import torch
 
 from . import functional as F
@@ -366,11 +368,38 @@ class SyntheticCartpoleDataset:
     `states` (policy input) and `labels` (simulation start state) hold the
     same values."""
 
-    def __init__(self, num_states=1000, seed=0, device="cuda"):
+    def __init__(self, num_states=1000, seed=0, device="cuda", dt=0.05,
+                 dynamics=None):
         from . import synthetic
         d = synthetic.cartpole_batch(int(num_states), 1, seed=seed)
         self.labels = d["state0"].to(torch.device(device))
         self.states = self.labels.clone()
+        self.num_sampled_states = int(num_states)
+        # resample_data: construct_states' environment (CartpoleDynamics()
+        # with the default parameters unless given, the trainer's dt) and its
+        # draws - a seeded torch.Generator, not numpy's global stream
+        self.dt = dt
+        self.dynamics = dynamics
+        self.generator = torch.Generator().manual_seed(int(seed) + 1)
+
+    def resample_data(self, num_states, thresh_div):
+        """construct_states (neural_control/environments/cartpole_env.py:
+        178-236) on the device: randomized runs, then balancing runs, taken in
+        run order and truncated to num_states; labels == states.  The draws
+        come from self.generator (draw_cartpole_states)."""
+        from .dynamics.cartpole_dynamics import CartpoleDynamics
+        if self.dynamics is None:
+            self.dynamics = CartpoleDynamics()
+        dev = self.states.device
+        draws = draw_cartpole_states(int(num_states), self.generator)
+        new = cartpole_states_from_draws(
+            {k: v.to(dev) for k, v in draws.items()}, int(num_states),
+            thresh_div, self.dt, self.dynamics.params)
+        if new.shape == self.states.shape:   # in place: loaders keep the tensors
+            self.states.copy_(new)
+            self.labels.copy_(new)
+        else:
+            self.states, self.labels = new, new.clone()
         self.num_sampled_states = int(num_states)
 
     def __len__(self):
@@ -378,3 +407,63 @@ class SyntheticCartpoleDataset:
 
     def __getitem__(self, index):
         return self.states[index], self.labels[index]
+
+
+# construct_states, cartpole_env.py:178-236: 80 % (rounded up to whole runs of
+# 20 steps) randomized runs, then balancing runs until num_states are reached.
+CARTPOLE_RANDOM_RUN = 20
+CARTPOLE_STATE_LIMITS = (2.4, 7.5, math.pi, 7.5)
+# A balancing run ends at its first state that is not upright; with random
+# actions U(-.5, .5) a run rarely lasts more than a few dozen steps.  Here a
+# run is cut after this many steps (the reference has no cap).
+CARTPOLE_BALANCE_CAP = 100
+
+
+def draw_cartpole_states(num_states, generator):
+    """The uniform draws of one construct_states call as CPU tensors:
+    rand_start [R, 4] / rand_act [R, 20] for the randomized runs, bal_start
+    [num_states, 4] / bal_act [num_states, CAP] for enough balancing runs (each
+    run yields at least one state unless it starts outside the threshold)."""
+    runs = 0
+    while runs * CARTPOLE_RANDOM_RUN < num_states * .8:
+        runs += 1
+    rnd = lambda *shape: torch.rand(*shape, generator=generator)
+    return dict(rand_start=rnd(runs, 4), rand_act=rnd(runs, CARTPOLE_RANDOM_RUN),
+                bal_start=rnd(num_states, 4),
+                bal_act=rnd(num_states, CARTPOLE_BALANCE_CAP))
+
+
+def cartpole_states_from_draws(draws, num_states, thresh_div, dt, params):
+    """construct_states from explicit uniform draws (draw_cartpole_states):
+    randomized runs start from _reset's U(-1, 1) * limits with x_dot and
+    theta_dot scaled by 0.2 and take actions (U - .5) * .2; balancing runs
+    start from (U - .5) * .1, take actions U - .5 and keep every state up to
+    and including the first one that is not upright (|theta| >= thresh_div; a
+    run that starts outside keeps none).  Both unrolls are one
+    apg_cartpole_rollout_fwd launch each.  Returns [num_states, 4]."""
+    limits = torch.tensor(CARTPOLE_STATE_LIMITS, device=draws["rand_start"].device)
+    s0 = (draws["rand_start"] * 2 - 1) * limits
+    s0[:, 1] *= .2
+    s0[:, 3] *= .2
+    acts = ((draws["rand_act"] - .5) * .2)[:, :, None]
+    rand_states = F.cartpole_rollout_fwd(s0.contiguous(), acts.contiguous(), dt,
+                                         params).reshape(-1, 4)
+    data = [rand_states]
+    need = num_states - rand_states.shape[0]
+    if need > 0:
+        b0 = (draws["bal_start"] - .5) * .1
+        bacts = (draws["bal_act"] - .5)[:, :, None]
+        bs = F.cartpole_rollout_fwd(b0.contiguous(), bacts.contiguous(), dt, params)
+        R, L = bs.shape[:2]
+        up = (bs[:, :, 2] > -thresh_div) & (bs[:, :, 2] < thresh_div)
+        # run r keeps steps k <= its first non-upright step (all L if none)
+        first_down = torch.where(up.all(1), torch.full((R,), L - 1, device=up.device),
+                                 (~up).float().argmax(1))
+        start_up = (b0[:, 2] > -thresh_div) & (b0[:, 2] < thresh_div)
+        length = torch.where(start_up, first_down + 1, torch.zeros_like(first_down))
+        keep = torch.arange(L, device=up.device)[None, :] < length[:, None]
+        data.append(bs[keep])            # row-major: run order, then step order
+    out = torch.cat(data)
+    if out.shape[0] < num_states:
+        raise RuntimeError("construct_states: the draws yield too few states")
+    return out[:num_states].contiguous()

@@ -1782,6 +1782,65 @@ def wing_mlp_closed_loop(net, targets, dt, params, mean, std, data_dt=0.05,
     return out
 
 
+CARTPOLE_MODES = {"balance": 0, "swingup": 1}
+
+
+def cartpole_mlp_closed_loop(net, state0, dt, params, max_steps=250,
+                             mode="balance", thresh_div=0.21, burn_in=50,
+                             want_trajectory=False):
+    """`Evaluator.evaluate_in_environment` (mode "balance") /
+    `evaluate_swingup` ("swingup") of scripts/evaluate_cartpole.py:79-318 for
+    B episodes in one launch (apg_cartpole_mlp_closed_loop).  net:
+    simple_model.Net(4, H) - the first action of the plan is applied;
+    state0 [B, 4] the start states.  Returns dict of device tensors: steps [B]
+    int32 (steps taken; balance: success + 1), upright [B] int32, vel_sum /
+    vel_sq [B] float64 (sum / sum of squares of the recorded |x_dot|: every
+    step (balance), the steps after burn_in (swing-up)), and with want_trajectory: states
+    [T, 4, B] (state after each step) and actions [T, B]; rows past an
+    episode's last step are zero."""
+    m = CARTPOLE_MODES.get(mode, mode)
+    if m not in (0, 1):
+        raise ValueError(f"mode must be 'balance' or 'swingup', got {mode!r}")
+    if state0.dim() != 2 or state0.shape[1] != 4 or state0.shape[0] < 1:
+        raise ValueError(f"state0 [B, 4] expected, got {tuple(state0.shape)}")
+    B, T = state0.shape[0], int(max_steps)
+    if T < 1:
+        raise ValueError(f"max_steps must be >= 1, got {T}")
+    dev = state0.device
+    layers = (net.fc0, net.fc1, net.fc2, net.fc3, net.fc_out)
+    shapes = ((32, 4), (64, 32), (64, 64), (32, 64))
+    if (any(tuple(l.weight.shape) != s for l, s in zip(layers, shapes))
+            or net.fc_out.weight.shape[1] != 32):
+        raise ValueError("closed loop needs simple_model.Net(4, H)")
+    pw = []
+    for l in layers:
+        pw += [_f32c(l.weight), _f32c(l.bias)]
+    s_in = _f32c(state0)
+    require_device(s_in, *pw)
+    s0 = to_soa(s_in)
+    _guard_policy_inputs("cart-pole closed loop", state0=state0)
+    pol = _capi.ApgCartpolePolicy(*[ptr(t) for t in pw])
+    steps = torch.zeros(B, dtype=torch.int32, device=dev)
+    upright = torch.zeros(B, dtype=torch.int32, device=dev)
+    vel_sum = torch.zeros(B, dtype=torch.float64, device=dev)
+    vel_sq = torch.zeros(B, dtype=torch.float64, device=dev)
+    states = actions = None
+    if want_trajectory:
+        states = torch.zeros(T, 4, B, dtype=torch.float32, device=dev)
+        actions = torch.zeros(T, B, dtype=torch.float32, device=dev)
+    ws = torch.empty(lib().apg_cartpole_policy_workspace_floats(),
+                     dtype=torch.float32, device=dev)
+    check(lib().apg_cartpole_mlp_closed_loop(
+        ptr(s0), float(dt), ctypes.byref(params), ctypes.byref(pol), B, T, m,
+        float(thresh_div), int(burn_in), steps.data_ptr(), upright.data_ptr(),
+        vel_sum.data_ptr(), vel_sq.data_ptr(), ptr(states), ptr(actions),
+        ptr(ws), stream_of(s0)), "apg_cartpole_mlp_closed_loop")
+    out = dict(steps=steps, upright=upright, vel_sum=vel_sum, vel_sq=vel_sq)
+    if want_trajectory:
+        out.update(states=states, actions=actions)
+    return out
+
+
 # --------------------------- concurrent mode with the policy inside (config 2)
 def note_in_kernel_update(tensors):
     """The kernels have written these tensors (parameters, momentum buffers)

@@ -32,20 +32,21 @@
  *    PACKED a lane moves a whole row with one 16-byte access (1 KiB per wave
  *    instruction) - a quarter of the memory instructions, which is what the
  *    one-wave-per-SIMD rollout kernel is paced by.
- *  - Operand range.  The dynamics, losses and adjoints are plain fp32 and take
- *    any finite input.  The entry points that run a POLICY NETWORK inside the
- *    kernel (apg_quad_mlp_*, apg_quad_lstm_*, apg_wing_policy_*,
- *    apg_wing_mlp_closed_loop) evaluate its layers on the 16-bit matrix pipe
- *    with every fp32 operand split into two fp16 terms (fp32 accuracy,
- *    csrc/policy_mfma16.h).  Cotangents are rescaled per trajectory inside the
- *    kernels; the first-layer inputs are not: normalised features, initial
- *    state, reference windows / trajectories and network weights must be
- *    FINITE with |x| < 16 384 (2^14; fp16 overflows at 65 504, the margin
- *    covers what a rollout adds to a state).  Smaller is always fine: the low
- *    term keeps an absolute accuracy of 2^-25.  The library cannot see device
- *    data at enqueue time - the caller checks (the Python host does, once per
- *    tensor version: functional._guard_policy_inputs raises ValueError); a
- *    violation yields inf / NaN losses, never a wrong finite number.
+ *  - Operand range.  The dynamics, losses and adjoints are plain fp32 and
+ *    take any finite input.  The entry points that run a POLICY NETWORK
+ *    inside the kernel (apg_quad_mlp_*, apg_quad_lstm_*, apg_wing_policy_*,
+ *    apg_wing_mlp_closed_loop, apg_cartpole_mlp_closed_loop) evaluate its
+ *    layers on the 16-bit matrix pipe with every fp32 operand split into two
+ *    fp16 terms (fp32 accuracy, csrc/policy_mfma16.h).  Cotangents are
+ *    rescaled per trajectory inside the kernels; the first-layer inputs are
+ *    not: normalised features, initial state, reference windows /
+ *    trajectories and network weights must be FINITE with |x| < 16 384 (2^14;
+ *    fp16 overflows at 65 504, the margin covers what a rollout adds to a
+ *    state).  Smaller is always fine: the low term keeps an absolute accuracy
+ *    of 2^-25.  The library cannot see device data at enqueue time - the
+ *    caller checks (the Python host does, once per tensor version:
+ *    functional._guard_policy_inputs raises ValueError); a violation yields
+ *    inf / NaN losses, never a wrong finite number.
  *    apg_planes_gemm / apg_linear_wgrad split into bf16 terms (fp32's exponent
  *    range): finite operands of any magnitude; a non-finite operand gives a
  *    non-finite (NaN) result where fp32 arithmetic would give inf.
@@ -952,6 +953,52 @@ int apg_cartpole_rollout_fwd_bwd(const float *state0, const float *actions,
 int apg_cartpole_rollout_fwd(const float *state0, const float *actions, float dt,
                              const ApgCartpoleParams *params, int B, int H,
                              int layout, float *states_out, apg_stream_t stream);
+
+/* The cart-pole controller simple_model.Net(4, H) (neural_control/models/
+ * simple_model.py:9-28: 4 -> 32 -> 64 -> 64 -> 32 -> H, tanh after every
+ * layer): device pointers to the plain row-major torch parameters. */
+typedef struct ApgCartpolePolicy {
+  const float *w0;     /* [32][4]  fc0.weight */
+  const float *b0;     /* [32] */
+  const float *w1;     /* [64][32] fc1.weight */
+  const float *b1;     /* [64] */
+  const float *w2;     /* [64][64] fc2.weight */
+  const float *b2;     /* [64] */
+  const float *w3;     /* [32][64] fc3.weight */
+  const float *b3;     /* [32] */
+  const float *w_out;  /* [H][32]  fc_out.weight (row 0 read) */
+  const float *b_out;  /* [H]      (entry 0 read) */
+} ApgCartpolePolicy;
+
+enum { APG_CARTPOLE_BALANCE = 0, APG_CARTPOLE_SWINGUP = 1 };
+
+/* Closed-loop evaluation of the cart-pole controller: Evaluator.
+ * evaluate_in_environment (mode APG_CARTPOLE_BALANCE) / evaluate_swingup
+ * (APG_CARTPOLE_SWINGUP) (scripts/evaluate_cartpole.py:79-318) for B episodes
+ * in one launch.  Per step: CartpoleWrapper.predict_actions (neural_control/
+ * controllers/network_wrapper.py:101-149: the raw state, column 0 zeroed by
+ * Net.forward, tanh; the first action of the plan is applied), cart_step
+ * (dt, params) and CartPoleEnv._step's theta wrap (neural_control/
+ * environments/cartpole_env.py:57-82).  From the second step on the cart
+ * position entering a step is 0 (the policy zeroes it in the environment's
+ * own state array in the reference).  state0 [4][B] (SoA).
+ * Balance: |x_dot| is recorded every step; the episode stops after the first
+ * step whose theta is not inside (-thresh_div, thresh_div).  Swing-up: never
+ * stops; |x_dot| is recorded for steps i > burn_in, where theta > 1 clears
+ * the upright flag.  Outputs [B]: steps = steps taken (balance: success + 1),
+ * upright = 1 unless cleared (balance: 1 iff the episode never failed),
+ * vel_sum / vel_sq = sum / sum of squares (fp64) of the recorded values;
+ * optional states [T][4][B] (state after each step) and actions [T][B].
+ * Rows of steps not taken are not written.  B >= 1, max_steps >= 1.
+ * workspace: apg_cartpole_policy_workspace_floats(). */
+int apg_cartpole_policy_workspace_floats(void);
+int apg_cartpole_mlp_closed_loop(const float *state0, float dt,
+                                 const ApgCartpoleParams *params,
+                                 const ApgCartpolePolicy *policy, int B, int max_steps,
+                                 int mode, float thresh_div, int burn_in, int *steps,
+                                 int *upright, double *vel_sum, double *vel_sq,
+                                 float *states, float *actions, float *workspace,
+                                 apg_stream_t stream);
 
 /* --------------------------------------------------------------- misc --- */
 /* loss[0] = fixed-order sum of partials[0..n) (one small kernel). */

@@ -1,0 +1,258 @@
+"""The cart-pole closed loop (apg_cartpole_mlp_closed_loop, evaluate_cartpole)
+without a GPU: a batched torch restatement of the reference's evaluator loop
+reproduces every recording of the REAL Evaluator (G19, tests/golden/
+make_golden_cartpole_eval.py); the evaluator's start states come from numpy's
+global stream in the reference's order; the construct_states restatement fed
+explicit draws matches a per-run CPU loop; the new entry point checks its
+arguments before any launch."""
+import ctypes
+import math
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import load_golden
+
+CASES = ["balance_zero", "balance_tight", "balance_tight_mod", "swingup",
+         "swingup_untrained"]
+DT = 0.05
+
+
+def case(g, name):
+    return {k[len(name) + 1:]: g[k] for k in g.files if k.startswith(name + ".")}
+
+
+def golden_net(g, which):
+    """The shipped controller (G9) or G19's seeded untrained Net, on CPU."""
+    from apg_trajectory_tracking_amd.models.simple_model import Net
+    if which == "untrained":
+        sd = {k[len("untrained.w."):]: torch.from_numpy(g[k])
+              for k in g.files if k.startswith("untrained.w.")}
+    else:
+        ck = load_golden("checkpoints.npz")
+        sd = {k[len("cartpole.w."):]: torch.from_numpy(ck[k])
+              for k in ck.files if k.startswith("cartpole.w.")}
+    net = Net(4, sd["fc_out.weight"].shape[0])
+    net.load_state_dict(sd)
+    return net
+
+
+def case_net(g, name):
+    return golden_net(g, "untrained" if name.endswith("untrained") else "shipped")
+
+
+def closed_loop_cpu(net, state0, dt, mp, max_steps, mode, thresh_div, burn_in):
+    """Batched restatement of evaluate_in_environment / evaluate_swingup
+    (scripts/evaluate_cartpole.py:79-318) on CPU: the dict of
+    functional.cartpole_mlp_closed_loop (states [T, 4, B], actions [T, B])."""
+    from oracle.torch_port import CartpoleOracle
+    dyn = CartpoleOracle(mp)
+    s = torch.as_tensor(state0, dtype=torch.float32).clone()
+    B, T = s.shape[0], int(max_steps)
+    pi = torch.tensor(math.pi, dtype=torch.float32)
+    alive = torch.ones(B, dtype=torch.bool)
+    upright = torch.ones(B, dtype=torch.bool)
+    steps = torch.zeros(B, dtype=torch.int32)
+    vel_sum = torch.zeros(B, dtype=torch.float64)
+    vel_sq = torch.zeros(B, dtype=torch.float64)
+    states = torch.zeros(T, 4, B)
+    actions = torch.zeros(T, B)
+    with torch.no_grad():
+        for k in range(T):
+            a = net(s.clone())[:, 0]          # Net zeroes column 0 of its input
+            if k > 0:                         # ... in the environment's state
+                s[:, 0] = 0
+            s = dyn(s, a[:, None], dt)
+            th = s[:, 2].clone()              # CartPoleEnv._step's wrap, fp32
+            s[:, 2] = torch.where(th > pi, th - 2 * pi, s[:, 2])
+            s[:, 2] = torch.where(th <= -pi, 2 * pi + th, s[:, 2])
+            states[k, :, alive] = s[alive].t()
+            actions[k, alive] = a[alive]
+            v = s[:, 1].abs().double()
+            if mode == "swingup":
+                if k > burn_in:
+                    vel_sum += v
+                    vel_sq += v * v
+                    upright &= ~(s[:, 2] > 1)
+            else:
+                vel_sum += torch.where(alive, v, 0)
+                vel_sq += torch.where(alive, v * v, 0)
+                down = ~((-thresh_div < s[:, 2]) & (s[:, 2] < thresh_div))
+                upright &= ~(down & alive)
+            steps[alive] = k + 1
+            if mode != "swingup":
+                alive &= ~down
+                if not alive.any():
+                    break
+    return dict(steps=steps, upright=upright.int(), vel_sum=vel_sum,
+                vel_sq=vel_sq, states=states, actions=actions)
+
+
+def stats(out, mode, burn_in, max_steps):
+    """The evaluator's returned dict from a closed-loop result."""
+    steps = np.asarray(out["steps"]).astype(np.int64)
+    if mode == "swingup":
+        n = len(steps) * (max_steps - burn_in - 1)
+        m = float(np.asarray(out["vel_sum"]).sum()) / n
+        return {"mean_vel": m, "std_vel": m}
+    n = steps.sum()
+    m = float(np.asarray(out["vel_sum"]).sum()) / n
+    var = float(np.asarray(out["vel_sq"]).sum()) / n - m * m
+    return {"mean_vel": m, "std_vel": math.sqrt(max(var, 0.0)),
+            "mean_stable": float(np.mean(steps - 1)),
+            "std_stable": float(np.std(steps - 1))}
+
+
+def check_against_case(c, out, max_steps=250, state_tol=1e-4):
+    """Step counts / flags equal; flown states within state_tol of each
+    column's range (+1e-6); statistics within 1e-4 relative."""
+    mode = "swingup" if int(c["swingup"]) else "balance"
+    steps = np.asarray(out["steps"])
+    assert steps.tolist() == c["steps"].tolist()
+    if mode == "swingup":
+        assert np.asarray(out["upright"]).tolist() == c["upright"].tolist()
+    else:
+        assert (steps - 1).tolist() == c["success"].tolist()
+    got = np.asarray(out["states"]).transpose(2, 0, 1)        # [B, T, 4]
+    scale = np.abs(c["states"]).reshape(-1, 4).max(0)
+    for i, n in enumerate(c["steps"]):
+        err = np.abs(got[i, :n] - c["states"][i, :n]).max(0)
+        assert np.all(err <= state_tol * scale + 1e-6), (i, err, scale)
+    acts = np.asarray(out["actions"]).T
+    for i, n in enumerate(c["steps"]):
+        assert np.abs(acts[i, :n] - c["actions"][i, :n]).max() <= state_tol + 1e-6
+    res = stats(out, mode, int(c["burn_in"]), max_steps)
+    for k, v in res.items():
+        assert abs(v - float(c[k])) <= 1e-4 * max(abs(float(c[k])), 1e-12), (k, v, c[k])
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_cpu_restatement_reproduces_reference_recordings(name):
+    g = load_golden("cartpole_closed_loop.npz")
+    c = case(g, name)
+    mode = "swingup" if int(c["swingup"]) else "balance"
+    mp = {"masspole": float(c["masspole"]), "length": float(c["length"])}
+    out = closed_loop_cpu(case_net(g, name), c["start"], DT, mp, 250, mode,
+                          float(c["thresh_div"]), int(c["burn_in"]))
+    check_against_case(c, {k: v.numpy() for k, v in out.items()})
+
+
+def test_recordings_cover_the_interesting_outcomes():
+    g = load_golden("cartpole_closed_loop.npz")
+    assert (case(g, "balance_zero")["steps"] == 250).all()
+    assert (case(g, "balance_tight")["steps"] < 250).all()
+    assert case(g, "swingup")["upright"].all()
+    assert not case(g, "swingup_untrained")["upright"].any()
+
+
+class _Params:   # CartPoleEnv needs `.params` only when it steps
+    params = None
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_start_states_and_next_draw_follow_numpy_stream(name):
+    """CartPoleEnv / Evaluator draw the reference's start states from numpy's
+    global stream and leave it where the reference leaves it."""
+    from apg_trajectory_tracking_amd.evaluate_cartpole import (
+        CartPoleEnv, CartpoleWrapper, Evaluator)
+    g = load_golden("cartpole_closed_loop.npz")
+    c = case(g, name)
+    np.random.seed(int(c["seed"]))
+    env = CartPoleEnv(_Params(), DT, thresh_div=float(c["thresh_div"]))
+    ev = Evaluator(CartpoleWrapper(case_net(g, name)), env)
+    ev.initialize_straight = int(c["straight"])
+    n = len(c["steps"])
+    starts = ev.swingup_starts(n) if int(c["swingup"]) else ev.balance_starts(n)
+    np.testing.assert_array_equal(starts, c["start"])
+    assert np.random.rand() == float(c["next_rand"])
+    if not int(c["swingup"]):    # the balance loop leaves the last _reset draw
+        np.testing.assert_array_equal(env.state, c["env_state"])
+
+
+def test_evaluator_quirks_without_a_launch():
+    from apg_trajectory_tracking_amd.evaluate_cartpole import (
+        CartPoleEnv, CartpoleWrapper, Evaluator)
+    g = load_golden("cartpole_closed_loop.npz")
+    env = CartPoleEnv(_Params(), DT)
+    ev = Evaluator(CartpoleWrapper(golden_net(g, "shipped")), env)
+    assert ev.evaluate_in_environment(nr_iters=0) == (0, 0, [])
+    with pytest.raises(ValueError):
+        ev.evaluate_in_environment(nr_iters=2, render=True)
+    with pytest.raises(ValueError):
+        ev.evaluate_swingup(nr_iters=2, render=True)
+    with pytest.raises(NotImplementedError):
+        Evaluator(CartpoleWrapper(golden_net(g, "shipped")), env, eval_dyn=object())
+
+
+def construct_states_loop(draws, num_states, thresh_div, dt, mp=None):
+    """construct_states (cartpole_env.py:178-236) run by run on CPU from the
+    explicit draws of dataset.draw_cartpole_states."""
+    from oracle.torch_port import CartpoleOracle
+    from apg_trajectory_tracking_amd.dataset import (
+        CARTPOLE_BALANCE_CAP, CARTPOLE_STATE_LIMITS)
+    dyn = CartpoleOracle(mp)
+    limits = torch.tensor(CARTPOLE_STATE_LIMITS)
+    data = []
+    for r in range(draws["rand_start"].shape[0]):
+        s = (draws["rand_start"][r] * 2 - 1) * limits
+        s[1] *= .2
+        s[3] *= .2
+        for k in range(draws["rand_act"].shape[1]):
+            s = dyn(s[None], ((draws["rand_act"][r, k] - .5) * .2).reshape(1, 1), dt)[0]
+            data.append(s)
+    r = 0
+    while len(data) < num_states:
+        s = (draws["bal_start"][r] - .5) * .1
+        k = 0
+        while -thresh_div < s[2] < thresh_div and k < CARTPOLE_BALANCE_CAP:
+            s = dyn(s[None], (draws["bal_act"][r, k] - .5).reshape(1, 1), dt)[0]
+            data.append(s)
+            k += 1
+        r += 1
+    return torch.stack(data)[:num_states]
+
+
+def test_construct_states_draw_shapes_and_reference_distribution():
+    from apg_trajectory_tracking_amd.dataset import draw_cartpole_states
+    g = load_golden("cartpole_closed_loop.npz")
+    n, thresh = int(g["construct.num"]), float(g["construct.thresh_div"])
+    d = draw_cartpole_states(n, torch.Generator().manual_seed(3))
+    assert d["rand_start"].shape == (16, 4) and d["rand_act"].shape == (16, 20)
+    loop = construct_states_loop(d, n, thresh, DT)
+    ref = g["construct.states"]
+    assert loop.shape == ref.shape == (n, 4)
+    # the balancing tail stays near upright in both; the random head spans theta
+    tail = slice(320, n)
+    assert np.abs(ref[tail, 2]).max() < 0.3 and loop[tail, 2].abs().max() < 0.3
+    assert np.abs(ref[:320, 2]).max() > 2 and loop[:320, 2].abs().max() > 2
+
+
+def test_new_entry_point_checks_arguments_before_launch():
+    from apg_trajectory_tracking_amd import _capi, functional as F
+    from apg_trajectory_tracking_amd.dynamics.cartpole_dynamics import (
+        CartpoleDynamics)
+    lib = _capi.lib()
+    p = CartpoleDynamics().params
+    pol = _capi.ApgCartpolePolicy(*([1] * 10))
+    buf = ctypes.c_void_p(1)
+
+    def call(policy=pol, B=4, T=10, mode=0, state0=buf, steps=buf, params=p):
+        return lib.apg_cartpole_mlp_closed_loop(
+            state0, 0.05, None if params is None else ctypes.byref(params),
+            None if policy is None else ctypes.byref(policy), B, T, mode, 0.2,
+            50, steps, buf, buf, buf, None, None, buf, None)
+    assert lib.apg_cartpole_policy_workspace_floats() > 0
+    assert call(policy=None) == -1
+    assert call(policy=_capi.ApgCartpolePolicy(*([1] * 9 + [0]))) == -1
+    assert b"NULL" in lib.apg_last_error_string()
+    assert call(params=None) == -1
+    assert call(B=0) == -1 and b"B and max_steps" in lib.apg_last_error_string()
+    assert call(B=-3) == -1
+    assert call(T=0) == -1
+    assert call(mode=2) == -1 and b"mode" in lib.apg_last_error_string()
+    assert call(state0=None) == -1 and b"NULL buffer" in lib.apg_last_error_string()
+    assert call(steps=None) == -1
+    assert call(B=1 << 20, T=1 << 12) == -1 and b"32-bit" in lib.apg_last_error_string()
+    with pytest.raises(ValueError):
+        F.cartpole_mlp_closed_loop(None, torch.zeros(3, 4), DT, p, mode="hover")

@@ -1,0 +1,211 @@
+"""The batched cart-pole closed-loop evaluation (apg_cartpole_mlp_closed_loop,
+evaluate_cartpole.Evaluator) on the GPU: against the recordings of the REAL
+Evaluator (G19), against the CPU restatement of tests/test_cartpole_eval_cpu.py
+at a batch of many workgroups, the trainer's evaluation hook and training loop
+(TrainCartpole.evaluate_model / train_control), and the device restatement of
+construct_states (SyntheticCartpoleDataset.resample_data)."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import load_golden
+from test_cartpole_eval_cpu import (CASES, DT, case, case_net, check_against_case,
+                                    closed_loop_cpu, construct_states_loop,
+                                    golden_net)
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "needs an MI355X"
+    return torch.device("cuda:0")
+
+
+def host(out):
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_kernel_and_evaluator_vs_reference_recordings(dev, name):
+    """(a) Every G19 case: the kernel on the recorded start states, and the
+    Evaluator drawing them itself from the same numpy seed."""
+    from apg_trajectory_tracking_amd import functional as F
+    from apg_trajectory_tracking_amd.dynamics.cartpole_dynamics import (
+        CartpoleDynamics)
+    from apg_trajectory_tracking_amd.evaluate_cartpole import (
+        CartPoleEnv, CartpoleWrapper, Evaluator)
+    g = load_golden("cartpole_closed_loop.npz")
+    c = case(g, name)
+    swing = int(c["swingup"])
+    mp = {"masspole": float(c["masspole"]), "length": float(c["length"])}
+    net = case_net(g, name).to(dev)
+    dyn = CartpoleDynamics(mp)
+    out = F.cartpole_mlp_closed_loop(
+        net, torch.from_numpy(c["start"]).to(dev), DT, dyn.params, max_steps=250,
+        mode="swingup" if swing else "balance", thresh_div=float(c["thresh_div"]),
+        burn_in=int(c["burn_in"]), want_trajectory=True)
+    # the untrained controller spins the pole (|theta_dot| up to 22 rad/s, the
+    # angle wrapping round): the ulp-level differences between the device's
+    # and the host's sin / cos / atan2 grow to 2.3e-4 of the angle's range
+    # over 250 steps there (measured); the shipped controller's flights keep
+    # the 1e-4 bound.  Steps and flags are compared exactly in every case.
+    check_against_case(c, host(out),
+                       state_tol=1e-3 if name == "swingup_untrained" else 1e-4)
+
+    np.random.seed(int(c["seed"]))
+    env = CartPoleEnv(dyn, DT, thresh_div=float(c["thresh_div"]))
+    ev = Evaluator(CartpoleWrapper(net), env)
+    ev.initialize_straight = int(c["straight"])
+    n = len(c["steps"])
+    if swing:
+        res = ev.evaluate_swingup(nr_iters=n, max_steps=250)
+    else:
+        res = ev.evaluate_in_environment(nr_iters=n, max_steps=250)
+    assert np.random.rand() == float(c["next_rand"])
+    np.testing.assert_array_equal(ev.last_flights["steps"].cpu().numpy(), c["steps"])
+    for k, v in res.items():
+        assert abs(v - float(c[k])) <= 1e-4 * abs(float(c[k])), (k, v, c[k])
+    if swing:
+        np.testing.assert_allclose(env.state, c["env_state"], rtol=0,
+                                   atol=1e-4 * np.abs(c["states"]).max())
+    else:
+        np.testing.assert_array_equal(env.state, c["env_state"])
+    # return_success: the per-flight values
+    np.random.seed(int(c["seed"]))
+    env = CartPoleEnv(dyn, DT, thresh_div=float(c["thresh_div"]))
+    ev = Evaluator(CartpoleWrapper(net), env)
+    ev.initialize_straight = int(c["straight"])
+    if swing:
+        np.testing.assert_array_equal(
+            ev.evaluate_swingup(nr_iters=n, return_success=1), c["upright"])
+    else:
+        success, velocities = ev.evaluate_in_environment(nr_iters=n, return_success=1)
+        np.testing.assert_array_equal(success, c["success"])
+        assert len(velocities) == int(c["steps"].sum())
+        assert ev.evaluate_in_environment(nr_iters=0) == (0, 0, [])
+
+
+def test_large_random_swingup_batch_vs_cpu_restatement(dev):
+    """(b) B = 65 536 + 37 random swing-up flights (many workgroups, a ragged
+    last wave) against the CPU restatement on a strided subset."""
+    from apg_trajectory_tracking_amd import functional as F
+    from apg_trajectory_tracking_amd.dynamics.cartpole_dynamics import (
+        CartpoleDynamics)
+    g = load_golden("cartpole_closed_loop.npz")
+    net = golden_net(g, "shipped")
+    B, T = 65536 + 37, 250
+    gen = torch.Generator().manual_seed(5)
+    u = torch.rand(B, 4, generator=gen)
+    s0 = (u * 2 - 1) * torch.tensor([2.4, 7.5, np.pi, 7.5])
+    s0[:, 0] = 0
+    s0[:, 1] *= .1
+    s0[:, 3] *= .1
+    sign = torch.where(torch.rand(B, generator=gen) > .5, -1.0, 1.0)
+    s0[:, 2] = sign * (2.8 + torch.rand(B, generator=gen) * .3)
+    out = host(F.cartpole_mlp_closed_loop(
+        net.to(dev), s0.to(dev), DT, CartpoleDynamics().params, max_steps=T,
+        mode="swingup", burn_in=100, want_trajectory=True))
+    assert (out["steps"] == T).all()
+    idx = np.unique(np.concatenate([np.arange(0, B, 251), np.arange(B - 37, B)]))
+    assert len(idx) >= 256
+    ref = closed_loop_cpu(golden_net(g, "shipped"), s0[idx], DT, {}, T, "swingup",
+                          .21, 100)
+    assert out["upright"][idx].tolist() == ref["upright"].tolist()
+    got = out["states"][:, :, idx]
+    want = ref["states"].numpy()
+    scale = np.abs(want).max((0, 2))
+    err = np.abs(got - want).max((0, 2))
+    assert np.all(err <= 1e-4 * scale + 1e-6), (err, scale)
+    np.testing.assert_allclose(out["vel_sum"][idx], ref["vel_sum"].numpy(), rtol=1e-4)
+
+
+def cartpole_config(tmp_path, **kw):
+    cfg = {"system": "cartpole", "delta_t": 0.05, "state_size": 4, "batch_size": 8,
+           "nr_epochs": 3, "sample_in": "eval_env", "resample_every": 3,
+           "thresh_div_start": 0.07, "thresh_div_step": 0.02, "thresh_div_end": 0.21,
+           "l2_lambda": 0, "modified_params": {}, "horizon": 10, "action_dim": 1,
+           "learning_rate_controller": 1e-9, "sample_data": 200, "suc_up_down": -1,
+           "save_name": str(tmp_path / "cp")}
+    cfg.update(kw)
+    return cfg
+
+
+def test_trainer_evaluate_model_and_train_control(dev, tmp_path, monkeypatch):
+    """(c) TrainCartpole with the shipped controller: evaluate_model fills
+    results_dict, runs the thresh_div ladder (0.07 -> 0.09 at epoch 0, -> 0.11
+    at epoch 3), resamples at epoch 2 and checkpoints epochs > 0;
+    train_control runs to finalize."""
+    monkeypatch.chdir(tmp_path)
+    from apg_trajectory_tracking_amd import train_cartpole as tc
+    from apg_trajectory_tracking_amd.dynamics.cartpole_dynamics import (
+        CartpoleDynamics)
+    g = load_golden("cartpole_closed_loop.npz")
+    cfg = cartpole_config(tmp_path)
+    tr = tc.TrainCartpole(CartpoleDynamics(), CartpoleDynamics(test_time=1), cfg)
+    tr.initialize_model(golden_net(g, "shipped"), device=dev)
+    assert cfg["thresh_div"] == 0.07
+    before = tr.state_data.states.clone()
+    ladder = []
+    for epoch in range(4):
+        res = tr.evaluate_model(epoch)
+        ladder.append(round(cfg["thresh_div"], 6))
+        assert res == (tr.results_dict["mean_vel"][-1], tr.results_dict["std_vel"][-1])
+        if epoch == 1:
+            assert torch.equal(tr.state_data.states, before)
+        if epoch == 2:
+            resampled = tr.state_data.states
+            assert not torch.equal(resampled, before)
+            assert torch.equal(tr.state_data.labels, resampled)
+            assert resampled.shape == (200, 4)
+            tr.run_epoch(train="controller")       # the loader sees the new rows
+    assert ladder == [0.09, 0.09, 0.09, 0.11]
+    assert tr.results_dict["evaluate_at"] == [0, 1, 2, 3]
+    for k in ("mean_vel", "std_vel", "mean_stable", "std_stable"):
+        assert len(tr.results_dict[k]) == 4
+    assert tr.results_dict["mean_stable"][0] == 249.0      # balances throughout
+    saved = sorted(os.listdir(tr.save_path))
+    assert saved == ["model_cartpole1", "model_cartpole2", "model_cartpole3"]
+
+    base = tmp_path / "base.pt"
+    torch.save(golden_net(g, "shipped").state_dict(), base)
+    cfg = cartpole_config(tmp_path, save_name=str(tmp_path / "tc"))
+    trainer = tc.train_control(str(base), cfg, swingup=1, device=dev)
+    assert cfg["learning_rate_controller"] == 1e-5
+    assert trainer.results_dict["evaluate_at"] == [0, 1, 2]
+    assert len(trainer.results_dict["loss_controller"]) == 3
+    assert os.path.exists(os.path.join(trainer.save_path, "model_cartpole"))
+    assert os.path.exists(os.path.join(trainer.save_path, "results.json"))
+
+
+@pytest.mark.parametrize("num,thresh", [(400, .11), (333, .07)])
+def test_resample_data_vs_cpu_loop(dev, num, thresh):
+    """(d) construct_states on the device fed explicit draws equals the CPU
+    loop; exactly num rows; every balancing run ends at its first state that
+    is not upright."""
+    from apg_trajectory_tracking_amd import dataset as ds
+    from apg_trajectory_tracking_amd.dynamics.cartpole_dynamics import (
+        CartpoleDynamics)
+    d = ds.draw_cartpole_states(num, torch.Generator().manual_seed(num))
+    got = ds.cartpole_states_from_draws({k: v.to(dev) for k, v in d.items()}, num,
+                                        thresh, DT, CartpoleDynamics().params).cpu()
+    want = construct_states_loop(d, num, thresh, DT)
+    assert got.shape == want.shape == (num, 4)
+    scale = want.abs().amax(0)
+    assert ((got - want).abs().amax(0) <= 1e-4 * scale + 1e-6).all()
+    # balancing part: a row outside the threshold is the last row of its run,
+    # so the next row (if any) starts a new run near upright
+    n_rand = d["rand_start"].shape[0] * ds.CARTPOLE_RANDOM_RUN
+    tail = got[n_rand:]
+    down = ~((tail[:, 2] > -thresh) & (tail[:, 2] < thresh))
+    assert down.any()
+    for i in torch.nonzero(down[:-1]).flatten().tolist():
+        assert abs(float(tail[i + 1, 2])) < 0.05 + 0.5 * thresh
+
+    data = ds.SyntheticCartpoleDataset(num, seed=1, device=dev)
+    rows = data.states
+    data.resample_data(num, thresh)
+    assert data.states is rows and data.num_sampled_states == num
+    assert torch.equal(data.states, data.labels)
