@@ -156,6 +156,15 @@ class ApgCartpolePolicy(ctypes.Structure):
         "w0", "b0", "w1", "b1", "w2", "b2", "w3", "b3", "w_out", "b_out")]
 
 
+CARTPOLE_LEARNT_FIELDS = ("max_force_mag", "masspole", "length", "friction",
+                          "total_mass", "polemass_length")
+
+
+class ApgCartpoleLearnt(ctypes.Structure):
+    """Device pointers to a LearntCartpoleDynamics module's own tensors."""
+    _fields_ = [(n, ctypes.c_void_p) for n in CARTPOLE_LEARNT_FIELDS + ("w1", "b1", "w2")]
+
+
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 _F = ctypes.c_float
@@ -308,6 +317,18 @@ SIGNATURES = {
     "apg_cartpole_policy_workspace_floats": [],
     "apg_cartpole_mlp_closed_loop": [
         _P, _F, ctypes.POINTER(ApgCartpoleParams), ctypes.POINTER(ApgCartpolePolicy),
+        _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "apg_cartpole_learnt_param_count": [],
+    "apg_cartpole_learnt_workspace_floats": [_I],
+    "apg_cartpole_learnt_step_fwd": [_P, _P, _F, ctypes.POINTER(ApgCartpoleLearnt), _I,
+                                     _P, _P],
+    "apg_cartpole_learnt_step_bwd": [_P, _P, _F, ctypes.POINTER(ApgCartpoleLearnt), _I,
+                                     _P, _P, _P, _P, _P, _P],
+    "apg_cartpole_learnt_rollout_fwd_bwd": [
+        _P, _P, _F, ctypes.POINTER(ApgCartpoleLearnt), _I, _I, _I, _P, _P, _P, _P, _P,
+        _P],
+    "apg_cartpole_learnt_mlp_closed_loop": [
+        _P, _F, ctypes.POINTER(ApgCartpoleLearnt), ctypes.POINTER(ApgCartpolePolicy),
         _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P],
     "apg_reduce_loss_partials": [_P, _I, _P, _P],
     "apg_loss_partials_count": [_I],

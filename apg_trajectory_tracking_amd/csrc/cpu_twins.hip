@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "apg_cpu.h"
+#include "cartpole_learnt_math.h"
 #include "cartpole_math.h"
 #include "quad_math.h"
 #include "wing_math.h"
@@ -488,6 +489,168 @@ int apg_cartpole_rollout_fwd_cpu(const float *state0, const float *actions, floa
       for (int i = 0; i < 4; ++i) states_out[ix.seq(b, k, i, H, 4)] = s[i];
     }
   }
+  return APG_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------- cartpole, learnt
+namespace {
+
+// the module's tensors -> step constants and the residual's unit rows (the
+// kernels' LDS image); false: no residual
+bool learnt_setup(const ApgCartpoleLearnt &m, float dt, CartLearntParams &p, CartConst &c,
+                  std::vector<float> &rows) {
+  p = CartLearntParams{*m.max_force_mag, *m.masspole, *m.length,
+                       *m.friction,      *m.total_mass, *m.polemass_length};
+  c = make_learnt_const(p, dt);
+  if (!m.w1) return false;
+  rows.resize(kCartResFloats);
+  for (int t = 0; t < kCartResFloats; ++t) {
+    const int u = t / kCartResRow, j = t - u * kCartResRow;
+    rows[t] = j < 5 ? m.w1[u * 5 + j] : j == 5 ? m.b1[u] : m.w2[(j - 6) * kCartResHidden + u];
+  }
+  return true;
+}
+
+int check_learnt(const ApgCartpoleLearnt *m, int B, bool need_residual) {
+  if (B < 0) return fail("B must be >= 0 (got %d)", B);
+  if (!m) return fail("model is NULL");
+  if (!m->max_force_mag || !m->masspole || !m->length || !m->friction || !m->total_mass ||
+      !m->polemass_length)
+    return fail("a physical parameter pointer is NULL");
+  const bool any = m->w1 || m->b1 || m->w2, all = m->w1 && m->b1 && m->w2;
+  if (any != all || (need_residual && !all))
+    return fail("w1 / b1 / w2 must be all given%s", need_residual ? "" : " or all NULL");
+  return APG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int apg_cartpole_learnt_step_fwd_cpu(const float *state, const float *action, float dt,
+                                     const ApgCartpoleLearnt *model, int B,
+                                     float *next_state) {
+  if (int e = check_learnt(model, B, false)) return e;
+  if (B > 0 && (!state || !action)) return fail("NULL input pointer");
+  if (!next_state) return fail("next_state is NULL");
+  CartLearntParams p;
+  CartConst c;
+  std::vector<float> rows;
+  const bool res = learnt_setup(*model, dt, p, c, rows);
+  for (int b = 0; b < B; ++b) {
+    float s[4] = {state[b * 4], state[b * 4 + 1], state[b * 4 + 2], state[b * 4 + 3]};
+    cart_learnt_step(s, action[b], c, res ? rows.data() : nullptr);
+    for (int i = 0; i < 4; ++i) next_state[b * 4 + i] = s[i];
+  }
+  return APG_OK;
+}
+
+int apg_cartpole_learnt_step_bwd_cpu(const float *state, const float *action, float dt,
+                                     const ApgCartpoleLearnt *model, int B,
+                                     const float *grad_next, float *grad_state,
+                                     float *grad_action, float *grad_params,
+                                     float *workspace) {
+  (void)workspace;
+  if (int e = check_learnt(model, B, false)) return e;
+  if (!grad_params) return fail("grad_params is NULL");
+  if (B > 0 && (!state || !action || !grad_next)) return fail("NULL input pointer");
+  CartLearntParams p;
+  CartConst c;
+  std::vector<float> rows;
+  const bool res = learnt_setup(*model, dt, p, c, rows);
+  float g[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  std::vector<float> gw(kCartResFloats, 0.f);   // unit-row order
+  for (int b = 0; b < B; ++b) {
+    float s[4], lam[4];
+    for (int i = 0; i < 4; ++i) s[i] = state[b * 4 + i], lam[i] = grad_next[b * 4 + i];
+    const float a = action[b];
+    const float z[5] = {s[0], s[1], s[2], s[3], a}, lam0[4] = {lam[0], lam[1], lam[2], lam[3]};
+    float tmp[4] = {s[0], s[1], s[2], s[3]};
+    const CartAux x = cart_step(tmp, a, c);
+    cart_param_adjoint(lam, a, s[1], s[3], x, p, dt, g);
+    const float ga = cart_learnt_step_adjoint(lam, s, a, x, c, res ? rows.data() : nullptr);
+    if (grad_state)
+      for (int i = 0; i < 4; ++i) grad_state[b * 4 + i] = lam[i];
+    if (grad_action) grad_action[b] = ga;
+    if (res)
+      for (int m = 0; m < kCartResHidden; ++m) {
+        float u[kCartResRow];
+        for (int j = 0; j < kCartResRow; ++j) u[j] = gw[m * kCartResRow + j];
+        cart_residual_unit_grads(&rows[m * kCartResRow], z, lam0, u);
+        for (int j = 0; j < kCartResRow; ++j) gw[m * kCartResRow + j] = u[j];
+      }
+  }
+  for (int i = 0; i < kCartPhysGrads; ++i) grad_params[i] = g[i];
+  for (int m = 0; m < kCartResHidden; ++m) {
+    const float *u = &gw[m * kCartResRow];
+    for (int j = 0; j < 5; ++j) grad_params[kCartGW1 + m * 5 + j] = u[j];
+    grad_params[kCartGB1 + m] = u[5];
+    for (int o = 0; o < 4; ++o) grad_params[kCartGW2 + o * kCartResHidden + m] = u[6 + o];
+  }
+  return APG_OK;
+}
+
+int apg_cartpole_learnt_rollout_fwd_bwd_cpu(const float *state0, const float *actions,
+                                            float dt, const ApgCartpoleLearnt *model,
+                                            int B, int H, int layout,
+                                            float *loss_partials, float *loss,
+                                            float *grad_actions, float *grad_state0,
+                                            float *states_out) {
+  if (int e = check_learnt(model, B, true)) return e;
+  if (layout != APG_LAYOUT_AOS && layout != APG_LAYOUT_SOA)
+    return fail("unknown layout %d", layout);
+  if (B > 0 && (!state0 || !actions)) return fail("NULL input pointer");
+  if (int e = check_h(H)) return e;
+  if (!loss_partials || !grad_actions)
+    return fail("loss_partials / grad_actions must not be NULL");
+  CartLearntParams p;
+  CartConst c;
+  std::vector<float> rows;
+  learnt_setup(*model, dt, p, c, rows);
+  const Idx ix{layout, (size_t)B};
+  // as apg_cartpole_rollout_fwd_bwd_cpu, each step the learnt one
+  const float wq[4] = {0.f, 3.f, 10.f, 1.f};
+  const double inv = H > 1 ? 1.0 / (double)(H - 1) : 0.0;
+  LossOut out{loss_partials, loss};
+  std::vector<float> pre((size_t)H * 4), st((size_t)H * 4);
+  for (int b = 0; b < B; ++b) {
+    float s0[4], s[4], l = 0.f;
+    for (int i = 0; i < 4; ++i) s0[i] = s[i] = state0[ix.vec(b, i, 4)];
+    for (int k = 0; k < H; ++k) {
+      const float a = actions[ix.seq(b, k, 0, H, 1)];
+      for (int i = 0; i < 4; ++i) pre[k * 4 + i] = s[i];
+      cart_learnt_step(s, a, c, rows.data());
+      const float f = k < H - 1 ? (float)(1.0 - inv * (double)k) : 0.f;
+      for (int i = 0; i < 4; ++i) {
+        st[k * 4 + i] = s[i];
+        if (states_out) states_out[ix.seq(b, k, i, H, 4)] = s[i];
+        const float d = s[i] - s0[i] * f;
+        l += (d * d) * wq[i];
+      }
+      l += 0.01f * a * a;
+    }
+    float lam[4] = {0.f, 0.f, 0.f, 0.f}, g0[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int k = H - 1; k >= 0; --k) {
+      const float a = actions[ix.seq(b, k, 0, H, 1)];
+      const float f = k < H - 1 ? (float)(1.0 - inv * (double)k) : 0.f;
+      for (int i = 0; i < 4; ++i) {
+        const float seed = 2.f * wq[i] * (st[k * 4 + i] - s0[i] * f);
+        lam[i] += seed;
+        g0[i] -= seed * f;
+      }
+      const float pk[4] = {pre[k * 4], pre[k * 4 + 1], pre[k * 4 + 2], pre[k * 4 + 3]};
+      float tmp[4] = {pk[0], pk[1], pk[2], pk[3]};
+      const CartAux x = cart_step(tmp, a, c);
+      grad_actions[ix.seq(b, k, 0, H, 1)] =
+          cart_learnt_step_adjoint(lam, pk, a, x, c, rows.data()) + 0.02f * a;
+    }
+    if (grad_state0)
+      for (int i = 0; i < 4; ++i) grad_state0[ix.vec(b, i, 4)] = lam[i] + g0[i];
+    out.add(b, B, l);
+  }
+  out.finish(B);
   return APG_OK;
 }
 

@@ -30,7 +30,13 @@
 // the 16-bit matrix pipe with fp16-split operands, the weights packed into
 // LDS tables by a pack launch.  Only row 0 of fc_out is evaluated
 // (action_seq[:, 0] is the action applied).
+//
+// cart_closed_loop_kernel<true> flies the LEARNT environment of the adapt flow
+// (LearntCartpoleDynamics, cartpole_learnt_math.h) with the same policy.
+#include <type_traits>
+
 #include "apg_device.h"
+#include "cartpole_learnt_math.h"
 #include "cartpole_math.h"
 #include "policy_mfma.h"
 #include "policy_mfma16.h"
@@ -169,9 +175,33 @@ __device__ __forceinline__ float cart_policy(const float (&s)[4], int hi, const 
   return tanhf(hi ? oth : z[0]);
 }
 
-__global__ __launch_bounds__(kMaxWaves * 64) void cart_closed_loop_kernel(CartLoopArgs A) {
+// The learnt environment (apg_cartpole_learnt_mlp_closed_loop): the module's
+// tensors; its residual's unit rows (cartpole_learnt_math.h) sit in LDS behind
+// the policy tables, its six physical parameters are read at kernel start.
+struct CartLearntLoopArgs : CartLoopArgs {
+  ApgCartpoleLearnt m;
+};
+
+template <bool LEARNT>
+__global__ __launch_bounds__(kMaxWaves * 64) void cart_closed_loop_kernel(
+    std::conditional_t<LEARNT, CartLearntLoopArgs, CartLoopArgs> A) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   fill_lds(lds, A.tables, kCartLds);
+  CartConst cc = A.c;
+  if constexpr (LEARNT) {
+    float *rows = lds + kCartLds;
+    for (int t = threadIdx.x; t < kCartResFloats; t += blockDim.x) {
+      const int u = t / kCartResRow, j = t - u * kCartResRow;
+      rows[t] = j < 5 ? A.m.w1[u * 5 + j] : j == 5 ? A.m.b1[u]
+                                                   : A.m.w2[(j - 6) * kCartResHidden + u];
+    }
+    cc = make_learnt_const(CartLearntParams{*A.m.max_force_mag, *A.m.masspole, *A.m.length,
+                                            *A.m.friction, *A.m.total_mass,
+                                            *A.m.polemass_length},
+                           A.c.dt);
+    __syncthreads();
+  }
+  const CartConst &c = cc;
   const int lane = threadIdx.x & 63, hi = lane >> 5;
   const LdsView L(lds, lane);
   const LdsView16 L16(lds, lane);
@@ -201,7 +231,21 @@ __global__ __launch_bounds__(kMaxWaves * 64) void cart_closed_loop_kernel(CartLo
     const unsigned vrec = (alive && hi == 0) ? vb : kDead;
     const float act = cart_policy(s, hi, L, L16);
     if (k > 0) s[0] = 0.f;          // the in-place zeroing of the policy input
-    cart_step(s, act, A.c);
+    if constexpr (LEARNT) {
+      // the residual on the pre-step state: each half-wave takes 32 of the 64
+      // hidden units, the two halves exchange their 4 sums (same order on both:
+      // both end with the same state)
+      const float z[5] = {s[0], s[1], s[2], s[3], act};
+      cart_step(s, act, c);
+      float add[4] = {0.f, 0.f, 0.f, 0.f};
+      int u0 = 32 * hi;
+      asm volatile("" : "+v"(u0));
+      cart_residual_add(add, z, lds + kCartLds, u0, u0 + 32);
+#pragma unroll
+      for (int o = 0; o < 4; ++o) s[o] += add[o] + other_half(add[o]);
+    } else {
+      cart_step(s, act, c);
+    }
     // CartPoleEnv._step: the comparisons with the ORIGINAL theta, in fp32
     const float th = s[2];
     if (th > pi) s[2] = th - two_pi;
@@ -237,24 +281,21 @@ __global__ __launch_bounds__(kMaxWaves * 64) void cart_closed_loop_kernel(CartLo
   }
 }
 
-}  // namespace
-}  // namespace apg
-
-using namespace apg;
-
-extern "C" {
-
-int apg_cartpole_policy_workspace_floats(void) { return kCartLds; }
-
-int apg_cartpole_mlp_closed_loop(const float *state0, float dt,
-                                 const ApgCartpoleParams *params,
-                                 const ApgCartpolePolicy *policy, int B, int max_steps,
-                                 int mode, float thresh_div, int burn_in, int *steps,
-                                 int *upright, double *vel_sum, double *vel_sq,
-                                 float *states, float *actions, float *workspace,
-                                 apg_stream_t stream) {
-  if (!params || !policy) {
-    set_error("params / policy is NULL");
+// argument checks and the two launches of both entry points; `learnt` NULL:
+// the analytic environment on `params`
+int closed_loop(const float *state0, float dt, const ApgCartpoleParams *params,
+                const ApgCartpoleLearnt *learnt, const ApgCartpolePolicy *policy, int B,
+                int max_steps, int mode, float thresh_div, int burn_in, int *steps,
+                int *upright, double *vel_sum, double *vel_sq, float *states,
+                float *actions, float *workspace, apg_stream_t stream) {
+  if (!(params || learnt) || !policy) {
+    set_error("%s / policy is NULL", learnt ? "model" : "params");
+    return APG_ERR_ARG;
+  }
+  if (learnt && (!learnt->max_force_mag || !learnt->masspole || !learnt->length ||
+                 !learnt->friction || !learnt->total_mass || !learnt->polemass_length ||
+                 !learnt->w1 || !learnt->b1 || !learnt->w2)) {
+    set_error("learnt model pointer is NULL");
     return APG_ERR_ARG;
   }
   if (!policy->w0 || !policy->b0 || !policy->w1 || !policy->b1 || !policy->w2 ||
@@ -278,11 +319,16 @@ int apg_cartpole_mlp_closed_loop(const float *state0, float dt,
     set_error("NULL buffer");
     return APG_ERR_ARG;
   }
-  CartLoopArgs A = {};
+  CartLearntLoopArgs A = {};
   A.state0 = state0, A.steps = steps, A.upright = upright;
   A.vel_sum = vel_sum, A.vel_sq = vel_sq, A.states = states, A.actions = actions;
   A.tables = workspace;
-  A.c = make_const(*params, dt);
+  if (learnt) {
+    A.c.dt = dt;          // (the rest is built in the kernel from the tensors)
+    A.m = *learnt;
+  } else {
+    A.c = make_const(*params, dt);
+  }
   A.thresh_div = thresh_div;
   A.B = B, A.T = max_steps, A.mode = mode, A.burn_in = burn_in;
   hipStream_t st = (hipStream_t)stream;
@@ -291,9 +337,52 @@ int apg_cartpole_mlp_closed_loop(const float *state0, float dt,
   // a small batch gets a small workgroup: the trainer's 10 episodes are one wave
   const int waves = (B + 31) / 32 < kMaxWaves ? (B + 31) / 32 : kMaxWaves;
   const int per_block = waves * 32;
-  hipLaunchKernelGGL(cart_closed_loop_kernel, dim3((B + per_block - 1) / per_block),
-                     dim3(waves * 64), kCartLds * sizeof(float), st, A);
-  return check_launch("cartpole_mlp_closed_loop");
+  const dim3 grid((B + per_block - 1) / per_block), block(waves * 64);
+  if (learnt)
+    hipLaunchKernelGGL(cart_closed_loop_kernel<true>, grid, block,
+                       (kCartLds + kCartResFloats) * sizeof(float), st, A);
+  else
+    hipLaunchKernelGGL(cart_closed_loop_kernel<false>, grid, block, kCartLds * sizeof(float),
+                       st, static_cast<const CartLoopArgs &>(A));
+  return check_launch(learnt ? "cartpole_learnt_mlp_closed_loop" : "cartpole_mlp_closed_loop");
+}
+
+}  // namespace
+}  // namespace apg
+
+using namespace apg;
+
+extern "C" {
+
+int apg_cartpole_policy_workspace_floats(void) { return kCartLds; }
+
+int apg_cartpole_mlp_closed_loop(const float *state0, float dt,
+                                 const ApgCartpoleParams *params,
+                                 const ApgCartpolePolicy *policy, int B, int max_steps,
+                                 int mode, float thresh_div, int burn_in, int *steps,
+                                 int *upright, double *vel_sum, double *vel_sq,
+                                 float *states, float *actions, float *workspace,
+                                 apg_stream_t stream) {
+  return closed_loop(state0, dt, params, nullptr, policy, B, max_steps, mode, thresh_div,
+                     burn_in, steps, upright, vel_sum, vel_sq, states, actions, workspace,
+                     stream);
+}
+
+int apg_cartpole_learnt_mlp_closed_loop(const float *state0, float dt,
+                                        const ApgCartpoleLearnt *model,
+                                        const ApgCartpolePolicy *policy, int B,
+                                        int max_steps, int mode, float thresh_div,
+                                        int burn_in, int *steps, int *upright,
+                                        double *vel_sum, double *vel_sq, float *states,
+                                        float *actions, float *workspace,
+                                        apg_stream_t stream) {
+  if (!model) {
+    set_error("model / policy is NULL");
+    return APG_ERR_ARG;
+  }
+  return closed_loop(state0, dt, nullptr, model, policy, B, max_steps, mode, thresh_div,
+                     burn_in, steps, upright, vel_sum, vel_sq, states, actions, workspace,
+                     stream);
 }
 
 }  // extern "C"

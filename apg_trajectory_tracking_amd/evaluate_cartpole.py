@@ -20,6 +20,13 @@ import torch
 from . import functional as F
 
 
+def _is_learnt(dynamics):
+    """A LearntCartpoleDynamics environment (the adapt flow flies the trained
+    simulator, scripts/train_cartpole.py:50-55)?"""
+    from .dynamics.cartpole_dynamics import LearntCartpoleDynamics
+    return isinstance(dynamics, LearntCartpoleDynamics)
+
+
 class CartpoleWrapper:
     """network_wrapper.py:101-149: the raw state (no normalisation) in, the
     action plan [1, horizon, action_dim] out."""
@@ -45,7 +52,8 @@ class CartpoleWrapper:
 
 class CartPoleEnv:
     """cartpole_env.py:32-115 without the renderer: `state` is a numpy array,
-    `_step` goes through the step kernel (apg_cartpole_step_fwd)."""
+    `_step` goes through the step kernel (apg_cartpole_step_fwd), or through
+    the module's forward when `dynamics` is a LearntCartpoleDynamics."""
 
     def __init__(self, dynamics, dt, thresh_div=.21):
         self.dynamics = dynamics
@@ -65,7 +73,11 @@ class CartPoleEnv:
         state = torch.tensor([list(self.state)], dtype=torch.float32, device=device)
         action = torch.as_tensor(action if is_torch else [action],
                                  dtype=torch.float32).reshape(1, 1).to(device)
-        nxt = F.cartpole_step(state, action, self.dt, self.dynamics.params)
+        if _is_learnt(self.dynamics):     # the module's forward, no grad
+            with torch.no_grad():
+                nxt = self.dynamics(state, action, self.dt)
+        else:
+            nxt = F.cartpole_step(state, action, self.dt, self.dynamics.params)
         self.state = nxt[0].cpu().numpy()
         # stay in bounds with theta (the reference's numpy scalar arithmetic)
         theta = self.state[2]
@@ -131,11 +143,13 @@ class Evaluator:
     def _fly(self, starts, max_steps, mode, burn_in):
         net = self.controller.net
         dev = next(net.parameters()).device
+        dyn = self.eval_env.dynamics
+        learnt = _is_learnt(dyn)
         out = F.cartpole_mlp_closed_loop(
             net, torch.from_numpy(starts).to(dev), self.eval_env.dt,
-            self.eval_env.dynamics.params, max_steps=max_steps, mode=mode,
+            None if learnt else dyn.params, max_steps=max_steps, mode=mode,
             thresh_div=self.eval_env.thresh_div, burn_in=burn_in,
-            want_trajectory=True)
+            want_trajectory=True, learnt=dyn if learnt else None)
         self.last_flights = out
         return out
 

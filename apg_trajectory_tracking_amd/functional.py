@@ -519,6 +519,142 @@ def cartpole_rollout_loss(state0, action_seq, dt, params):
     return _CartpoleRolloutLoss.apply(state0, action_seq, dt, params)
 
 
+# ------------------------------------------ through LearntCartpoleDynamics
+def _cartpole_learnt_tensors(dyn):
+    """The module's nine tensors in the order of ApgCartpoleLearnt: the six
+    physical [1] parameters of `cfg`, linear_state_1.weight / .bias,
+    linear_state_2.weight."""
+    return ([dyn.cfg[k] for k in _capi.CARTPOLE_LEARNT_FIELDS]
+            + [dyn.linear_state_1.weight, dyn.linear_state_1.bias,
+               dyn.linear_state_2.weight])
+
+
+def _cartpole_learnt_model(tensors, residual=True):
+    """ApgCartpoleLearnt over the module's own tensors (device pointers: the
+    kernels read the values when they run)."""
+    for t in tensors:
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise ValueError("LearntCartpoleDynamics tensors must be contiguous fp32 "
+                             "device tensors (module.to('cuda'))")
+    if (tuple(tensors[6].shape) != (64, 5) or tuple(tensors[7].shape) != (64,)
+            or tuple(tensors[8].shape) != (4, 64)
+            or any(t.numel() != 1 for t in tensors[:6])):
+        raise ValueError("LearntCartpoleDynamics: 5 -> 64 -> 4 residual and [1] "
+                         "parameters expected")
+    ptrs = [t.data_ptr() for t in tensors]
+    return _capi.ApgCartpoleLearnt(*ptrs[:6], *(ptrs[6:] if residual else (None,) * 3))
+
+
+def _cartpole_learnt_inputs(state, action):
+    if state.dim() != 2 or state.shape[1] != 4 or action.dim() != 2 \
+            or action.shape[1] != 1 or action.shape[0] != state.shape[0]:
+        raise ValueError(f"state [B, 4] / action [B, 1] expected, got "
+                         f"{tuple(state.shape)} and {tuple(action.shape)}")
+    for t in (state, action):
+        if not (t.is_cuda and t.dtype == torch.float32):
+            raise ValueError("LearntCartpoleDynamics takes fp32 device tensors, got "
+                             f"{t.dtype} on {t.device}")
+    return state.contiguous(), action.contiguous()
+
+
+class _CartpoleLearntStep(torch.autograd.Function):
+    """next = LearntCartpoleDynamics.forward(state, action, dt) (or its
+    physics alone): one launch forward; backward one reverse launch and the
+    fixed-order sum, every input's gradient from it."""
+
+    @staticmethod
+    def forward(ctx, state, action, dt, residual, *tensors):
+        s, a = _cartpole_learnt_inputs(state, action)
+        model = _cartpole_learnt_model(tensors, residual)
+        out = torch.empty_like(s)
+        check(lib().apg_cartpole_learnt_step_fwd(
+            ptr(s), ptr(a), float(dt), ctypes.byref(model), s.shape[0], ptr(out),
+            stream_of(s)), "apg_cartpole_learnt_step_fwd")
+        ctx.save_for_backward(s, a, *tensors)
+        ctx.meta = (float(dt), bool(residual))
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_next):
+        s, a, *tensors = ctx.saved_tensors
+        dt, residual = ctx.meta
+        B = s.shape[0]
+        g = _f32c(grad_next)
+        need = ctx.needs_input_grad
+        gs = torch.empty_like(s) if need[0] else None
+        ga = torch.empty_like(a) if need[1] else None
+        n = lib().apg_cartpole_learnt_param_count()
+        gp = torch.empty(n, dtype=torch.float32, device=s.device)
+        ws = torch.empty(max(lib().apg_cartpole_learnt_workspace_floats(B), 1),
+                         dtype=torch.float32, device=s.device)
+        model = _cartpole_learnt_model(tensors, residual)
+        check(lib().apg_cartpole_learnt_step_bwd(
+            ptr(s), ptr(a), dt, ctypes.byref(model), B, ptr(g), ptr(gs), ptr(ga),
+            ptr(gp), ptr(ws), stream_of(s)), "apg_cartpole_learnt_step_bwd")
+        parts = list(gp[:6].split(1)) + [gp[6:326].view(64, 5), gp[326:390],
+                                         gp[390:646].view(4, 64)]
+        grads = [p.view_as(t) if need[4 + i] and (residual or i < 6) else None
+                 for i, (p, t) in enumerate(zip(parts, tensors))]
+        return (gs, ga, None, None, *grads)
+
+
+def cartpole_learnt_step(dyn, state, action, dt, residual=True):
+    """LearntCartpoleDynamics.forward of `dyn` (residual False: its
+    simulate_cartpole) as one autograd op (apg_cartpole_learnt_step_fwd /
+    _bwd): gradients to state, action and every parameter that requires one."""
+    return _CartpoleLearntStep.apply(state, action, dt, residual,
+                                     *_cartpole_learnt_tensors(dyn))
+
+
+def cartpole_learnt_rollout_fwd_bwd(dyn, state0, actions, dt, layout="aos",
+                                    want_grad_state0=True, want_states=False,
+                                    want_loss=True, out=None):
+    """cartpole_rollout_fwd_bwd through the LearntCartpoleDynamics `dyn`
+    (apg_cartpole_learnt_rollout_fwd_bwd): make_reference + H learnt steps +
+    cartpole_loss_mpc + adjoint in one launch.  The module's tensors are read,
+    never differentiated."""
+    lay = _layout(layout)
+    if lay == LAYOUT_PACKED:
+        raise ValueError("the learnt cart-pole rollout takes 'aos' or 'soa' tensors")
+    require_device(state0, actions)
+    B, H, A = _seq_shape(actions, lay)
+    if A != 1 or _state_batch(state0, lay) != B:
+        raise ValueError("inconsistent rollout shapes")
+    o = _alloc_outs(out, state0.device, B, H, 4, 1, lay, state0, actions,
+                    want_grad_state0, want_states, want_loss)
+    model = _cartpole_learnt_model(_cartpole_learnt_tensors(dyn))
+    check(lib().apg_cartpole_learnt_rollout_fwd_bwd(
+        ptr(state0), ptr(actions), float(dt), ctypes.byref(model), B, H, lay,
+        ptr(o["loss_partials"]), ptr(o["loss"]), ptr(o["grad_actions"]),
+        ptr(o["grad_state0"]), ptr(o["states"]), stream_of(state0)),
+        "apg_cartpole_learnt_rollout_fwd_bwd")
+    return o
+
+
+class _CartpoleLearntRolloutLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, state0, action_seq, dt, dyn):
+        s, a = _f32c(state0), _f32c(action_seq)
+        res = cartpole_learnt_rollout_fwd_bwd(
+            dyn, s, a, dt, want_grad_state0=ctx.needs_input_grad[0])
+        ctx.save_for_backward(res["grad_actions"], res["grad_state0"])
+        return res["loss"].reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        ga, gs = ctx.saved_tensors
+        ga = ga * g if ctx.needs_input_grad[1] else None
+        gs = gs * g if (gs is not None and ctx.needs_input_grad[0]) else None
+        return gs, ga, None, None
+
+
+def cartpole_learnt_rollout_loss(dyn, state0, action_seq, dt):
+    """loss = cartpole_loss_mpc(unroll(dyn, state0, action_seq),
+    make_reference(state0), action_seq) as ONE kernel; gradients to
+    action_seq and state0 (the simulator is frozen in the controller phase)."""
+    return _CartpoleLearntRolloutLoss.apply(state0, action_seq, dt, dyn)
+
+
 # ------------------------------------------------------ pre-bound launches
 def reduce_loss_partials(partials, loss=None):
     """loss[0] = fixed-order sum of `partials` (apg_reduce_loss_partials)."""
@@ -1787,7 +1923,7 @@ CARTPOLE_MODES = {"balance": 0, "swingup": 1}
 
 def cartpole_mlp_closed_loop(net, state0, dt, params, max_steps=250,
                              mode="balance", thresh_div=0.21, burn_in=50,
-                             want_trajectory=False):
+                             want_trajectory=False, learnt=None):
     """`Evaluator.evaluate_in_environment` (mode "balance") /
     `evaluate_swingup` ("swingup") of scripts/evaluate_cartpole.py:79-318 for
     B episodes in one launch (apg_cartpole_mlp_closed_loop).  net:
@@ -1797,7 +1933,9 @@ def cartpole_mlp_closed_loop(net, state0, dt, params, max_steps=250,
     vel_sq [B] float64 (sum / sum of squares of the recorded |x_dot|: every
     step (balance), the steps after burn_in (swing-up)), and with want_trajectory: states
     [T, 4, B] (state after each step) and actions [T, B]; rows past an
-    episode's last step are zero."""
+    episode's last step are zero.
+    learnt: a LearntCartpoleDynamics module - the environment steps through
+    its forward (apg_cartpole_learnt_mlp_closed_loop; `params` is not read)."""
     m = CARTPOLE_MODES.get(mode, mode)
     if m not in (0, 1):
         raise ValueError(f"mode must be 'balance' or 'swingup', got {mode!r}")
@@ -1830,11 +1968,16 @@ def cartpole_mlp_closed_loop(net, state0, dt, params, max_steps=250,
         actions = torch.zeros(T, B, dtype=torch.float32, device=dev)
     ws = torch.empty(lib().apg_cartpole_policy_workspace_floats(),
                      dtype=torch.float32, device=dev)
-    check(lib().apg_cartpole_mlp_closed_loop(
-        ptr(s0), float(dt), ctypes.byref(params), ctypes.byref(pol), B, T, m,
+    if learnt is None:
+        name, env = "apg_cartpole_mlp_closed_loop", params
+    else:
+        name = "apg_cartpole_learnt_mlp_closed_loop"
+        env = _cartpole_learnt_model(_cartpole_learnt_tensors(learnt))
+    check(getattr(lib(), name)(
+        ptr(s0), float(dt), ctypes.byref(env), ctypes.byref(pol), B, T, m,
         float(thresh_div), int(burn_in), steps.data_ptr(), upright.data_ptr(),
         vel_sum.data_ptr(), vel_sq.data_ptr(), ptr(states), ptr(actions),
-        ptr(ws), stream_of(s0)), "apg_cartpole_mlp_closed_loop")
+        ptr(ws), stream_of(s0)), name)
     out = dict(steps=steps, upright=upright, vel_sum=vel_sum, vel_sq=vel_sq)
     if want_trajectory:
         out.update(states=states, actions=actions)

@@ -3,8 +3,16 @@ to the APG hot path: `run_epoch` (:118-165) with `make_reference` (:103-110).
 The controller branch is one fused HIP launch (make_reference + H x cartpole
 dynamics + cartpole_loss_mpc + adjoint).  Quirks kept: the policy ends in
 tanh with NO sigmoid (:127-130), `simple_model.Net` zeroes column 0 of its
-input in place, run_epoch has no `epoch` argument and divides by the last
-batch index (:163).
+input in place, run_epoch divides by the last batch index (:163).
+
+With a LearntCartpoleDynamics as train dynamics (`train_norm_dynamics`, the
+reference's adapt mode :245-262) run_epoch also fits the simulator
+(train="dynamics") and the controller branch runs through it, fused into one
+launch (apg_cartpole_learnt_rollout_fwd_bwd).  Two deliberate deviations make
+that loop run at all: run_epoch accepts the `epoch` that TrainBase.run_dynamics
+passes (the reference's raises TypeError), and init_optimizer builds the
+simulator's optimizer for any nn.Module simulator (the reference's only for
+the quad / wing learnt classes: AttributeError).
 
 The evaluation side (:167-205, :220-238): `evaluate_model` flies the trainer's
 10 test episodes through evaluate_cartpole.Evaluator - one kernel launch -
@@ -13,8 +21,10 @@ and runs the divergence-threshold ladder and the resampling of the data set
 loop around it."""
 import torch
 
+from . import _capi
 from . import functional as F
 from .dataset import SyntheticCartpoleDataset, TensorBatches
+from .drone_loss import cartpole_loss_mpc
 from .evaluate_cartpole import CartPoleEnv, CartpoleWrapper, Evaluator
 from .models.simple_model import Net
 from .train_base import TrainBase
@@ -78,24 +88,75 @@ class TrainCartpole(TrainBase):
                 current_state * (1 - 1 / (self.horizon - 1) * k))
         return ref_states
 
-    def run_epoch(self, train="controller"):
-        if train != "controller":
+    def learnt_simulator(self):
+        """Is the train dynamics the trainable LearntCartpoleDynamics?"""
+        from .dynamics.cartpole_dynamics import LearntCartpoleDynamics
+        return isinstance(self.train_dynamics, LearntCartpoleDynamics)
+
+    def learnt_fused(self, B):
+        """The controller step through the learnt simulator as ONE launch
+        (apg_cartpole_learnt_rollout_fwd_bwd) rather than H module steps:
+        measured faster at every batch size timed (profiles/
+        cartpole_learnt_timing.jsonl), so chosen whenever the horizon fits."""
+        return self.horizon <= _capi.MAX_HORIZON
+
+    def _controller_loss(self, current_state, action_seq):
+        """scripts/train_cartpole.py:133-148: make_reference, H steps of the
+        train dynamics, cartpole_loss_mpc."""
+        if not self.learnt_simulator():
+            return F.cartpole_rollout_loss(current_state, action_seq,
+                                           self.delta_t, self.train_dynamics.params)
+        if self.learnt_fused(current_state.shape[0]):
+            return F.cartpole_learnt_rollout_loss(
+                self.train_dynamics, current_state, action_seq, self.delta_t)
+        ref_states = self.make_reference(current_state)
+        states, s = [], current_state
+        for k in range(action_seq.size()[1]):
+            s = self.train_dynamics(s, action_seq[:, k], dt=self.delta_t)
+            states.append(s)
+        return cartpole_loss_mpc(torch.stack(states, 1), ref_states, action_seq)
+
+    def train_dynamics_model(self, current_state, action_seq):
+        """scripts/train_base.py:160-186 for the cart-pole simulator.  The
+        reference's regulariser reads linear_state_2.bias, which this network
+        does not have: l2_lambda > 0 is refused, as it fails there."""
+        if self.l2_lambda > 0 and self.learnt_simulator():
+            raise ValueError("l2_lambda > 0 needs linear_state_2.bias, which "
+                             "LearntCartpoleDynamics does not have: set l2_lambda 0")
+        return super().train_dynamics_model(current_state, action_seq)
+
+    def run_epoch(self, train="controller", epoch=0):
+        """scripts/train_cartpole.py:118-165.  train "dynamics" fits a
+        learnable simulator (TrainBase.train_dynamics_model) on the policy's
+        actions, computed without grad (the reference's next controller step
+        zeroes the policy gradient they would leave).  `epoch` is accepted for
+        TrainBase.run_dynamics and not used, as there."""
+        if train == "dynamics" and not isinstance(self.train_dynamics, torch.nn.Module):
             raise NotImplementedError(
-                "learnt-dynamics training is outside the APG hot path")
+                "dynamics epochs need a learnable simulator (LearntCartpoleDynamics)")
+        if train not in ("controller", "dynamics"):
+            raise ValueError("train must be 'controller' or 'dynamics'")
         self.results_dict["trained"].append(train)
         running_loss = None
         i = -1
         for i, data in enumerate(self.trainloader, 0):
             in_state, current_state = data
+            if train == "dynamics":
+                with torch.no_grad():
+                    actions = self.net(in_state.clone())
+                action_seq = torch.reshape(
+                    actions, (-1, self.horizon, self.action_dim))
+                loss = self.train_dynamics_model(current_state, action_seq).detach()
+                self.count_finetune_data += len(current_state)
+                running_loss = loss if running_loss is None else running_loss + loss
+                continue
             # the policy zeroes column 0 of its input in place: hand it a
             # private copy, as DataLoader collation does in the reference
             actions = self.net(in_state.clone())  # tanh output, no sigmoid
             action_seq = torch.reshape(
                 actions, (-1, self.horizon, self.action_dim))
             self.optimizer_controller.zero_grad()
-            loss = F.cartpole_rollout_loss(
-                current_state, action_seq, self.delta_t,
-                self.train_dynamics.params)
+            loss = self._controller_loss(current_state, action_seq)
             loss = self._step(loss).detach()
             running_loss = loss if running_loss is None else running_loss + loss
         epoch_loss = float(running_loss.item()) / i
@@ -162,4 +223,28 @@ def train_control(base_model, config, swingup=0, device=None):
     except KeyboardInterrupt:
         pass
     trainer.finalize()
+    return trainer
+
+
+def train_norm_dynamics(base_model, config, not_trainable="all", device=None):
+    """scripts/train_cartpole.py:245-262 (`-t adapt`): fit a
+    LearntCartpoleDynamics to CartpoleDynamics(modified_params) for the first
+    epochs, then train the controller through it (TrainBase.run_dynamics),
+    evaluating in the LEARNT environment (sample_in "train_env").
+    base_model: a state_dict checkpoint file (checkpoint.load_policy) or None.
+    finalize saves the simulator's state_dict as `dynamics_model`.  Returns
+    the trainer."""
+    from .checkpoint import load_policy
+    from .dynamics.cartpole_dynamics import CartpoleDynamics, LearntCartpoleDynamics
+    modified_params = config["modified_params"]
+    config["sample_in"] = "train_env"
+    config["thresh_div_start"] = 0.2
+    config["train_dyn_every"] = 1
+    dev = torch.device(device or "cuda")
+    train_dyn = LearntCartpoleDynamics(not_trainable=not_trainable).to(dev)
+    eval_dyn = CartpoleDynamics(modified_params=modified_params)
+    trainer = TrainCartpole(train_dyn, eval_dyn, config)
+    net = None if base_model is None else load_policy(base_model, system="cartpole")
+    trainer.initialize_model(net, device=dev)
+    trainer.run_dynamics(config)
     return trainer

@@ -1000,6 +1000,68 @@ int apg_cartpole_mlp_closed_loop(const float *state0, float dt,
                                  float *states, float *actions, float *workspace,
                                  apg_stream_t stream);
 
+/* ---------------------------------------------------- cartpole, learnt --- */
+/* LearntCartpoleDynamics (neural_control/dynamics/cartpole_dynamics.py:
+ * 122-140, learnt_dynamics.py:58-98):
+ *   s' = simulate_cartpole(s, a) + W2 relu(W1 [s; a] + b1)
+ * with the physics (:53-119) on six LIVE parameters - after training they are
+ * independent, so total_mass is not masspole + masscart - and gravity 9.81.
+ * Every pointer is a DEVICE pointer to the module's own tensors: the six [1]
+ * parameters of its `cfg`, linear_state_1.weight [64][5] / .bias [64] and
+ * linear_state_2.weight [4][64].  The kernels read them when they run: no
+ * host read-back, graph-capturable, always the latest values. */
+typedef struct ApgCartpoleLearnt {
+  const float *max_force_mag, *masspole, *length, *friction, *total_mass,
+      *polemass_length, *w1, *b1, *w2;
+} ApgCartpoleLearnt;
+
+/* The module's forward / its VJP for AoS state [B,4], action [B,1].  w1, b1
+ * and w2 all NULL: physics only (simulate_cartpole).  The reverse returns
+ * dL/dstate and dL/daction (either may be NULL) and grad_params:
+ * apg_cartpole_learnt_param_count() = 646 device floats, the batch-summed
+ * cotangents [max_force_mag, masspole, length, friction, total_mass,
+ * polemass_length | W1 [64][5] | b1 [64] | W2 [4][64]] (what loss.backward()
+ * leaves in the module for scripts/train_base.py:160-186; the weight part is 0
+ * without a residual).  Two stages, no float atomics: bit-reproducible.
+ * workspace: apg_cartpole_learnt_workspace_floats(B) device floats. */
+int apg_cartpole_learnt_param_count(void);
+int apg_cartpole_learnt_workspace_floats(int B);
+int apg_cartpole_learnt_step_fwd(const float *state, const float *action, float dt,
+                                 const ApgCartpoleLearnt *model, int B, float *next_state,
+                                 apg_stream_t stream);
+int apg_cartpole_learnt_step_bwd(const float *state, const float *action, float dt,
+                                 const ApgCartpoleLearnt *model, int B,
+                                 const float *grad_next, float *grad_state,
+                                 float *grad_action, float *grad_params, float *workspace,
+                                 apg_stream_t stream);
+
+/* apg_cartpole_rollout_fwd_bwd through the learnt simulator: the controller
+ * phase of TrainBase.run_dynamics (scripts/train_base.py:334-375) for the
+ * cart-pole (scripts/train_cartpole.py:131-150, each step
+ * LearntCartpoleDynamics.forward).  The simulator is frozen in this phase: no
+ * parameter gradient is produced.  The residual must be given.  Layouts:
+ * APG_LAYOUT_AOS or APG_LAYOUT_SOA. */
+int apg_cartpole_learnt_rollout_fwd_bwd(const float *state0, const float *actions, float dt,
+                                        const ApgCartpoleLearnt *model, int B, int H,
+                                        int layout, float *loss_partials, float *loss,
+                                        float *grad_actions, float *grad_state0,
+                                        float *states_out, apg_stream_t stream);
+
+/* apg_cartpole_mlp_closed_loop in the LEARNT environment - what
+ * CartPoleEnv(train_dynamics) steps with in the adapt flow
+ * (scripts/train_cartpole.py:50-55, 245-262): each env step is the module's
+ * forward (the residual reads the pre-step state, whose cart position is 0
+ * from the second step on, and the raw action), then the theta wrap.  The
+ * residual must be given. */
+int apg_cartpole_learnt_mlp_closed_loop(const float *state0, float dt,
+                                        const ApgCartpoleLearnt *model,
+                                        const ApgCartpolePolicy *policy, int B,
+                                        int max_steps, int mode, float thresh_div,
+                                        int burn_in, int *steps, int *upright,
+                                        double *vel_sum, double *vel_sq, float *states,
+                                        float *actions, float *workspace,
+                                        apg_stream_t stream);
+
 /* --------------------------------------------------------------- misc --- */
 /* loss[0] = fixed-order sum of partials[0..n) (one small kernel). */
 int apg_reduce_loss_partials(const float *partials, int n, float *loss,

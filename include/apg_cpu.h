@@ -31,7 +31,9 @@
  *  - the policy-inside entry points (apg_quad_mlp_*, apg_quad_lstm_*,
  *    apg_wing_policy_*), the learnt simulators, the matrix products and the
  *    layout helpers have no twin: they are matrix-core kernels without
- *    shared per-lane headers.
+ *    shared per-lane headers.  Exception: the learnt cart-pole simulator is
+ *    plain fp32 per lane (csrc/cartpole_learnt_math.h); its twins are
+ *    declared in apg_cpu_learnt.h, included below.
  * Errors: same codes; apg_cpu_last_error_string().
  */
 #ifndef APG_CPU_H_
@@ -110,4 +112,7 @@ const char *apg_cpu_last_error_string(void);
 #ifdef __cplusplus
 }
 #endif
+
+/* the learnt cart-pole simulator's twins (apg_cartpole_learnt_*_cpu) */
+#include "apg_cpu_learnt.h"
 #endif /* APG_CPU_H_ */

@@ -1,0 +1,275 @@
+"""LearntCartpoleDynamics on the GPU (csrc/cartpole_learnt.hip, the learnt
+instantiation of cart_closed_loop_kernel): the module's forward and every
+parameter gradient, the simulator fit, the fused controller phase and the
+closed loop in the learnt environment against the recordings of the REAL
+reference (G20, tests/golden/make_golden_cartpole_learnt.py), and the adapt
+flow (train_cartpole.train_norm_dynamics) end to end."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import load_golden
+from test_cartpole_eval_cpu import check_against_case, golden_net
+from test_cartpole_learnt_cpu import DT, PHYS, close, fitted, g20
+
+pytestmark = pytest.mark.gpu
+
+CASES = ["learnt_balance_a", "learnt_balance_b", "learnt_swingup"]
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "needs an MI355X"
+    return torch.device("cuda:0")
+
+
+def shipped(dev):
+    return golden_net(load_golden("cartpole_closed_loop.npz"), "shipped").to(dev)
+
+
+@pytest.mark.parametrize("frozen", [False, True])
+def test_forward_and_parameter_gradients_vs_golden(dev, frozen):
+    """(1) forward, simulate_cartpole and - after the fit loss's backward -
+    dL/dstate, dL/daction and every parameter's gradient; the seven keys that
+    do not enter the physics (and, frozen, all 13) have grad None."""
+    g = g20()
+    m = fitted(g).to(dev)
+    if frozen:
+        for p in m.cfg.values():
+            p.requires_grad_(False)
+    s = torch.from_numpy(g["step.state"]).to(dev).requires_grad_(True)
+    a = torch.from_numpy(g["step.action"]).to(dev).requires_grad_(True)
+    pred = m(s, a, DT)
+    close(pred.detach().cpu(), g["step.forward"], 1e-5)
+    with torch.no_grad():
+        close(m.simulate_cartpole(s, a, DT).cpu(), g["step.simulate"], 1e-5)
+    loss = torch.sum((pred - torch.from_numpy(g["step.target"]).to(dev))**2)
+    assert abs(loss.item() - float(g["step.loss"])) <= 1e-4 * float(g["step.loss"])
+    loss.backward()
+    close(s.grad.cpu(), g["step.grad_state"], 1e-4)
+    close(a.grad.cpu(), g["step.grad_action"], 1e-4)
+    tag = "step_frozen" if frozen else "step"
+    for k, p in m.named_parameters():
+        assert int(p.grad is not None) == int(g[f"{tag}.has_grad.{k}"]), k
+        if p.grad is not None:
+            close(p.grad.cpu(), g[f"{tag}.grad.{k}"], 1e-4)
+    assert sum(p.grad is None for k, p in m.cfg.items()) == (13 if frozen else 7)
+
+
+def test_parameter_gradients_bit_identical_at_large_batch(dev):
+    """(2) two stages, no float atomics: the same bits twice at B = 65 537."""
+    g = g20()
+    m = fitted(g).to(dev)
+    gen = torch.Generator().manual_seed(3)
+    B = 65537
+    s = ((torch.rand(B, 4, generator=gen) * 2 - 1) * torch.tensor([2.4, 7.5, 3.1, 7.5])).to(dev)
+    a = (torch.rand(B, 1, generator=gen) * 2 - 1).to(dev)
+    w = torch.randn(B, 4, generator=gen).to(dev)
+    grads = []
+    for _ in range(2):
+        m.zero_grad()
+        (m(s, a, DT) * w).sum().backward()
+        grads.append([p.grad.clone() for p in m.parameters() if p.grad is not None])
+    assert len(grads[0]) == 9
+    for x, y in zip(*grads):
+        assert torch.equal(x, y)
+
+
+@pytest.mark.parametrize("tag,nt", [("all", []), ("frozen", "all")])
+def test_train_dynamics_model_steps_vs_golden(dev, tag, nt):
+    """(3) five train_dynamics_model steps (momentum SGD 0.9, lr 0.01): the
+    loss of each step and the state_dict after it."""
+    import types
+    from apg_trajectory_tracking_amd.dynamics.cartpole_dynamics import (
+        CartpoleDynamics, LearntCartpoleDynamics)
+    from apg_trajectory_tracking_amd.train_base import TrainBase, momentum_sgd
+    g = g20()
+    torch.manual_seed(21)           # (the generator's seed: the same init draws)
+    m = LearntCartpoleDynamics(not_trainable=nt).to(dev)
+    s = torch.from_numpy(g[f"train_{tag}.state"]).to(dev)
+    a = torch.from_numpy(g[f"train_{tag}.action"]).to(dev)
+    tr = types.SimpleNamespace(
+        train_dynamics=m, eval_dynamics=CartpoleDynamics({"masspole": .2, "length": .7}),
+        delta_t=DT, l2_lambda=0, results_dict={"loss_dyn_per_step": []},
+        optimizer_dynamics=momentum_sgd(m.parameters(), 0.01))
+    seq = a[:, None, :].repeat(1, 10, 1)
+    for k in range(5):
+        loss = TrainBase.train_dynamics_model(tr, s, seq)
+        want = float(g[f"train_{tag}.losses"][k])
+        assert abs(loss.item() - want) <= 1e-4 * want, (k, loss.item(), want)
+        for key, v in m.state_dict().items():
+            close(v.cpu(), g[f"train_{tag}.after{k}.{key}"], 1e-4)
+
+
+def _unroll_loss(m, net, s0, dt):
+    """The module's step-by-step autograd unroll of the controller branch."""
+    from apg_trajectory_tracking_amd.drone_loss import cartpole_loss_mpc
+    H = 10
+    acts = net(s0.clone()).reshape(-1, H, 1)
+    ref = torch.zeros(s0.shape[0], H, 4, device=s0.device)
+    for k in range(H - 1):
+        ref[:, k] = s0 * (1 - 1 / (H - 1) * k)
+    st, s = [], s0
+    for k in range(H):
+        s = m(s, acts[:, k], dt)
+        st.append(s)
+    return cartpole_loss_mpc(torch.stack(st, 1), ref, acts)
+
+
+def _fused_loss(m, net, s0, dt):
+    from apg_trajectory_tracking_amd import functional as F
+    acts = net(s0.clone()).reshape(-1, 10, 1)
+    return F.cartpole_learnt_rollout_loss(m, s0, acts, dt)
+
+
+def _policy_grads(net, loss):
+    net.zero_grad()
+    loss.backward()
+    return {k: p.grad.detach().clone() for k, p in net.named_parameters()}
+
+
+@pytest.mark.parametrize("B", [8, 64, 1003, 65536])
+def test_fused_controller_step_vs_unroll_and_golden(dev, B):
+    """(4) the fused controller phase (one launch) against the module's own
+    step-by-step unroll; at B = 8 / 64 also against G20."""
+    g = g20()
+    m = fitted(g).to(dev)
+    for p in m.parameters():
+        p.requires_grad_(False)
+    net = shipped(dev)
+    if f"ctrl{B}.state" in g.files:
+        s0 = torch.from_numpy(g[f"ctrl{B}.state"]).to(dev)
+    else:
+        gen = torch.Generator().manual_seed(B)
+        s0 = ((torch.rand(B, 4, generator=gen) * 2 - 1)
+              * torch.tensor([1.0, 1.0, 0.3, 1.0])).to(dev)
+    lf = _fused_loss(m, net, s0, DT)
+    gf = _policy_grads(net, lf)
+    lu = _unroll_loss(m, net, s0, DT)
+    gu = _policy_grads(net, lu)
+    assert abs(lf.item() - lu.item()) <= 1e-4 * abs(lu.item())
+    for k in gf:
+        close(gf[k].cpu(), gu[k].cpu().numpy(), 1e-4)
+    if f"ctrl{B}.loss" in g.files:
+        want = float(g[f"ctrl{B}.loss"])
+        assert abs(lf.item() - want) <= 1e-4 * want
+        for k in gf:
+            close(gf[k].cpu(), g[f"ctrl{B}.grad.{k}"], 1e-4)
+
+
+def test_zeroed_residual_matches_the_analytic_rollout(dev):
+    """(4) nominal parameters, residual weights zero: the analytic fused
+    rollout to 1e-5 (not bit-exact: total_mass is rounded to fp32 once here,
+    summed in fp32 there)."""
+    from apg_trajectory_tracking_amd import functional as F
+    from apg_trajectory_tracking_amd.dynamics.cartpole_dynamics import (
+        CartpoleDynamics, LearntCartpoleDynamics)
+    m = LearntCartpoleDynamics(not_trainable="all").to(dev)
+    with torch.no_grad():
+        for p in (m.linear_state_1.weight, m.linear_state_1.bias, m.linear_state_2.weight):
+            p.zero_()
+    gen = torch.Generator().manual_seed(9)
+    B = 300
+    s0 = ((torch.rand(B, 4, generator=gen) * 2 - 1) * 0.5).to(dev)
+    acts = (torch.rand(B, 10, 1, generator=gen) * 2 - 1).to(dev)
+    ga = acts.clone().requires_grad_(True)
+    gb = acts.clone().requires_grad_(True)
+    ll = F.cartpole_learnt_rollout_loss(m, s0, ga, DT)
+    la = F.cartpole_rollout_loss(s0, gb, DT, CartpoleDynamics().params)
+    ll.backward()
+    la.backward()
+    assert abs(ll.item() - la.item()) <= 1e-5 * abs(la.item())
+    close(ga.grad.cpu(), gb.grad.cpu().numpy(), 1e-5)
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_learnt_closed_loop_vs_golden(dev, name):
+    """(5) the real Evaluator's flights in CartPoleEnv(fitted module): the
+    kernel on the recorded starts, and the Evaluator drawing them itself;
+    step counts and flags exact, states within G19's bounds."""
+    from apg_trajectory_tracking_amd import functional as F
+    from apg_trajectory_tracking_amd.evaluate_cartpole import (
+        CartPoleEnv, CartpoleWrapper, Evaluator)
+    from test_cartpole_eval_cpu import case
+    g = g20()
+    c = case(g, name)
+    swing = int(c["swingup"])
+    m = fitted(g).to(dev)
+    net = shipped(dev)
+    out = F.cartpole_mlp_closed_loop(
+        net, torch.from_numpy(c["start"]).to(dev), DT, None, max_steps=250,
+        mode="swingup" if swing else "balance", thresh_div=float(c["thresh_div"]),
+        burn_in=int(c["burn_in"]), want_trajectory=True, learnt=m)
+    host = {k: v.cpu().numpy() for k, v in out.items()}
+    check_against_case(c, host, state_tol=1e-3 if swing else 1e-4)
+    if not swing:
+        assert 0 < int((c["steps"] < 250).sum()) < len(c["steps"])  # both branches
+    np.random.seed(int(c["seed"]))
+    env = CartPoleEnv(m, DT, thresh_div=float(c["thresh_div"]))
+    ev = Evaluator(CartpoleWrapper(net), env)
+    ev.initialize_straight = int(c["straight"])
+    n = len(c["steps"])
+    res = (ev.evaluate_swingup if swing else ev.evaluate_in_environment)(
+        nr_iters=n, max_steps=250)
+    assert np.random.rand() == float(c["next_rand"])
+    np.testing.assert_array_equal(ev.last_flights["steps"].cpu().numpy(), c["steps"])
+    for k, v in res.items():
+        assert abs(v - float(c[k])) <= 1e-4 * abs(float(c[k])), (k, v, c[k])
+
+
+def test_env_step_through_the_module(dev):
+    """(5) CartPoleEnv._step in the learnt environment: one recorded step."""
+    from apg_trajectory_tracking_amd.evaluate_cartpole import CartPoleEnv
+    g = g20()
+    c = {k[len("learnt_balance_a."):]: g[k] for k in g.files
+         if k.startswith("learnt_balance_a.")}
+    m = fitted(g).to(dev)
+    env = CartPoleEnv(m, DT, thresh_div=float(c["thresh_div"]))
+    env.state = np.array(c["start"][0], np.float64)
+    nxt = env._step(torch.tensor([[float(c["actions"][0, 0])]]))
+    scale = np.abs(c["states"]).reshape(-1, 4).max(0)
+    assert np.all(np.abs(nxt - c["states"][0, 0]) <= 1e-4 * scale + 1e-6)
+
+
+def test_train_norm_dynamics_end_to_end(dev, tmp_path, monkeypatch):
+    """(6) the adapt flow with a small config: the fit lowers the one-step
+    error against the eval dynamics on a held-out batch, results_dict holds
+    the fit's logs, `dynamics_model` loads strictly into a fresh module."""
+    monkeypatch.chdir(tmp_path)
+    from apg_trajectory_tracking_amd import train_cartpole as tc
+    from apg_trajectory_tracking_amd.dynamics.cartpole_dynamics import (
+        CartpoleDynamics, LearntCartpoleDynamics)
+    base = tmp_path / "base.pt"
+    torch.save(shipped(dev).state_dict(), base)
+    cfg = {"system": "cartpole", "delta_t": DT, "state_size": 4, "batch_size": 64,
+           "nr_epochs": 4, "train_dyn_for_epochs": 2, "resample_every": 100,
+           "thresh_div_step": 0.0, "thresh_div_end": 0.2, "l2_lambda": 0,
+           "modified_params": {"masspole": .2, "length": .7}, "horizon": 10,
+           "action_dim": 1, "learning_rate_controller": 1e-6,
+           "learning_rate_dynamics": 0.001, "sample_data": 512, "suc_up_down": -1,
+           "save_name": str(tmp_path / "adapt")}
+    gen = torch.Generator().manual_seed(4)
+    hs = ((torch.rand(512, 4, generator=gen) * 2 - 1) * 0.3).to(dev)
+    ha = (torch.rand(512, 1, generator=gen) * 2 - 1).to(dev)
+    target = CartpoleDynamics(cfg["modified_params"])(hs, ha, DT)
+
+    def err(m):
+        with torch.no_grad():
+            return float(((m(hs, ha, DT) - target)**2).sum())
+    torch.manual_seed(0)
+    before = err(LearntCartpoleDynamics().to(dev))
+    torch.manual_seed(0)
+    tr = tc.train_norm_dynamics(str(base), cfg, not_trainable=[], device=dev)
+    assert cfg["sample_in"] == "train_env" and cfg["train_dyn_every"] == 1
+    assert tr.results_dict["trained"] == ["dynamics"] * 3 + ["controller"]
+    after = err(tr.train_dynamics)
+    assert after < before, (before, after)
+    for k in ("loss_dynamics", "loss_dyn_per_step", "samples_in_d2"):
+        assert len(tr.results_dict[k]) > 0, k
+    assert tr.results_dict["samples_in_d2"][-1] == 3 * 512
+    assert len(tr.results_dict["loss_dynamics"]) == 3
+    assert isinstance(tr.eval_env.dynamics, LearntCartpoleDynamics)
+    sd = torch.load(os.path.join(tr.save_path, "dynamics_model"))
+    LearntCartpoleDynamics().load_state_dict(sd, strict=True)
