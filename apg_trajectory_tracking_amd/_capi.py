@@ -69,6 +69,12 @@ class ApgLearntResidual(ctypes.Structure):
         "linear_at", "w1", "b1", "w2", "b2")]
 
 
+class ApgQuadMpcOptions(ctypes.Structure):
+    """include/apg.h: the shooting MPC's iteration count and step rule."""
+    _fields_ = [("iters", ctypes.c_int), ("beta", ctypes.c_float),
+                ("alpha_thrust", ctypes.c_float), ("alpha_rate", ctypes.c_float)]
+
+
 class ApgLstmPolicy(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in (
         "conv_w", "conv_b", "w_ih", "w_hh", "b_ih", "b_hh", "w_out", "b_out")]
@@ -330,6 +336,16 @@ SIGNATURES = {
     "apg_cartpole_learnt_mlp_closed_loop": [
         _P, _F, ctypes.POINTER(ApgCartpoleLearnt), ctypes.POINTER(ApgCartpolePolicy),
         _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "apg_quad_mpc_solve": [
+        _P, _P, _I, _F, ctypes.POINTER(ApgQuadParams),
+        ctypes.POINTER(ApgQuadLossWeights), ctypes.POINTER(ApgQuadMpcOptions), _I, _I,
+        _P, _P, _P, _P],
+    "apg_quad_mpc_closed_loop": [
+        _P, _I, _F, ctypes.POINTER(ApgQuadParams), ctypes.POINTER(ApgLearntResidual),
+        ctypes.POINTER(ApgQuadParams), ctypes.POINTER(ApgQuadLossWeights),
+        ctypes.POINTER(ApgQuadMpcOptions), _I, _I, _I, _F, _F, _I, _P, _P, _P, _P, _P,
+        _P, _P, _P],
+    "apg_quad_mpc_workspace_floats": [],
     "apg_reduce_loss_partials": [_P, _I, _P, _P],
     "apg_loss_partials_count": [_I],
     "apg_stream_copy": [_P, _P, ctypes.c_longlong, _P],

@@ -14,7 +14,7 @@ LIB = os.path.join(CSRC, "libapg_hip.so")
 SOURCES = ["common.hip", "quad.hip", "wing.hip", "cartpole.hip", "lstm.hip",
            "mlp_rollout.hip", "mlp_concurrent.hip", "mlp_wing.hip", "wing_learnt.hip",
            "linear_wgrad.hip", "planes_gemm.hip", "mlp_cartpole.hip",
-           "cartpole_learnt.hip"]
+           "cartpole_learnt.hip", "quad_mpc.hip"]
 # -fno-slp-vectorize: hipcc's SLP pass packs neighbouring f32 ops into
 # v_pk_fma/mul/add_f32; on gfx950 a packed op issues no faster than two plain
 # ones here and needs v_mov shuffles to form register pairs - measured on
@@ -132,7 +132,8 @@ def build_cpu(force=False, verbose=False):
     entry points.  A separate library that the package never loads."""
     src = os.path.join(CSRC, "cpu_twins.hip")
     deps = [src, os.path.join(REPO, "include", "apg_cpu.h"),
-            os.path.join(REPO, "include", "apg_cpu_learnt.h"), __file__] + _headers()
+            os.path.join(REPO, "include", "apg_cpu_learnt.h"),
+            os.path.join(REPO, "include", "apg_cpu_mpc.h"), __file__] + _headers()
     if (not force and os.path.exists(LIB_CPU)
             and os.path.getmtime(LIB_CPU) >= max(os.path.getmtime(d) for d in deps)):
         return LIB_CPU

@@ -1,0 +1,86 @@
+"""Drop-in for `neural_control.controllers.mpc.MPC` on the quadrotor: the
+comparator the reference judges its learnt controllers against, batched.
+
+    mpc = MPC(horizon=10, dt=0.1, dynamics="flightmare")
+    action = mpc.predict_actions(current_state, ref_states)    # [1, 4]
+
+Kept from the reference (neural_control/controllers/mpc.py): the stage cost
+(_initParamsSimpleQuad: Q_pen = diag(100,100,100, 0,0,0, 10,10,10, 1,1,1), Q_u
+= diag(50,1,1,1) around u = 0.5 - quad_mpc_loss is that cost divided by ten),
+the action box [0, 1], the Flightmare model with `modified_params`, the warm
+start by shifting the previous solution, and this call surface.
+
+Two deliberate differences:
+  * ALL H stages carry state cost (the reference's NLP drops the last
+    stage's): the MPC optimum and a policy's training loss are then the same
+    quantity on the same window (functional.quad_policy_optimality_gap);
+  * the solver is first-order single shooting - projected heavy-ball descent
+    with a fixed number of iterations, one trajectory per GPU lane
+    (apg_quad_mpc_solve) - instead of IPOPT on a multiple-shooting NLP: every
+    trajectory of a batch does the same work and the result is a deterministic
+    function of the inputs.
+
+`QuadEvaluator(MPC(...), environment)` flies whole batches of reference
+trajectories with the solver inside the closed-loop kernel
+(functional.quad_mpc_closed_loop): plant = the evaluator's environment, model =
+this object's parameters."""
+import numpy as np
+import torch
+
+from .. import functional as F
+from ..dynamics.quad_dynamics_flightmare import FlightmareDynamics
+
+DYNAMICS = ("flightmare",)
+
+
+class MPC:
+
+    def __init__(self, horizon=10, dt=0.1, dynamics="flightmare", modified_params={},
+                 iters=10, beta=None, alpha_thrust=None, alpha_rate=None, device=None,
+                 **kwargs):
+        if dynamics not in DYNAMICS:
+            raise NotImplementedError(
+                f"MPC dynamics {dynamics!r}: implemented here: {', '.join(DYNAMICS)} "
+                "(the quadrotor; no fixed-wing or cart-pole MPC)")
+        if horizon not in (5, 10):
+            raise ValueError("the batched MPC is built for horizon 5 or 10")
+        self.horizon = horizon
+        self.dt = dt
+        self.dynamics_model = dynamics
+        self.model = FlightmareDynamics(modified_params=modified_params)
+        self.params = self.model.params
+        self.options = dict(iters=iters, beta=beta, alpha_thrust=alpha_thrust,
+                            alpha_rate=alpha_rate)
+        self.device = device
+        self.warm_start = None      # [B,H,4]: the previous solution, not yet shifted
+        self.last_cost = None
+
+    def reset(self):
+        """Forget the warm start: the next call starts from u = 0.5."""
+        self.warm_start = None
+        self.last_cost = None
+
+    def predict_actions(self, current_state, ref_states):
+        """current_state [12] + ref_states [H,9] (numpy, rows as
+        `preprocess_quad` lays them out: columns 0:3 position, 6:9 velocity) ->
+        np.ndarray [1,4] like the reference; [B,12] + [B,H,9] tensors -> tensor
+        [B,4].  The warm start lives in the object and is shifted per call."""
+        numpy_in = not torch.is_tensor(current_state)
+        dev = torch.device(self.device or
+                           ("cuda" if numpy_in else current_state.device))
+        s = torch.as_tensor(np.asarray(current_state, dtype=np.float32) if numpy_in
+                            else current_state).to(dev, torch.float32)
+        r = torch.as_tensor(np.asarray(ref_states, dtype=np.float32) if numpy_in
+                            else ref_states).to(dev, torch.float32)
+        if s.dim() == 1:
+            s, r = s[None], r[None]
+        if r.shape[1:] != (self.horizon, 9) or s.shape != (r.shape[0], 12):
+            raise ValueError(f"state [B,12] and reference rows [B,{self.horizon},9] expected")
+        u0 = None
+        if self.warm_start is not None and self.warm_start.shape[0] == s.shape[0]:
+            w = self.warm_start
+            u0 = torch.cat((w[:, 1:], w[:, -1:]), 1)
+        res = F.quad_mpc_solve(s, r, self.dt, self.params, u0=u0, **self.options)
+        self.warm_start, self.last_cost = res["u"], res["cost"]
+        action = res["u"][:, 0]
+        return action.cpu().numpy() if numpy_in else action

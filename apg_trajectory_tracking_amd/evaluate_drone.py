@@ -13,7 +13,12 @@ Same names and statistics as the reference evaluator:
     stable = number of steps with divergence < thresh_div and "complete" is
     measured against the length of the last run, as in the reference
     (:266-299).
-There is no renderer and no MPC baseline here (out of scope)."""
+A controller that is a `controllers.mpc.MPC` - the comparator the reference
+judges its controllers against - is flown the same way, with the solver inside
+the closed-loop kernel (apg_quad_mpc_closed_loop): the plant is the evaluator's
+environment, the solver's model the MPC's own parameters (other parameters =
+the model-mismatch experiment).  There is no renderer here (out of scope,
+SURVEY §8)."""
 import numpy as np
 import torch
 
@@ -32,8 +37,12 @@ class QuadEvaluator:
         used) or, after train_dynamics() swapped it in (scripts/train_drone.py:
         44-45), a LearntDynamics module: the kernel then steps through the
         action transform, the analytic step and the residual network."""
+        from .controllers.mpc import MPC
         from .dynamics.quad_dynamics_trained import LearntDynamics
         self.net = getattr(controller, "net", controller)
+        self.mpc = self.net if isinstance(self.net, MPC) else None
+        if self.mpc is not None and self.mpc.horizon != 10:
+            raise ValueError("the closed-loop MPC kernel is built for horizon 10")
         self.dynamics = getattr(environment, "dynamics", environment)
         self.learnt = (self.dynamics if isinstance(self.dynamics, LearntDynamics)
                        else None)
@@ -51,7 +60,11 @@ class QuadEvaluator:
         self.hidden = None     # (h0, c0) [B,8] for an LSTM controller
 
     def _closed_loop(self, traj, **kw):
-        """One launch for the whole batch; MLP or LSTM controller."""
+        """One launch for the whole batch; MLP or LSTM controller, or the MPC."""
+        if self.mpc is not None:
+            return F.quad_mpc_closed_loop(
+                traj, self.dt, self.dynamics.params, model_params=self.mpc.params,
+                learnt=self.learnt, **self.mpc.options, **kw)
         if hasattr(self.net, "lstm"):
             B, dev = traj.shape[0], traj.device
             if self.hidden is None or self.hidden[0].shape[0] != B:
@@ -63,6 +76,11 @@ class QuadEvaluator:
                 self.hidden[1], learnt=self.learnt, **kw)
         return F.quad_mlp_closed_loop(self.net, traj, self.dt,
                                       self.dynamics.params, learnt=self.learnt, **kw)
+
+    def _device(self):
+        if self.mpc is not None:
+            return torch.device(self.mpc.device or "cuda")
+        return next(self.net.parameters()).device
 
     def reference_batch(self, nr_test, seed=None):
         """Counterpart of `Random.__init__` (random_traj.py:28-35): nr_test
@@ -83,7 +101,7 @@ class QuadEvaluator:
                           nr_test=1, seed=None, **traj_args):
         if traj_type != "rand":
             raise ValueError("only the 'rand' reference is evaluated on the GPU")
-        dev = next(self.net.parameters()).device
+        dev = self._device()
         traj = (self.reference_batch(nr_test, seed) if trajectories is None
                 else trajectories).to(dev)
         out = self._closed_loop(
@@ -133,7 +151,7 @@ class QuadEvaluator:
             return 0, 0
         if reference != "rand":
             raise ValueError("only the 'rand' reference is evaluated on the GPU")
-        dev = next(self.net.parameters()).device
+        dev = self._device()
         traj = (self.reference_batch(nr_test, seed) if trajectories is None
                 else trajectories).to(dev)
         with torch.no_grad():

@@ -1796,6 +1796,136 @@ def quad_mlp_closed_loop(net, traj, dt, params, max_steps=251, thresh_div=1.0,
     return out
 
 
+# --------------------------------------------------- batched shooting MPC
+MPC_DEFAULTS = dict(iters=10, beta=0.5, alpha_thrust=1.0 / 300.0, alpha_rate=1.0 / 10.0)
+
+
+def quad_mpc_options(iters=None, beta=None, alpha_thrust=None, alpha_rate=None):
+    """ApgQuadMpcOptions (include/apg.h); None = the default of MPC_DEFAULTS."""
+    given = dict(iters=iters, beta=beta, alpha_thrust=alpha_thrust, alpha_rate=alpha_rate)
+    o = {k: MPC_DEFAULTS[k] if v is None else v for k, v in given.items()}
+    return _capi.ApgQuadMpcOptions(int(o["iters"]), float(o["beta"]),
+                                   float(o["alpha_thrust"]), float(o["alpha_rate"]))
+
+
+def quad_mpc_solve(state0, ref, dt, params, u0=None, weights=None, iters=10, beta=None,
+                   alpha_thrust=None, alpha_rate=None, want_trace=False):
+    """One shooting-MPC solve per trajectory in one launch (apg_quad_mpc_solve):
+    `iters` iterations of projected heavy-ball descent on quad_mpc_loss of the
+    H-step unroll of the model `params` from state0 [B,12] against the window
+    rows ref [B,H,9] ([pos, euler, vel]) or [B,H,6] ([pos, vel]), actions boxed
+    to [0, 1].  u0 [B,H,4]: the start (None: 0.5 - hover thrust, zero rates).
+    H = 5 or 10.  Returns dict(u [B,H,4], cost [B] = the cost of u, trace
+    [iters+1,B] with want_trace: the cost before every iteration and at the
+    end, else None)."""
+    if ref.dim() != 3 or state0.dim() != 2:
+        raise ValueError("state0 [B,12] and ref [B,H,9|6] expected")
+    B, H, C = ref.shape
+    if state0.shape != (B, 12) or (u0 is not None and tuple(u0.shape) != (B, H, 4)):
+        raise ValueError("inconsistent MPC shapes: state0 [B,12], ref [B,H,C], u0 [B,H,4]")
+    dev = state0.device
+    s = _f32c(state0).t().contiguous()
+    r = _f32c(ref).permute(1, 2, 0).contiguous()
+    if u0 is None:
+        u = torch.full((H, 4, B), 0.5, dtype=torch.float32, device=dev)
+    else:
+        u = _f32c(u0).permute(1, 2, 0).contiguous()
+        if u.data_ptr() == u0.data_ptr():
+            u = u.clone()           # in: start, out: solution
+    require_device(s, r, u)
+    opt = quad_mpc_options(iters, beta, alpha_thrust, alpha_rate)
+    weights = weights or quad_loss_weights()
+    cost = torch.empty(B, dtype=torch.float32, device=dev)
+    trace = (torch.empty(opt.iters + 1, B, dtype=torch.float32, device=dev)
+             if want_trace else None)
+    check(lib().apg_quad_mpc_solve(
+        ptr(s), ptr(r), C, float(dt), ctypes.byref(params), ctypes.byref(weights),
+        ctypes.byref(opt), B, H, ptr(u), ptr(cost), ptr(trace), stream_of(s)),
+        "apg_quad_mpc_solve")
+    return dict(u=u.permute(2, 0, 1).contiguous(), cost=cost, trace=trace)
+
+
+def quad_mpc_closed_loop(traj, dt, params, model_params=None, learnt=None, weights=None,
+                         iters=10, beta=None, alpha_thrust=None, alpha_rate=None,
+                         max_steps=251, thresh_div=1.0, thresh_stable=1.0, test_time=0,
+                         want_trajectory=False):
+    """quad_mlp_closed_loop with the policy replaced by the shooting MPC: per
+    control step "shift the warm start, solve, apply u[0]", every flight of the
+    batch in one launch (apg_quad_mpc_closed_loop).  `params` (and `learnt`, a
+    LearntDynamics module) step the flight; `model_params` is what the solver
+    plans with (None: `params` - the nominal case; other parameters: the
+    model-mismatch experiment).  Returns the dict quad_mlp_closed_loop returns,
+    plus cost [T,B]: the solver's cost at every control step."""
+    B, L, _ = traj.shape
+    H = 10
+    dev = traj.device
+    tr = _f32c(traj).permute(1, 2, 0).contiguous()
+    require_device(tr)
+    T = min(int(max_steps), L + 1)
+    new = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+    div, cost = new(T, B), new(T, B)
+    steps = torch.zeros(B, dtype=torch.int32, device=dev)
+    drone = new(T + 1, 12, B) if want_trajectory else None
+    actions = new(T, 4, B) if want_trajectory else None
+    start = new(T, 12, B) if want_trajectory else None
+    env, _keep = _closed_loop_env(learnt)
+    ws = new(lib().apg_quad_mpc_workspace_floats()) if learnt is not None else None
+    opt = quad_mpc_options(iters, beta, alpha_thrust, alpha_rate)
+    weights = weights or quad_loss_weights()
+    model = params if model_params is None else model_params
+    check(lib().apg_quad_mpc_closed_loop(
+        ptr(tr), L, float(dt), ctypes.byref(params), env, ctypes.byref(model),
+        ctypes.byref(weights), ctypes.byref(opt), B, H, int(max_steps),
+        float(thresh_div), float(thresh_stable), int(test_time), ptr(div),
+        steps.data_ptr(), ptr(drone), ptr(actions), ptr(start), ptr(cost), ptr(ws),
+        stream_of(tr)), "apg_quad_mpc_closed_loop")
+    out = dict(div=div, steps=steps, cost=cost)
+    if want_trajectory:
+        out.update(drone=drone, actions=actions, start_states=start)
+    return out
+
+
+def quad_policy_actions(net, state0, in_ref, dt, params):
+    """The action plan [B,H,4] a quadrotor policy commits to from state0 on the
+    window in_ref ([B,>=H,9] policy-input rows; [B,>=2H,9] for a one-step
+    policy): a `Net(15, H, 9, 4H)` gives it in one evaluation, a `Net(15, H, 9,
+    4)` by the autoregressive unroll of scripts/train_drone.py:113-165 through
+    the model `params` (window copied before the relative-position
+    subtraction).  The module's own forward is the policy here - the object
+    under judgement, evaluated once."""
+    H = 10
+    out_dim = net.fc_out.weight.shape[0]
+    with torch.no_grad():
+        if out_dim == 4 * H:
+            a = torch.sigmoid(net(quad_features(state0), in_ref[:, :H]))
+            return a.reshape(-1, H, 4).contiguous()
+        if out_dim != 4 or in_ref.shape[1] < 2 * H:
+            raise ValueError("Net(15, 10, 9, 40) or Net(15, 10, 9, 4) with in_ref [B,2H,9]")
+        cur, acts = _f32c(state0), []
+        for k in range(H):
+            rel = in_ref[:, k:k + H].clone()
+            rel[:, :, :3] = rel[:, :, :3] - cur[:, None, :3]
+            acts.append(torch.sigmoid(net(quad_features(cur), rel)))
+            cur = quad_step(cur, acts[-1], dt, params)
+        return torch.stack(acts, 1).contiguous()
+
+
+def quad_policy_optimality_gap(net, state0, in_ref, ref, dt, params, iters=50):
+    """How far is a policy from what the optimiser reaches on the same windows,
+    the same cost and the same model?  Per trajectory: the cost of the policy's
+    action plan (quad_policy_actions), the MPC cost after `iters` iterations
+    started AT that plan, and the MPC cost after `iters` iterations from u =
+    0.5.  ref [B,>=H,9|6]: the loss rows.  Returns dict(policy [B], mpc_from_policy
+    [B], mpc [B], actions [B,H,4])."""
+    H = 10
+    acts = quad_policy_actions(net, state0, in_ref, dt, params)
+    window = ref[:, :H]
+    policy = quad_mpc_solve(state0, window, dt, params, u0=acts, iters=0)["cost"]
+    warm = quad_mpc_solve(state0, window, dt, params, u0=acts, iters=iters)["cost"]
+    cold = quad_mpc_solve(state0, window, dt, params, iters=iters)["cost"]
+    return dict(policy=policy, mpc_from_policy=warm, mpc=cold, actions=acts)
+
+
 def quad_lstm_closed_loop(net, traj, dt, params, h0, c0, max_steps=251,
                           thresh_div=1.0, thresh_stable=1.0, test_time=0,
                           want_trajectory=False, learnt=None):

@@ -684,6 +684,58 @@ int apg_quad_lstm_closed_loop_env(const float *traj, int L, const float *h0,
                                   float *start_states, float *workspace,
                                   apg_stream_t stream);
 
+/* Batched shooting MPC - the role of the comparator the reference judges its
+ * controllers against (neural_control/controllers/mpc.py: CasADi + IPOPT on a
+ * multiple-shooting NLP, batch 1), by another METHOD: single shooting with
+ * projected heavy-ball descent, one trajectory per lane, every iteration in the
+ * registers of that lane (csrc/quad_mpc_math.h).  Kept from the reference: the
+ * stage cost (quad_mpc_loss with `weights` is _initParamsSimpleQuad's Q_pen /
+ * Q_u divided by ten), the action box [0, 1], the model (`model` through
+ * FlightmareDynamics' step), the warm start by shifting.  Different on
+ * purpose: all H rows carry state cost (the reference drops the last stage's),
+ * and the number of iterations is fixed (no data-dependent stopping: the
+ * result is a deterministic function of the inputs).
+ *   u <- clamp(u - m, 0, 1),  m <- beta m + alpha_c dJ/du   (m = 0 at the start
+ *   of a solve; alpha_thrust for action column 0, alpha_rate for 1..3)
+ * Reference defaults: iters 10, beta 0.5, alpha_thrust 1/300, alpha_rate 1/10. */
+typedef struct ApgQuadMpcOptions {
+  int iters;
+  float beta, alpha_thrust, alpha_rate;
+} ApgQuadMpcOptions;
+
+/* One solve per trajectory, SoA only: state0 [12][B]; ref [H][ref_cols][B] the
+ * window rows (ref_cols = 9: [pos, euler, vel], 6: [pos, vel]); u [H][4][B] in:
+ * start (0.5 = the reference's _quad_u0, or a shifted earlier solution), out:
+ * solution; cost_out [B] = J(u out); cost_trace [iters + 1][B] or NULL: row i =
+ * J before iteration i, row iters = cost_out.  H = 5 or 10. */
+int apg_quad_mpc_solve(const float *state0, const float *ref, int ref_cols, float dt,
+                       const ApgQuadParams *model, const ApgQuadLossWeights *weights,
+                       const ApgQuadMpcOptions *opt, int B, int H, float *u,
+                       float *cost_out, float *cost_trace, apg_stream_t stream);
+
+/* apg_quad_mlp_closed_loop_env with the policy replaced by "shift the warm
+ * start, solve, apply u[0]" (first step: from u = 0.5): same window rule, the
+ * solver sees the ABSOLUTE window rows (position, velocity), same divergence,
+ * attitude check, test_time break or reset to the reference state (the warm
+ * start is kept through a reset, as the reference keeps nlp_w0), same outputs
+ * and shapes, plus cost [T][B] or NULL (cost_out of every solve).  `plant`
+ * steps the flight (with `plant_learnt` != NULL through the learnt simulator),
+ * `model` is what the solver plans with: the same pointer for the nominal
+ * case, other parameters for the model-mismatch experiment.  H = 10.
+ * workspace: apg_quad_mpc_workspace_floats() floats (read only when
+ * plant_learnt is given; may be NULL otherwise). */
+int apg_quad_mpc_closed_loop(const float *traj, int L, float dt,
+                             const ApgQuadParams *plant,
+                             const ApgLearntResidual *plant_learnt,
+                             const ApgQuadParams *model,
+                             const ApgQuadLossWeights *weights,
+                             const ApgQuadMpcOptions *opt, int B, int H,
+                             int max_steps, float thresh_div, float thresh_stable,
+                             int test_time, float *div, int *steps, float *drone,
+                             float *actions, float *start_states, float *cost,
+                             float *workspace, apg_stream_t stream);
+int apg_quad_mpc_workspace_floats(void);
+
 /* "Planes x planes" reduction GEMM on the matrix cores (fp32 accuracy):
  *   C[m*ldc + j] = sum_{s<S} sum_{n<N} A[(m*S + s)*N + n] * B[bplane(j,s)*N + n]
  *   bplane(j, s) = bdesc[j] + (s / sdiv) * bdesc[J + j] + (s % sdiv) * bdesc[2J + j]

@@ -115,4 +115,6 @@ const char *apg_cpu_last_error_string(void);
 
 /* the learnt cart-pole simulator's twins (apg_cartpole_learnt_*_cpu) */
 #include "apg_cpu_learnt.h"
+/* the shooting MPC's twins (apg_quad_mpc_*_cpu) */
+#include "apg_cpu_mpc.h"
 #endif /* APG_CPU_H_ */

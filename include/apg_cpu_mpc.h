@@ -1,0 +1,37 @@
+/*
+ * apg_cpu_mpc.h - host twins of the shooting-MPC entry points of apg.h
+ * (apg_quad_mpc_solve, apg_quad_mpc_closed_loop), in libapg_cpu.so next to the
+ * twins of apg_cpu.h and under the same rules: HOST pointers, synchronous, the
+ * per-lane header of the kernels (csrc/quad_mpc_math.h) looped over the batch,
+ * signatures of apg.h minus the stream.  The closed loop flies the analytic
+ * plant only: `plant_learnt` must be NULL (the learnt simulator's step is a
+ * device function), `workspace` is not used (may be NULL).
+ */
+#ifndef APG_CPU_MPC_H_
+#define APG_CPU_MPC_H_
+
+#include "apg.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+int apg_quad_mpc_solve_cpu(const float *state0, const float *ref, int ref_cols, float dt,
+                           const ApgQuadParams *model, const ApgQuadLossWeights *weights,
+                           const ApgQuadMpcOptions *opt, int B, int H, float *u,
+                           float *cost_out, float *cost_trace);
+int apg_quad_mpc_closed_loop_cpu(const float *traj, int L, float dt,
+                                 const ApgQuadParams *plant,
+                                 const ApgLearntResidual *plant_learnt,
+                                 const ApgQuadParams *model,
+                                 const ApgQuadLossWeights *weights,
+                                 const ApgQuadMpcOptions *opt, int B, int H,
+                                 int max_steps, float thresh_div, float thresh_stable,
+                                 int test_time, float *div, int *steps, float *drone,
+                                 float *actions, float *start_states, float *cost,
+                                 float *workspace);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* APG_CPU_MPC_H_ */

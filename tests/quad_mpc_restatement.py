@@ -1,0 +1,266 @@
+"""Float64 / float32 restatement of the batched shooting MPC (include/apg.h:
+apg_quad_mpc_solve, apg_quad_mpc_closed_loop) - the arbiter of
+tests/test_quad_mpc_cpu.py and tests/test_gpu_quad_mpc.py.  Written from the
+ALGORITHM, not from the package: the model is `oracle.torch_port.QuadOracle`,
+the cost `torch_port.quad_mpc_loss`, the gradient torch autograd.
+
+    for it in range(iters):
+        J = quad_mpc_loss(unroll(model, state0, u), window, u)      # per trajectory
+        g = dJ/du
+        m = beta * m + alpha * g          # alpha: 1/300 thrust column, 1/10 rates
+        u = clamp(u - m, 0, 1)
+    J = cost of the returned u
+
+Not a test module (no test_ prefix); shared by the CPU and the GPU tests and by
+tools/time_quad_mpc.py's sanity check."""
+import ctypes
+import functools
+
+import numpy as np
+import torch
+
+from oracle import torch_port as tp
+
+BETA, ALPHA_THRUST, ALPHA_RATE = 0.5, 1.0 / 300.0, 1.0 / 10.0
+H = 10
+# the two drags of the G2 fixtures' modified_params (tests/test_cpu_twins.py: MOD)
+DRAGS = {"translational_drag": [.1, .2, .3], "rotational_drag": [.01, .02, .03]}
+
+
+def per_trajectory_cost(states, ref, u):
+    """quad_mpc_loss term by term with the batch axis kept: [B]."""
+    return (10 * ((states[:, :, :3] - ref[:, :, :3])**2).sum((1, 2))
+            + ((states[:, :, 6:9] - ref[:, :, 6:9])**2).sum((1, 2))
+            + 0.1 * (states[:, :, 9:12]**2).sum((1, 2))
+            + 0.1 * ((u[:, :, 1:] - .5)**2).sum((1, 2))
+            + 5 * ((u[:, :, 0] - .5)**2).sum(1))
+
+
+def cost_and_grad(model, state0, ref, u, dt):
+    """(J [B], dJ/du [B,H,4]); the scalar differentiated is torch_port's own
+    quad_mpc_loss over the batch (trajectories are independent, so its gradient
+    is every trajectory's own)."""
+    a = u.detach().clone().requires_grad_(True)
+    states = tp.unroll(model, state0, a, dt)
+    total = tp.quad_mpc_loss(states, ref, a)
+    total.backward()
+    J = per_trajectory_cost(states.detach(), ref, a.detach())
+    total = float(total.detach())
+    assert abs(float(J.sum()) - total) <= 1e-4 * abs(total)
+    return J, a.grad
+
+
+def cost(model, state0, ref, u, dt):
+    with torch.no_grad():
+        return per_trajectory_cost(tp.unroll(model, state0, u, dt), ref, u)
+
+
+def solve_snapshots(dtype, state0, ref, u0, dt, snaps, modified_params=None, beta=BETA,
+                    alpha_thrust=ALPHA_THRUST, alpha_rate=ALPHA_RATE):
+    """One run of max(snaps) iterations -> {iters: what `solve` returns for that
+    many iterations} (the iterates of a shorter solve are a prefix of a longer
+    one's: nothing in the rule depends on the iteration count)."""
+    model = tp.QuadOracle(modified_params, dtype=dtype)
+    s0, r, u = state0.to(dtype), ref.to(dtype), u0.to(dtype).clone()
+    alpha = torch.tensor([alpha_thrust, alpha_rate, alpha_rate, alpha_rate], dtype=dtype)
+    m = torch.zeros_like(u)
+    trace, out = [], {}
+    for it in range(max(snaps) + 1):
+        if it in snaps:
+            J = cost(model, s0, r, u, dt)
+            out[it] = dict(u=u.clone(), cost=J, trace=torch.stack(trace + [J]))
+        if it == max(snaps):
+            break
+        J, g = cost_and_grad(model, s0, r, u, dt)
+        trace.append(J)
+        m = beta * m + alpha * g
+        u = (u - m).clamp(0.0, 1.0)
+    return out
+
+
+def solve(dtype, state0, ref, u0, dt, iters, modified_params=None, **rule):
+    """-> dict(u [B,H,4], cost [B], trace [iters+1,B]) in `dtype`."""
+    return solve_snapshots(dtype, state0, ref, u0, dt, (iters,), modified_params,
+                           **rule)[iters]
+
+
+def shift(u):
+    return torch.cat((u[:, 1:], u[:, -1:]), 1)
+
+
+def projected_gradient_norm(state0, ref, u, dt, modified_params=None):
+    """Norm over the batch of the float64 gradient at `u` with the components
+    that point out of the box at an active bound removed."""
+    model = tp.QuadOracle(modified_params, dtype=torch.float64)
+    u = u.to(torch.float64)
+    _, g = cost_and_grad(model, state0.to(torch.float64), ref.to(torch.float64), u, dt)
+    out = ((u <= 0.0) & (g > 0)) | ((u >= 1.0) & (g < 0))   # descent leaves the box
+    return float(torch.where(out, torch.zeros_like(g), g).norm())
+
+
+def experiment_windows(B=256, seed=7, row=40, dt=0.1):
+    """The windows of the issue's experiment: rows row+1 .. row+H of
+    `quad_eval_trajectories(seed)`, the start state = row `row` perturbed by
+    0.2 m / 0.2 rad / 0.3 m/s (seeded), zero body rates.  -> state0 [B,12], ref
+    [B,H,9] float32."""
+    from apg_trajectory_tracking_amd import synthetic
+    traj = synthetic.quad_eval_trajectories(B, row + H + 1, dt, seed=seed)
+    g = torch.Generator(device="cpu")
+    g.manual_seed(seed + 1000)
+    state0 = torch.zeros(B, 12)
+    state0[:, 0:3] = traj[:, row, 0:3] + 0.2 * torch.randn(B, 3, generator=g)
+    state0[:, 3:6] = 0.2 * torch.randn(B, 3, generator=g)
+    state0[:, 6:9] = traj[:, row, 6:9] + 0.3 * torch.randn(B, 3, generator=g)
+    return state0, traj[:, row + 1:row + 1 + H].clone()
+
+
+def closed_loop(dtype, traj, dt, iters, max_steps, thresh_div, thresh_stable, test_time,
+                plant=None, model_params=None, second_step_probe=False):
+    """`torch_port.quad_closed_loop` with the policy replaced by "shift the warm
+    start, solve, apply u[0]" (first step from u = 0.5; the warm start survives
+    a reset).  traj [B,L,9] used as given.  plant: a dynamics callable
+    (QuadOracle / LearntQuadOracle; default the nominal QuadOracle in `dtype`);
+    model_params: modified parameters of the solver's model.
+    -> dict(drone [B,T+1,12], div [B,T], actions [B,T,4], cost [B,T], steps [B],
+    resets: number of (flight, step) pairs that failed)."""
+    B, L, _ = traj.shape
+    ref = traj.to(dtype)
+    plant = plant if plant is not None else tp.QuadOracle(dtype=dtype)
+    T = min(max_steps, L + 1)
+    state = torch.zeros(B, 12, dtype=dtype)
+    state[:, :3] = ref[:, 0, :3]
+    cur = 0
+    alive = torch.ones(B, dtype=torch.bool)
+    out = dict(drone=torch.zeros(B, T + 1, 12, dtype=dtype), div=torch.zeros(B, T, dtype=dtype),
+               actions=torch.zeros(B, T, 4, dtype=dtype), cost=torch.zeros(B, T, dtype=dtype),
+               steps=torch.zeros(B, dtype=torch.long), resets=0, start=[], windows=[])
+    out["drone"][:, 0] = state
+    last = ref[:, -1, :3]
+    u = torch.full((B, H, 4), 0.5, dtype=dtype)
+    for i in range(T):
+        if cur >= L - H:
+            left = ref[:, cur:]
+            pad = torch.zeros(B, H - (L - cur), 9, dtype=dtype)
+            pad[:, :, :3] = last[:, None]
+            window = torch.cat((left, pad), 1)
+        else:
+            window = ref[:, cur + 1:cur + H + 1]
+            cur += 1
+        if i > 0:
+            u = shift(u)
+        if second_step_probe and i < 2:
+            out["start"].append(state.clone()), out["windows"].append(window.clone())
+        res = solve(dtype, state, window, u, dt, iters, model_params)
+        u = res["u"]
+        action = u[:, 0]
+        with torch.no_grad():
+            new = plant(state.to(plant.dtype) if hasattr(plant, "dtype") else state,
+                        action, dt).to(dtype)
+        on_line = ref[:, cur, :3]
+        div = torch.linalg.norm(on_line - new[:, :3], dim=1)
+        stable = (new[:, 3:5].abs() < thresh_stable).all(1)
+        rec = alive.clone()
+        out["drone"][rec, i + 1] = new[rec]
+        out["div"][rec, i] = div[rec]
+        out["actions"][rec, i] = action[rec]
+        out["cost"][rec, i] = res["cost"][rec]
+        out["steps"][rec] = i + 1
+        failed = (div > thresh_div) | ~stable
+        out["resets"] += int((failed & rec).sum())
+        if test_time:
+            alive = alive & ~failed
+            if not alive.any():
+                break
+        reset = torch.cat((ref[:, cur], torch.zeros(B, 3, dtype=dtype)), 1)
+        state = torch.where((failed & (not test_time))[:, None], reset, new)
+        if i >= L:
+            break
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def loop_case(dtype, mismatch, B=32, steps=250, iters=10):
+    """The closed-loop cases of the tests (nominal / drag mismatch), cached: the
+    CPU and the GPU tests of one session share the restatement's runs."""
+    from apg_trajectory_tracking_amd import synthetic
+    traj = synthetic.quad_eval_trajectories(B, 501, 0.1, seed=42)
+    traj[:, :, 2] += 3
+    plant = tp.QuadOracle(DRAGS if mismatch else None, dtype=dtype)
+    out = closed_loop(dtype, traj, 0.1, iters, steps, LOOP_THRESH_DIV, 1.0, 0, plant=plant)
+    return traj, out
+
+
+# thresh_div of the closed-loop cases: the issue asks for >= 2 x the largest
+# divergence the float64 restatement shows (measured: see test_quad_mpc_cpu.py)
+LOOP_THRESH_DIV = 3.0
+
+
+# ---- the host twins (libapg_cpu.so) behind the restatement's tensors --------
+def twins():
+    from apg_trajectory_tracking_amd import _capi, build as b
+    lib = ctypes.CDLL(b.build_cpu())
+    P, I, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    lib.apg_quad_mpc_solve_cpu.argtypes = [
+        P, P, I, F, ctypes.POINTER(_capi.ApgQuadParams),
+        ctypes.POINTER(_capi.ApgQuadLossWeights), ctypes.POINTER(_capi.ApgQuadMpcOptions),
+        I, I, P, P, P]
+    lib.apg_quad_mpc_closed_loop_cpu.argtypes = [
+        P, I, F, ctypes.POINTER(_capi.ApgQuadParams), ctypes.POINTER(_capi.ApgLearntResidual),
+        ctypes.POINTER(_capi.ApgQuadParams), ctypes.POINTER(_capi.ApgQuadLossWeights),
+        ctypes.POINTER(_capi.ApgQuadMpcOptions), I, I, I, F, F, I, P, P, P, P, P, P, P]
+    lib.apg_cpu_last_error_string.restype = ctypes.c_char_p
+    return lib
+
+
+def _params(modified=None):
+    from apg_trajectory_tracking_amd import functional as F
+    cfg = dict(tp.QUAD_CFG)
+    cfg.update(modified or {})
+    return F.quad_params(cfg)
+
+
+def _options(iters, beta=BETA, alpha_thrust=ALPHA_THRUST, alpha_rate=ALPHA_RATE):
+    from apg_trajectory_tracking_amd import _capi
+    return _capi.ApgQuadMpcOptions(int(iters), beta, alpha_thrust, alpha_rate)
+
+
+def twin_solve(tw, state0, ref, u0, dt, iters, modified_params=None):
+    """apg_quad_mpc_solve_cpu on [B,12] / [B,H,C] / [B,H,4] float32 tensors ->
+    dict(u, cost, trace) as `solve` returns them."""
+    from apg_trajectory_tracking_amd import functional as F
+    B, Hh, C = ref.shape
+    s = state0.float().t().contiguous()
+    r = ref.float().permute(1, 2, 0).contiguous()
+    u = u0.float().permute(1, 2, 0).contiguous()
+    cost_out, trace = torch.zeros(B), torch.zeros(iters + 1, B)
+    rc = tw.apg_quad_mpc_solve_cpu(
+        s.data_ptr(), r.data_ptr(), C, dt, ctypes.byref(_params(modified_params)),
+        ctypes.byref(F.quad_loss_weights()), ctypes.byref(_options(iters)), B, Hh,
+        u.data_ptr(), cost_out.data_ptr(), trace.data_ptr())
+    assert rc == 0, tw.apg_cpu_last_error_string()
+    return dict(u=u.permute(2, 0, 1).contiguous(), cost=cost_out, trace=trace)
+
+
+def twin_closed_loop(tw, traj, dt, iters, max_steps, thresh_div, thresh_stable, test_time,
+                     plant_params=None, model_params=None):
+    """apg_quad_mpc_closed_loop_cpu -> the dict `closed_loop` returns ([B, ...])."""
+    from apg_trajectory_tracking_amd import functional as F
+    B, L, _ = traj.shape
+    T = min(max_steps, L + 1)
+    tr = traj.float().permute(1, 2, 0).contiguous()
+    div, cost_ = torch.zeros(T, B), torch.zeros(T, B)
+    steps = torch.zeros(B, dtype=torch.int32)
+    drone, actions, start = torch.zeros(T + 1, 12, B), torch.zeros(T, 4, B), torch.zeros(T, 12, B)
+    rc = tw.apg_quad_mpc_closed_loop_cpu(
+        tr.data_ptr(), L, dt, ctypes.byref(_params(plant_params)), None,
+        ctypes.byref(_params(model_params)), ctypes.byref(F.quad_loss_weights()),
+        ctypes.byref(_options(iters)), B, H, max_steps, thresh_div, thresh_stable,
+        test_time, div.data_ptr(), steps.data_ptr(), drone.data_ptr(), actions.data_ptr(),
+        start.data_ptr(), cost_.data_ptr(), None)
+    assert rc == 0, tw.apg_cpu_last_error_string()
+    return dict(div=div.t(), cost=cost_.t(), steps=steps.long(), drone=drone.permute(2, 0, 1),
+                actions=actions.permute(2, 0, 1), start=start.permute(2, 0, 1))
+
+
+def to_numpy(x):
+    return np.asarray(x.detach().cpu(), dtype=np.float64)
