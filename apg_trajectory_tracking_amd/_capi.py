@@ -69,6 +69,14 @@ class ApgLearntResidual(ctypes.Structure):
         "linear_at", "w1", "b1", "w2", "b2")]
 
 
+class ApgQuadFlight(ctypes.Structure):
+    """include/apg.h: reference, rule and log of a closed-loop quadrotor flight."""
+    _fields_ = [("traj", ctypes.c_void_p), ("L", ctypes.c_int), ("max_steps", ctypes.c_int),
+                ("thresh_div", ctypes.c_float), ("thresh_stable", ctypes.c_float),
+                ("test_time", ctypes.c_int)] + [(n, ctypes.c_void_p) for n in (
+                    "div", "steps", "drone", "actions", "start_states")]
+
+
 class ApgQuadMpcOptions(ctypes.Structure):
     """include/apg.h: the shooting MPC's iteration count and step rule."""
     _fields_ = [("iters", ctypes.c_int), ("beta", ctypes.c_float),
@@ -252,19 +260,11 @@ SIGNATURES = {
         _P, _P, _P, _P, _P, _P, ctypes.POINTER(ApgMlpPolicyGrads), _P, _P, _P,
         ctypes.POINTER(ApgMlpSgdUpdate), _P],
     "apg_quad_mlp_closed_loop": [
-        _P, _I, _F, ctypes.POINTER(ApgQuadParams), ctypes.POINTER(ApgMlpPolicy),
-        _I, _I, _I, _F, _F, _I, _P, _P, _P, _P, _P, _P, _P],
+        ctypes.POINTER(ApgQuadFlight), _F, ctypes.POINTER(ApgQuadParams),
+        ctypes.POINTER(ApgLearntResidual), ctypes.POINTER(ApgMlpPolicy), _I, _I, _P, _P],
     "apg_quad_lstm_closed_loop": [
-        _P, _I, _P, _P, _F, ctypes.POINTER(ApgQuadParams),
-        ctypes.POINTER(ApgLstmPolicy), _I, _I, _I, _F, _F, _I, _P, _P, _P, _P,
-        _P, _P, _P],
-    "apg_quad_mlp_closed_loop_env": [
-        _P, _I, _F, ctypes.POINTER(ApgQuadParams), ctypes.POINTER(ApgLearntResidual),
-        ctypes.POINTER(ApgMlpPolicy), _I, _I, _I, _F, _F, _I, _P, _P, _P, _P, _P, _P, _P],
-    "apg_quad_lstm_closed_loop_env": [
-        _P, _I, _P, _P, _F, ctypes.POINTER(ApgQuadParams),
-        ctypes.POINTER(ApgLearntResidual), ctypes.POINTER(ApgLstmPolicy), _I, _I, _I,
-        _F, _F, _I, _P, _P, _P, _P, _P, _P, _P],
+        ctypes.POINTER(ApgQuadFlight), _P, _P, _F, ctypes.POINTER(ApgQuadParams),
+        ctypes.POINTER(ApgLearntResidual), ctypes.POINTER(ApgLstmPolicy), _I, _I, _P, _P],
     "apg_planes_gemm_grouped": [ctypes.POINTER(ApgGemmProblem), _I, _P, _I, _P],
     "apg_to_soa": [_P, _P, _I, _I, _I, _P, _P],
     "apg_to_soa_multi": [ctypes.POINTER(ApgSoaItem), _I, _I, _P],
@@ -284,11 +284,6 @@ SIGNATURES = {
         _P, _P, _F, ctypes.POINTER(ApgWingParams), ctypes.POINTER(ctypes.c_float),
         _I, _P, _P, _P, _P, _P, _P],
     "apg_wing_mlp_closed_loop": [
-        _P, _I, _P, _F, ctypes.POINTER(ApgWingParams),
-        ctypes.POINTER(ApgWingPolicy), ctypes.POINTER(ctypes.c_float),
-        ctypes.POINTER(ctypes.c_float), _F, _I, _I, _I, _F, _F, _I, _P, _P, _P,
-        _P, _P, _P, _P, _P],
-    "apg_wing_mlp_closed_loop_env": [
         _P, _I, _P, _F, ctypes.POINTER(ApgWingParams), ctypes.POINTER(ctypes.c_float),
         ctypes.POINTER(ApgLearntResidual),
         ctypes.POINTER(ApgWingPolicy), ctypes.POINTER(ctypes.c_float),
@@ -341,9 +336,9 @@ SIGNATURES = {
         ctypes.POINTER(ApgQuadLossWeights), ctypes.POINTER(ApgQuadMpcOptions), _I, _I,
         _P, _P, _P, _P],
     "apg_quad_mpc_closed_loop": [
-        _P, _I, _F, ctypes.POINTER(ApgQuadParams), ctypes.POINTER(ApgLearntResidual),
-        ctypes.POINTER(ApgQuadParams), ctypes.POINTER(ApgQuadLossWeights),
-        ctypes.POINTER(ApgQuadMpcOptions), _I, _I, _I, _F, _F, _I, _P, _P, _P, _P, _P,
+        ctypes.POINTER(ApgQuadFlight), _F, ctypes.POINTER(ApgQuadParams),
+        ctypes.POINTER(ApgLearntResidual), ctypes.POINTER(ApgQuadParams),
+        ctypes.POINTER(ApgQuadLossWeights), ctypes.POINTER(ApgQuadMpcOptions), _I, _I,
         _P, _P, _P],
     "apg_quad_mpc_workspace_floats": [],
     "apg_reduce_loss_partials": [_P, _I, _P, _P],

@@ -716,76 +716,28 @@ int apg_quad_mpc_solve_cpu(const float *state0, const float *ref, int ref_cols, 
   return APG_OK;
 }
 
-int apg_quad_mpc_closed_loop_cpu(const float *traj, int L, float dt,
+int apg_quad_mpc_closed_loop_cpu(const ApgQuadFlight *flight, float dt,
                                  const ApgQuadParams *plant,
                                  const ApgLearntResidual *plant_learnt,
                                  const ApgQuadParams *model,
                                  const ApgQuadLossWeights *weights,
-                                 const ApgQuadMpcOptions *opt, int B, int H,
-                                 int max_steps, float thresh_div, float thresh_stable,
-                                 int test_time, float *div, int *steps, float *drone,
-                                 float *actions, float *start_states, float *cost,
+                                 const ApgQuadMpcOptions *opt, int B, int H, float *cost,
                                  float *workspace) {
   (void)workspace;
-  constexpr int kH = 10;
   if (int e = check_mpc(model, weights, opt, B, H, false)) return e;
   if (!plant) return fail("plant is NULL");
   if (plant_learnt) return fail("the host twin flies the analytic plant only");
-  if (L <= kH || max_steps < 1)
-    return fail("closed loop needs L > %d reference rows and max_steps >= 1", kH);
-  if (B == 0) return APG_OK;
-  if (!traj || !div || !steps) return fail("NULL buffer");
-  const int T = max_steps < L + 1 ? max_steps : L + 1;
+  QuadFlightRule rule;
+  if (const char *e = quad_flight_check(flight, plant_learnt, B, &rule)) return fail("%s", e);
   const QuadConst cp = make_const(*plant, dt), cm = make_const(*model, dt);
   const size_t Bs = (size_t)B;
-  const auto row = [&](int r, int col, int b) { return traj[((size_t)r * 9 + col) * Bs + b]; };
-  for (int b = 0; b < B; ++b) {
-    float s[12], win[kH][6], u[kH][4];
-    for (int i = 0; i < 12; ++i) s[i] = i < 3 ? row(0, i, b) : 0.f;  // zero_reset
-    for (int r = 0; r < kH; ++r)
-      for (int i = 0; i < 3; ++i) win[r][i] = row(1 + r, i, b), win[r][3 + i] = row(1 + r, 6 + i, b);
-    for (int k = 0; k < kH; ++k)
-      for (int j = 0; j < 4; ++j) u[k][j] = 0.5f;
-    if (drone)
-      for (int i = 0; i < 12; ++i) drone[i * Bs + b] = s[i];
-    int n = 0;
-    for (int k = 0; k < T; ++k) {
-      if (start_states)
-        for (int i = 0; i < 12; ++i) start_states[((size_t)k * 12 + i) * Bs + b] = s[i];
-      if (k > 0) mpc_shift<kH>(u);
-      const float J = mpc_solve<kH>(s, win, u, cm, *weights, *opt, [](int, float) {});
-      if (cost) cost[(size_t)k * Bs + b] = J;
-      if (actions)
-        for (int j = 0; j < 4; ++j) actions[((size_t)k * 4 + j) * Bs + b] = u[0][j];
-      quad_step(s, u[0], cp, make_trig(&s[3]));
-      float d2 = 0.f;
-      for (int q = 0; q < 3; ++q) {
-        const float e = win[0][q] - s[q];
-        d2 = fmaf(e, e, d2);
-      }
-      const float dv = sqrtf(d2);
-      const bool stable = fabsf(s[3]) < thresh_stable && fabsf(s[4]) < thresh_stable;
-      const bool failed = dv > thresh_div || !stable;
-      if (drone)
-        for (int i = 0; i < 12; ++i) drone[((size_t)(k + 1) * 12 + i) * Bs + b] = s[i];
-      div[(size_t)k * Bs + b] = dv;
-      n = k + 1;
-      if (test_time) {
-        if (failed) break;
-      } else if (failed) {  // get_current_full_state: row cur, zero rates
-        const int cur = k + 1 < L - kH ? k + 1 : L - kH;
-        for (int i = 0; i < 9; ++i) s[i] = row(cur, i, b);
-        for (int i = 9; i < 12; ++i) s[i] = 0.f;
-      }
-      if (k + 2 <= L - kH) {  // get_ref_traj advanced: slide, fetch row k+1+H
-        for (int r = 0; r + 1 < kH; ++r)
-          for (int i = 0; i < 6; ++i) win[r][i] = win[r + 1][i];
-        for (int i = 0; i < 3; ++i)
-          win[kH - 1][i] = row(k + 1 + kH, i, b), win[kH - 1][3 + i] = row(k + 1 + kH, 6 + i, b);
-      }
-    }
-    steps[b] = n;
-  }
+  for (size_t b = 0; b < Bs; ++b)
+    flight->steps[b] = mpc_flight(
+        [&](int r, int col) { return flight->traj[((size_t)r * 9 + col) * Bs + b]; },
+        [&](float (&s)[12], const float (&u0)[4]) { quad_step(s, u0, cp, make_trig(&s[3])); },
+        cm, *weights, *opt, rule,
+        MpcFlightLog{flight->div, flight->drone, flight->actions, flight->start_states, cost,
+                     Bs, b});
   return APG_OK;
 }
 

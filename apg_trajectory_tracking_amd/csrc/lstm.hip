@@ -39,6 +39,7 @@
 #include "policy_tm.h"
 #include "quad_math.h"
 #include "learnt_residual.h"
+#include "quad_flight.h"
 
 namespace apg {
 namespace {
@@ -411,26 +412,14 @@ __global__ __launch_bounds__(kThreads) void lstm_rollout_fwd_kernel(FwdArgs A) {
 // ------------------------------------------------------ closed-loop evaluation
 // N2 for the LSTM controller: QuadEvaluator.follow_trajectory
 // ("rand", scripts/evaluate_drone.py:81-194) for a batch of reference
-// trajectories - see mlp_closed_loop_kernel (mlp_rollout.hip) for the loop; here the
-// hidden / cell state is carried through all steps (it is reset once per
-// evaluator, evaluate_drone.py:56-58, never on a divergence).
-struct LoopArgs {
-  const float *traj;  // [L][9][B] (position, euler, velocity) rows
+// trajectories - the flight loop is quad_flight_half_wave (quad_flight.h); here the
+// policy of a step, whose hidden / cell state is carried through all steps (it
+// is reset once per evaluator, evaluate_drone.py:56-58, never on a divergence).
+struct LoopArgs : QuadFlightArgs {
   const float *h0, *c0;  // [8][B]
-  float *div;         // [T][B]
-  int *steps;         // [B] iterations executed
-  float *drone;       // [T+1][12][B] or NULL: states after each step
-  float *actions;     // [T][4][B] or NULL
-  float *start;       // [T][12][B] or NULL: states the policy saw
-  const float *tables;
-  QuadConst c;
-  int B, L, T, test_time;
-  float thresh_div, thresh_stable;
-  int learnt;         // LearntDynamics environment (learnt_residual.h)
+  const float *tables;   // the policy's, then a LearntDynamics environment's
 };
 
-// LEARNT: the environment is a LearntDynamics (a second instantiation, so that the
-// analytic loop keeps its registers)
 template <bool LEARNT>
 __global__ __launch_bounds__(kThreads) void lstm_closed_loop_kernel(LoopArgs A) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -440,52 +429,19 @@ __global__ __launch_bounds__(kThreads) void lstm_closed_loop_kernel(LoopArgs A) 
   const LdsView L(lds, lane);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int b = (blockIdx.x * (kThreads / 64) + wave) * 32 + (lane & 31);
-  const int B = A.B, T = A.T;
-  const bool live = b < B;
-  const bool st_lo = live && hi == 0;
-  const unsigned pitchB = (unsigned)B * 4u;
-  const QuadConst c = A.c;
-  // a NULL output becomes an empty buffer: every store to it is dropped
-  const Planes Ptr(A.traj, A.L * 9, pitchB), Pdv(A.div, T, pitchB);
+  const unsigned pitchB = (unsigned)A.B * 4u;
   const Planes Ph0(A.h0, kNH, pitchB), Pc0(A.c0, kNH, pitchB);
-  const Planes Pdr(A.drone, A.drone ? (T + 1) * 12 : 0, pitchB);
-  const Planes Pac(A.actions, A.actions ? T * 4 : 0, pitchB);
-  const Planes Pss(A.start, A.start ? T * 12 : 0, pitchB);
-  const unsigned vb = live ? (unsigned)b * 4u : kDead;
-  const unsigned vb_u = live ? vb + (hi ? 4u * pitchB : 0u) : kDead;
-  // window columns of this half-wave: lower (x, y, z, vx, -), upper (vy, vz,
-  // vx, vy, vz) - policy channels 0-3 / 4-8; trajectory columns 6..8 = velocity
-  unsigned vcol[5];
-#pragma unroll
-  for (int j = 0; j < 5; ++j) {
-    const int lo = j < 3 ? j : 6, up = j < 2 ? 7 + j : 4 + j;
-    vcol[j] = live ? vb + (unsigned)(hi ? up : lo) * pitchB : kDead;
-  }
-  float s[12], h[4], cell[4];
-#pragma unroll
-  for (int i = 0; i < 12; ++i) s[i] = i < 3 ? Ptr.ld(vb, i * pitchB) : 0.f;  // zero_reset
+  const unsigned vb_u = b < A.B ? (unsigned)b * 4u + (hi ? 4u * pitchB : 0u) : kDead;
+  float h[4], cell[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     h[r] = Ph0.ld(vb_u, r * pitchB);
     cell[r] = Pc0.ld(vb_u, r * pitchB);
   }
-  float w[kH][5];  // rows cur + 1 .. cur + H of the trajectory
-#pragma unroll
-  for (int r = 0; r < kH; ++r)
-#pragma unroll
-    for (int j = 0; j < 5; ++j) w[r][j] = Ptr.ld(vcol[j], ((1 + r) * 9) * pitchB);
-#pragma unroll
-  for (int i = 0; i < 12; ++i) Pdr.st(st_lo ? vb : kDead, i * pitchB, s[i]);
-  bool alive = live;
-  int steps = 0;
-
-#pragma unroll 1
-  for (int k = 0; k < T; ++k) {
-    const unsigned pB = opaque(pitchB);
-    const unsigned vrec = (alive && hi == 0) ? vb : kDead;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) Pss.st(vrec, (k * 12 + i) * pB, s[i]);
-    const Trig t = make_trig(&s[3]);
+  quad_flight_half_wave<LEARNT, kThreads>(A, lds + kFwd16Lds, [&](const float (&s)[12],
+                                                                  const Trig &t,
+                                                                  const float (&w)[kH][5],
+                                                                  float (&act)[4]) {
     float feat[kNF];
     quad_features(s, t, feat);
     // gates and conv on the 16-bit matrix pipe (policy_mfma16.h), as the
@@ -558,7 +514,6 @@ __global__ __launch_bounds__(kThreads) void lstm_closed_loop_kernel(LoopArgs A) 
       cell[r] = fmaf(gf, cell[r], gi * gg);
       h[r] = go * tanh_fast(cell[r]);
     }
-    float act[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float z = 0.f;
@@ -566,48 +521,8 @@ __global__ __launch_bounds__(kThreads) void lstm_closed_loop_kernel(LoopArgs A) 
       for (int r = 0; r < 4; ++r) z = fmaf(L.T(hTo + (j * 4 + r) * 2), h[r], z);
       z += other_half(z);
       act[j] = fminf(fmaxf(sigmoidf_(z + L.U(hBo + j)), 0.f), 1.f);  // np.clip
-      Pac.st(vrec, (k * 4 + j) * pB, act[j]);
     }
-    if (LEARNT) learnt_quad_step(s, act, c, t, lds + kFwd16Lds, hi);
-    else quad_step(s, act, c, t);
-    // window row 0 is reference[cur] after get_ref_traj: project_on_ref
-    float d2 = 0.f;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const float oth = other_half(w[0][q]);
-      const float e = (hi ? oth : w[0][q]) - s[q];
-      d2 = fmaf(e, e, d2);
-    }
-    const float dv = sqrtf(d2);
-    const bool stable = fabsf(s[3]) < A.thresh_stable && fabsf(s[4]) < A.thresh_stable;
-    const bool failed = dv > A.thresh_div || !stable;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) Pdr.st(vrec, ((k + 1) * 12 + i) * pB, s[i]);
-    Pdv.st(vrec, k * pB, dv);
-    if (alive) steps = k + 1;
-    if (A.test_time) {
-      alive = alive && !failed;
-      if (!__any(alive)) break;
-    } else if (__any(failed)) {  // get_current_full_state: row cur, zero rates
-      const int cur = k + 1 < A.L - kH ? k + 1 : A.L - kH;
-#pragma unroll
-      for (int i = 0; i < 9; ++i) {
-        const float rv = Ptr.ld(vb, (cur * 9 + i) * pB);
-        s[i] = failed ? rv : s[i];
-      }
-#pragma unroll
-      for (int i = 9; i < 12; ++i) s[i] = failed ? 0.f : s[i];
-    }
-    if (k + 2 <= A.L - kH) {  // get_ref_traj advanced: slide, fetch row k+1+H
-#pragma unroll
-      for (int r = 0; r + 1 < kH; ++r)
-#pragma unroll
-        for (int j = 0; j < 5; ++j) w[r][j] = w[r + 1][j];
-#pragma unroll
-      for (int j = 0; j < 5; ++j) w[kH - 1][j] = Ptr.ld(vcol[j], ((k + 1 + kH) * 9) * pB);
-    }
-  }
-  if (st_lo) A.steps[b] = steps;
+  });
 }
 
 // ------------------------------------------------------------ reverse sweep
@@ -2181,58 +2096,21 @@ int apg_quad_lstm_step_tail(const ApgLstmStepTail *tail, apg_stream_t stream) {
   return check_launch("quad_lstm_step_tail");
 }
 
-int apg_quad_lstm_closed_loop(const float *traj, int L, const float *h0,
-                              const float *c0, float dt,
-                              const ApgQuadParams *params,
-                              const ApgLstmPolicy *policy, int B, int H,
-                              int max_steps, float thresh_div,
-                              float thresh_stable, int test_time, float *div,
-                              int *steps, float *drone, float *actions,
-                              float *start_states, float *workspace,
-                              apg_stream_t stream) {
-  return apg_quad_lstm_closed_loop_env(traj, L, h0, c0, dt, params, nullptr, policy, B, H,
-                                       max_steps, thresh_div, thresh_stable, test_time, div,
-                                       steps, drone, actions, start_states, workspace, stream);
-}
-
-int apg_quad_lstm_closed_loop_env(const float *traj, int L, const float *h0, const float *c0,
-                                  float dt, const ApgQuadParams *params,
-                                  const ApgLearntResidual *learnt, const ApgLstmPolicy *policy,
-                                  int B, int H, int max_steps, float thresh_div,
-                                  float thresh_stable, int test_time, float *div, int *steps,
-                                  float *drone, float *actions, float *start_states,
-                                  float *workspace, apg_stream_t stream) {
+int apg_quad_lstm_closed_loop(const ApgQuadFlight *flight, const float *h0, const float *c0,
+                              float dt, const ApgQuadParams *params,
+                              const ApgLearntResidual *learnt, const ApgLstmPolicy *policy,
+                              int B, int H, float *workspace, apg_stream_t stream) {
   if (int e = check_lstm(params, B, H)) return e;
   if (int e = check_policy(policy)) return e;
-  if (learnt && (!learnt->linear_at || !learnt->w1 || !learnt->b1 || !learnt->w2 ||
-                 !learnt->b2)) {
-    set_error("learnt simulator: weight pointer is NULL");
-    return APG_ERR_ARG;
-  }
-  if (L <= kH || max_steps < 1) {
-    set_error("closed loop needs L > %d reference rows and max_steps >= 1", kH);
-    return APG_ERR_ARG;
-  }
-  const int T = max_steps < L + 1 ? max_steps : L + 1;
-  const long long planes = (long long)(T + 1) * 12 > (long long)L * 9
-                               ? (long long)(T + 1) * 12 : (long long)L * 9;
-  if ((long long)B * 4 * planes >= (1ll << 32) - 64) {
-    set_error("B * steps too large for 32-bit plane offsets; split the batch");
-    return APG_ERR_ARG;
-  }
+  LoopArgs A;
+  if (int e = set_flight(A, flight, learnt, B)) return e;
   if (B == 0) return APG_OK;
-  if (!traj || !h0 || !c0 || !div || !steps || !workspace) {
+  if (!h0 || !c0 || !workspace) {
     set_error("NULL buffer");
     return APG_ERR_ARG;
   }
-  LoopArgs A;
-  A.traj = traj, A.h0 = h0, A.c0 = c0, A.div = div, A.steps = steps;
-  A.drone = drone, A.actions = actions, A.start = start_states;
-  A.tables = workspace;
+  A.h0 = h0, A.c0 = c0, A.tables = workspace;
   A.c = make_const(*params, dt);
-  A.B = B, A.L = L, A.T = T, A.test_time = test_time;
-  A.thresh_div = thresh_div, A.thresh_stable = thresh_stable;
-  A.learnt = learnt != nullptr;
   PackArgs P;
   P.pol = *policy, P.dst = workspace;
   hipStream_t st = (hipStream_t)stream;

@@ -698,30 +698,14 @@ int apg_wing_policy_bwd(const float *actions, const float *grad_actions,
   return check_launch("wing_policy_bwd");
 }
 
-int apg_wing_mlp_closed_loop(const float *targets, int n_targets,
-                             const float *state0, float dt,
-                             const ApgWingParams *params,
-                             const ApgWingPolicy *policy, const float *mean,
-                             const float *std, float data_dt, int data_horizon,
-                             int B, int max_steps, float thresh_div,
-                             float thresh_stable, int test_time,
-                             float *div_linear, float *div_pass, float *div_fail,
-                             int *steps, float *drone, float *seen,
-                             float *workspace, apg_stream_t stream) {
-  return apg_wing_mlp_closed_loop_env(targets, n_targets, state0, dt, params, nullptr, nullptr,
-                                      policy, mean, std, data_dt, data_horizon, B, max_steps,
-                                      thresh_div, thresh_stable, test_time, div_linear,
-                                      div_pass, div_fail, steps, drone, seen, workspace, stream);
-}
-
-int apg_wing_mlp_closed_loop_env(const float *targets, int n_targets, const float *state0,
-                                 float dt, const ApgWingParams *params, const float *inertia,
-                                 const ApgLearntResidual *learnt, const ApgWingPolicy *policy,
-                                 const float *mean, const float *std, float data_dt,
-                                 int data_horizon, int B, int max_steps, float thresh_div,
-                                 float thresh_stable, int test_time, float *div_linear,
-                                 float *div_pass, float *div_fail, int *steps, float *drone,
-                                 float *seen, float *workspace, apg_stream_t stream) {
+int apg_wing_mlp_closed_loop(const float *targets, int n_targets, const float *state0,
+                             float dt, const ApgWingParams *params, const float *inertia,
+                             const ApgLearntResidual *learnt, const ApgWingPolicy *policy,
+                             const float *mean, const float *std, float data_dt,
+                             int data_horizon, int B, int max_steps, float thresh_div,
+                             float thresh_stable, int test_time, float *div_linear,
+                             float *div_pass, float *div_fail, int *steps, float *drone,
+                             float *seen, float *workspace, apg_stream_t stream) {
   if (int e = check_wing_policy(policy, B)) return e;
   if ((inertia != nullptr) != (learnt != nullptr)) {
     set_error("learnt environment: `inertia` and `learnt` come together");

@@ -86,25 +86,19 @@ __device__ __forceinline__ void learnt_quad_step_lane(float (&s)[12], const floa
 
 struct MpcLoopArgs {
   const float *traj;  // [L][9][B]
-  float *div;         // [T][B]
   int *steps;         // [B]
-  float *drone;       // [T+1][12][B] or NULL
-  float *actions;     // [T][4][B] or NULL
-  float *start;       // [T][12][B] or NULL
-  float *cost;        // [T][B] or NULL
+  MpcFlightLog log;   // B, b: set per lane
   const float *learnt;  // packed plant residual (learnt_pack_kernel) or NULL
   QuadConst cp, cm;   // plant, model
   ApgQuadLossWeights w;
   ApgQuadMpcOptions o;
-  int B, L, T, test_time;
-  float thresh_div, thresh_stable;
+  QuadFlightRule rule;
+  int B;
 };
 
-// The loop of mlp_closed_loop_kernel (mlp_rollout.hip) with the policy replaced
-// by "shift, solve, apply u[0]"; one flight per lane.
+// mpc_flight (quad_mpc_math.h), one flight per lane
 template <bool LEARNT>
 __global__ __launch_bounds__(kMpcThreads) void quad_mpc_closed_loop_kernel(MpcLoopArgs A) {
-  constexpr int H = 10;
   __shared__ float lr[LEARNT ? kLearntFloats : 1];
   if (LEARNT) {
     for (int i = threadIdx.x; i < kLearntFloats; i += kMpcThreads) lr[i] = A.learnt[i];
@@ -113,88 +107,17 @@ __global__ __launch_bounds__(kMpcThreads) void quad_mpc_closed_loop_kernel(MpcLo
   const int b = blockIdx.x * kMpcThreads + threadIdx.x;
   if (b >= A.B) return;
   const size_t B = (size_t)A.B;
-  const int T = A.T, L = A.L;
   const float *tr = A.traj + b;
-  float s[12], win[H][6], u[H][4];
-#pragma unroll
-  for (int i = 0; i < 12; ++i) s[i] = i < 3 ? tr[i * B] : 0.f;  // zero_reset
-#pragma unroll
-  for (int r = 0; r < H; ++r)
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      win[r][i] = tr[((size_t)(1 + r) * 9 + i) * B];
-      win[r][3 + i] = tr[((size_t)(1 + r) * 9 + 6 + i) * B];
-    }
-#pragma unroll
-  for (int k = 0; k < H; ++k)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) u[k][j] = 0.5f;
-  if (A.drone) {
-#pragma unroll
-    for (int i = 0; i < 12; ++i) A.drone[i * B + b] = s[i];
-  }
-  bool alive = true;
-  int steps = 0;
-
-#pragma unroll 1
-  for (int k = 0; k < T; ++k) {
-    if (A.start && alive) {
-#pragma unroll
-      for (int i = 0; i < 12; ++i) A.start[((size_t)k * 12 + i) * B + b] = s[i];
-    }
-    if (k > 0) mpc_shift<H>(u);
-    const float J = mpc_solve<H>(s, win, u, A.cm, A.w, A.o, [](int, float) {});
-    if (alive) {
-      if (A.cost) A.cost[(size_t)k * B + b] = J;
-      if (A.actions) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) A.actions[((size_t)k * 4 + j) * B + b] = u[0][j];
-      }
-    }
-    const Trig t = make_trig(&s[3]);
-    if (LEARNT) learnt_quad_step_lane(s, u[0], A.cp, t, lr);
-    else quad_step(s, u[0], A.cp, t);
-    // window row 0 is reference[cur] after get_ref_traj: project_on_ref
-    float d2 = 0.f;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const float e = win[0][q] - s[q];
-      d2 = fmaf(e, e, d2);
-    }
-    const float dv = sqrtf(d2);
-    const bool stable = fabsf(s[3]) < A.thresh_stable && fabsf(s[4]) < A.thresh_stable;
-    const bool failed = dv > A.thresh_div || !stable;
-    if (alive) {
-      if (A.drone) {
-#pragma unroll
-        for (int i = 0; i < 12; ++i) A.drone[((size_t)(k + 1) * 12 + i) * B + b] = s[i];
-      }
-      A.div[(size_t)k * B + b] = dv;
-      steps = k + 1;
-    }
-    if (A.test_time) {
-      alive = alive && !failed;
-      if (!__any(alive)) break;
-    } else if (failed) {  // get_current_full_state: row cur, zero rates
-      const int cur = k + 1 < L - H ? k + 1 : L - H;
-#pragma unroll
-      for (int i = 0; i < 9; ++i) s[i] = tr[((size_t)cur * 9 + i) * B];
-#pragma unroll
-      for (int i = 9; i < 12; ++i) s[i] = 0.f;
-    }
-    if (k + 2 <= L - H) {  // get_ref_traj advanced: slide, fetch row k+1+H
-#pragma unroll
-      for (int r = 0; r + 1 < H; ++r)
-#pragma unroll
-        for (int i = 0; i < 6; ++i) win[r][i] = win[r + 1][i];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        win[H - 1][i] = tr[((size_t)(k + 1 + H) * 9 + i) * B];
-        win[H - 1][3 + i] = tr[((size_t)(k + 1 + H) * 9 + 6 + i) * B];
-      }
-    }
-  }
-  A.steps[b] = steps;
+  MpcFlightLog log = A.log;
+  log.B = B, log.b = (size_t)b;
+  A.steps[b] = mpc_flight(
+      [&](int r, int col) { return tr[((size_t)r * 9 + col) * B]; },
+      [&](float (&s)[12], const float (&u0)[4]) {
+        const Trig t = make_trig(&s[3]);
+        if (LEARNT) learnt_quad_step_lane(s, u0, A.cp, t, lr);
+        else quad_step(s, u0, A.cp, t);
+      },
+      A.cm, A.w, A.o, A.rule, log);
 }
 
 int check_mpc(const ApgQuadParams *model, const ApgQuadLossWeights *weights,
@@ -255,47 +178,34 @@ int apg_quad_mpc_solve(const float *state0, const float *ref, int ref_cols, floa
 
 int apg_quad_mpc_workspace_floats(void) { return kLearntFloats; }
 
-int apg_quad_mpc_closed_loop(const float *traj, int L, float dt,
-                             const ApgQuadParams *plant,
-                             const ApgLearntResidual *plant_learnt,
-                             const ApgQuadParams *model,
-                             const ApgQuadLossWeights *weights,
-                             const ApgQuadMpcOptions *opt, int B, int H,
-                             int max_steps, float thresh_div, float thresh_stable,
-                             int test_time, float *div, int *steps, float *drone,
-                             float *actions, float *start_states, float *cost,
-                             float *workspace, apg_stream_t stream) {
-  constexpr int kH = 10;
+int apg_quad_mpc_closed_loop(const ApgQuadFlight *flight, float dt, const ApgQuadParams *plant,
+                             const ApgLearntResidual *plant_learnt, const ApgQuadParams *model,
+                             const ApgQuadLossWeights *weights, const ApgQuadMpcOptions *opt,
+                             int B, int H, float *cost, float *workspace, apg_stream_t stream) {
   if (int e = check_mpc(model, weights, opt, B)) return e;
   if (!plant) {
     set_error("plant is NULL");
     return APG_ERR_ARG;
   }
-  if (H != kH) {
-    set_error("H must be %d (got %d)", kH, H);
-    return APG_ERR_ARG;
-  }
-  if (plant_learnt && (!plant_learnt->linear_at || !plant_learnt->w1 || !plant_learnt->b1 ||
-                       !plant_learnt->w2 || !plant_learnt->b2)) {
-    set_error("learnt simulator: weight pointer is NULL");
-    return APG_ERR_ARG;
-  }
-  if (L <= kH || max_steps < 1) {
-    set_error("closed loop needs L > %d reference rows and max_steps >= 1", kH);
-    return APG_ERR_ARG;
-  }
-  if (B == 0) return APG_OK;
-  if (!traj || !div || !steps || (plant_learnt && !workspace)) {
-    set_error("NULL buffer");
+  if (H != kFlightH) {
+    set_error("H must be %d (got %d)", kFlightH, H);
     return APG_ERR_ARG;
   }
   MpcLoopArgs A;
-  A.traj = traj, A.div = div, A.steps = steps, A.drone = drone, A.actions = actions;
-  A.start = start_states, A.cost = cost, A.learnt = plant_learnt ? workspace : nullptr;
+  if (const char *e = quad_flight_check(flight, plant_learnt, B, &A.rule)) {
+    set_error("%s", e);
+    return APG_ERR_ARG;
+  }
+  if (B == 0) return APG_OK;
+  if (plant_learnt && !workspace) {
+    set_error("NULL buffer");
+    return APG_ERR_ARG;
+  }
+  A.traj = flight->traj, A.steps = flight->steps;
+  A.log = {flight->div, flight->drone, flight->actions, flight->start_states, cost, 0, 0};
+  A.learnt = plant_learnt ? workspace : nullptr;
   A.cp = make_const(*plant, dt), A.cm = make_const(*model, dt);
-  A.w = *weights, A.o = *opt;
-  A.B = B, A.L = L, A.T = max_steps < L + 1 ? max_steps : L + 1, A.test_time = test_time;
-  A.thresh_div = thresh_div, A.thresh_stable = thresh_stable;
+  A.w = *weights, A.o = *opt, A.B = B;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((B + kMpcThreads - 1) / kMpcThreads);
   if (plant_learnt) {

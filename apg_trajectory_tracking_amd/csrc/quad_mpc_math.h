@@ -20,6 +20,7 @@
 // m = 0 at the start of every solve.  After the last update one more forward
 // sweep gives the cost that belongs to the returned u.
 #pragma once
+#include "quad_flight_rule.h"
 #include "quad_math.h"
 
 namespace apg {
@@ -158,6 +159,77 @@ __host__ __device__ __forceinline__ void mpc_shift(float (&u)[H][4]) {
   for (int k = 0; k + 1 < H; ++k)
 #pragma unroll
     for (int j = 0; j < 4; ++j) u[k][j] = u[k + 1][j];
+}
+
+// The log of one flight of a [..][B] batch: a NULL output drops its writes
+struct MpcFlightLog {
+  float *div, *drone, *actions, *start, *cost;   // ApgQuadFlight's, cost [T][B]
+  size_t B, b;
+  template <int N>
+  __host__ __device__ __forceinline__ void put(float *out, int row, const float (&v)[N]) const {
+    if (!out) return;
+#pragma unroll
+    for (int i = 0; i < N; ++i) out[((size_t)row * N + i) * B + b] = v[i];
+  }
+};
+
+// One closed-loop flight (quad_flight_rule.h) with the controller "shift the warm
+// start, solve on the model `cm`, apply u[0]" (first step: from u = 0.5; the
+// warm start is kept through a reset).  row(r, col): the flight's reference;
+// plant(s, u0): the environment's step.  Returns the iterations executed.
+template <class Row, class Plant>
+__host__ __device__ __forceinline__ int mpc_flight(Row &&row, Plant &&plant, const QuadConst &cm,
+                                                   const ApgQuadLossWeights &w,
+                                                   const ApgQuadMpcOptions &o,
+                                                   const QuadFlightRule &rule,
+                                                   const MpcFlightLog &log) {
+  constexpr int H = kFlightH;
+  float s[12], win[H][6], u[H][4];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) s[i] = i < 3 ? row(0, i) : 0.f;  // zero_reset
+  const auto window_row = [&](int r, float (&x)[6]) {   // (position, velocity)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) x[i] = row(r, i), x[3 + i] = row(r, 6 + i);
+  };
+#pragma unroll
+  for (int r = 0; r < H; ++r) window_row(1 + r, win[r]);
+#pragma unroll
+  for (int k = 0; k < H; ++k)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) u[k][j] = 0.5f;
+  log.put(log.drone, 0, s);
+  int steps = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+  for (int k = 0; k < rule.T; ++k) {
+    log.put(log.start, k, s);
+    if (k > 0) mpc_shift<H>(u);
+    const float J[1] = {mpc_solve<H>(s, win, u, cm, w, o, [](int, float) {})};
+    log.put(log.cost, k, J);
+    log.put(log.actions, k, u[0]);
+    plant(s, u[0]);
+    // window row 0 is reference[cur] after get_ref_traj: project_on_ref
+    const float ref[3] = {win[0][0], win[0][1], win[0][2]};
+    const float dv[1] = {flight_divergence(ref, s)};
+    log.put(log.drone, k + 1, s);
+    log.put(log.div, k, dv);
+    steps = k + 1;
+    if (rule.failed(s, dv[0])) {
+      if (rule.test_time) break;
+      const int cur = rule.reset_row(k);   // get_current_full_state: zero rates
+#pragma unroll
+      for (int i = 0; i < 12; ++i) s[i] = i < 9 ? row(cur, i) : 0.f;
+    }
+    if (rule.window_advances(k)) {
+#pragma unroll
+      for (int r = 0; r + 1 < H; ++r)
+#pragma unroll
+        for (int i = 0; i < 6; ++i) win[r][i] = win[r + 1][i];
+      window_row(k + 1 + H, win[H - 1]);
+    }
+  }
+  return steps;
 }
 
 // argument rules shared by the device entry points and the twins; NULL: fine

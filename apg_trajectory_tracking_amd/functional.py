@@ -1734,7 +1734,7 @@ def quad_mlp_rollout_loss(net, state0, in_ref, ref, dt, params, weights=None):
 
 
 # ------------------------------------------ batched closed-loop evaluation (N2)
-def _closed_loop_env(learnt):
+def _learnt_env(learnt):
     """(struct or None, params override) for the closed-loop kernels: `learnt`
     is a LearntDynamics module (the simulator train_dynamics() fits and
     evaluate_model then flies, scripts/train_drone.py:44-45) or None."""
@@ -1742,6 +1742,35 @@ def _closed_loop_env(learnt):
         return None, None
     model = _learnt_model(learnt)
     return ctypes.byref(model), model
+
+
+def _mlp_policy(net):
+    """(ApgMlpPolicy, the contiguous fp32 tensors of `_MLP_PARAMS` it points to)."""
+    pw = [_f32c(v).contiguous() for v in _net_params(net, _MLP_PARAMS)]
+    return _capi.ApgMlpPolicy(*map(ptr, pw)), pw
+
+
+class _QuadFlight:
+    """What the three quadrotor closed-loop wrappers share: the [L][9][B]
+    reference `tr`, T, the zero-initialised outputs, the ApgQuadFlight naming
+    them (`ref`: by reference) and the result dict `out`."""
+
+    def __init__(self, traj, max_steps, thresh_div, thresh_stable, test_time,
+                 want_trajectory):
+        self.B, L, _ = traj.shape
+        B, dev = self.B, traj.device
+        self.tr = _f32c(traj).permute(1, 2, 0).contiguous()
+        self.T = T = min(int(max_steps), L + 1)
+        self.new = new = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+        self.out = dict(div=new(T, B), steps=torch.zeros(B, dtype=torch.int32, device=dev))
+        if want_trajectory:
+            self.out.update(drone=new(T + 1, 12, B), actions=new(T, 4, B),
+                            start_states=new(T, 12, B))
+        self.flight = _capi.ApgQuadFlight(
+            ptr(self.tr), L, int(max_steps), float(thresh_div), float(thresh_stable),
+            int(test_time), *[ptr(self.out.get(k)) for k in (
+                "div", "steps", "drone", "actions", "start_states")])
+        self.ref = ctypes.byref(self.flight)
 
 
 def quad_mlp_closed_loop(net, traj, dt, params, max_steps=251, thresh_div=1.0,
@@ -1759,41 +1788,19 @@ def quad_mlp_closed_loop(net, traj, dt, params, max_steps=251, thresh_div=1.0,
     transform, analytic step on `params`, residual network) instead of
     FlightmareDynamics."""
     _guard_policy_inputs("closed-loop evaluation", traj=traj)
-    B, L, _ = traj.shape
-    H = 10
-    dev = traj.device
-    tr = _f32c(traj).permute(1, 2, 0).contiguous()
-    names = ("w_s", "b_s", "conv_w", "conv_b", "w_1", "b_1", "w_2", "b_2",
-             "w_3", "b_3", "w_out", "b_out")
-    vals = (net.states_in.weight, net.states_in.bias, net.conv_ref.weight,
-            net.conv_ref.bias, net.fc1.weight, net.fc1.bias, net.fc2.weight,
-            net.fc2.bias, net.fc3.weight, net.fc3.bias, net.fc_out.weight,
-            net.fc_out.bias)
-    pw = {k: _f32c(v.detach()).contiguous() for k, v in zip(names, vals)}
-    if (pw["w_s"].shape != (64, 15) or pw["conv_w"].shape != (20, 9, 3)
-            or pw["w_1"].shape != (64, 224) or pw["w_out"].shape[1] != 64
-            or pw["w_out"].shape[0] < 4):
+    pol, pw = _mlp_policy(net)
+    if (pw[0].shape != (64, 15) or pw[2].shape != (20, 9, 3)
+            or pw[4].shape != (64, 224) or pw[10].shape[1] != 64
+            or pw[10].shape[0] < 4):
         raise ValueError("closed loop needs Net(15, 10, 9, 4*k, conv=1)")
-    require_device(tr, *pw.values())
-    pol = _capi.ApgMlpPolicy(**{k: ptr(v) for k, v in pw.items()})
-    T = min(int(max_steps), L + 1)
-    new = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
-    div = new(T, B)
-    steps = torch.zeros(B, dtype=torch.int32, device=dev)
-    drone = new(T + 1, 12, B) if want_trajectory else None
-    actions = new(T, 4, B) if want_trajectory else None
-    start = new(T, 12, B) if want_trajectory else None
-    ws = new(lib().apg_quad_mlp_workspace_floats())
-    env, _keep = _closed_loop_env(learnt)
-    check(lib().apg_quad_mlp_closed_loop_env(
-        ptr(tr), L, float(dt), ctypes.byref(params), env, ctypes.byref(pol), B, H,
-        int(max_steps), float(thresh_div), float(thresh_stable), int(test_time),
-        ptr(div), steps.data_ptr(), ptr(drone), ptr(actions), ptr(start),
-        ptr(ws), stream_of(tr)), "apg_quad_mlp_closed_loop_env")
-    out = dict(div=div, steps=steps)
-    if want_trajectory:
-        out.update(drone=drone, actions=actions, start_states=start)
-    return out
+    fl = _QuadFlight(traj, max_steps, thresh_div, thresh_stable, test_time, want_trajectory)
+    require_device(fl.tr, *pw)
+    ws = fl.new(lib().apg_quad_mlp_workspace_floats())
+    env, _keep = _learnt_env(learnt)
+    check(lib().apg_quad_mlp_closed_loop(
+        fl.ref, float(dt), ctypes.byref(params), env, ctypes.byref(pol), fl.B, 10,
+        ptr(ws), stream_of(fl.tr)), "apg_quad_mlp_closed_loop")
+    return fl.out
 
 
 # --------------------------------------------------- batched shooting MPC
@@ -1856,33 +1863,19 @@ def quad_mpc_closed_loop(traj, dt, params, model_params=None, learnt=None, weigh
     plans with (None: `params` - the nominal case; other parameters: the
     model-mismatch experiment).  Returns the dict quad_mlp_closed_loop returns,
     plus cost [T,B]: the solver's cost at every control step."""
-    B, L, _ = traj.shape
-    H = 10
-    dev = traj.device
-    tr = _f32c(traj).permute(1, 2, 0).contiguous()
-    require_device(tr)
-    T = min(int(max_steps), L + 1)
-    new = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
-    div, cost = new(T, B), new(T, B)
-    steps = torch.zeros(B, dtype=torch.int32, device=dev)
-    drone = new(T + 1, 12, B) if want_trajectory else None
-    actions = new(T, 4, B) if want_trajectory else None
-    start = new(T, 12, B) if want_trajectory else None
-    env, _keep = _closed_loop_env(learnt)
-    ws = new(lib().apg_quad_mpc_workspace_floats()) if learnt is not None else None
+    fl = _QuadFlight(traj, max_steps, thresh_div, thresh_stable, test_time, want_trajectory)
+    require_device(fl.tr)
+    cost = fl.new(fl.T, fl.B)
+    env, _keep = _learnt_env(learnt)
+    ws = fl.new(lib().apg_quad_mpc_workspace_floats()) if learnt is not None else None
     opt = quad_mpc_options(iters, beta, alpha_thrust, alpha_rate)
     weights = weights or quad_loss_weights()
     model = params if model_params is None else model_params
     check(lib().apg_quad_mpc_closed_loop(
-        ptr(tr), L, float(dt), ctypes.byref(params), env, ctypes.byref(model),
-        ctypes.byref(weights), ctypes.byref(opt), B, H, int(max_steps),
-        float(thresh_div), float(thresh_stable), int(test_time), ptr(div),
-        steps.data_ptr(), ptr(drone), ptr(actions), ptr(start), ptr(cost), ptr(ws),
-        stream_of(tr)), "apg_quad_mpc_closed_loop")
-    out = dict(div=div, steps=steps, cost=cost)
-    if want_trajectory:
-        out.update(drone=drone, actions=actions, start_states=start)
-    return out
+        fl.ref, float(dt), ctypes.byref(params), env, ctypes.byref(model),
+        ctypes.byref(weights), ctypes.byref(opt), fl.B, 10, ptr(cost), ptr(ws),
+        stream_of(fl.tr)), "apg_quad_mpc_closed_loop")
+    return dict(fl.out, cost=cost)
 
 
 def quad_policy_actions(net, state0, in_ref, dt, params):
@@ -1933,10 +1926,7 @@ def quad_lstm_closed_loop(net, traj, dt, params, h0, c0, max_steps=251,
     h0 / c0 [B, 8]: the hidden / cell state at the start of every run (the
     reference resets it once per evaluator and carries it through the run)."""
     _guard_policy_inputs("closed-loop evaluation", traj=traj)
-    B, L, _ = traj.shape
-    H = 10
-    dev = traj.device
-    tr = _f32c(traj).permute(1, 2, 0).contiguous()
+    B = traj.shape[0]
     h0s, c0s = to_soa(h0), to_soa(c0)
     pw = dict(conv_w=net.conv_ref.weight, conv_b=net.conv_ref.bias,
               w_ih=net.lstm.weight_ih, w_hh=net.lstm.weight_hh,
@@ -1946,27 +1936,16 @@ def quad_lstm_closed_loop(net, traj, dt, params, h0, c0, max_steps=251,
     if pw["w_ih"].shape != (32, 175) or pw["conv_w"].shape != (20, 9, 3) \
             or pw["w_out"].shape != (4, 8) or h0s.shape != (8, B):
         raise ValueError("closed loop needs LSTM_NEW(15, 10, 9, 4, conv=1), h0/c0 [B,8]")
-    require_device(tr, h0s, c0s, *pw.values())
+    fl = _QuadFlight(traj, max_steps, thresh_div, thresh_stable, test_time, want_trajectory)
+    require_device(fl.tr, h0s, c0s, *pw.values())
     pol = _capi.ApgLstmPolicy(**{k: ptr(v) for k, v in pw.items()})
-    T = min(int(max_steps), L + 1)
-    new = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
-    div = new(T, B)
-    steps = torch.zeros(B, dtype=torch.int32, device=dev)
-    drone = new(T + 1, 12, B) if want_trajectory else None
-    actions = new(T, 4, B) if want_trajectory else None
-    start = new(T, 12, B) if want_trajectory else None
-    ws = new(lib().apg_quad_lstm_workspace_floats())
-    env, _keep = _closed_loop_env(learnt)
-    check(lib().apg_quad_lstm_closed_loop_env(
-        ptr(tr), L, ptr(h0s), ptr(c0s), float(dt), ctypes.byref(params), env,
-        ctypes.byref(pol), B, H, int(max_steps), float(thresh_div),
-        float(thresh_stable), int(test_time), ptr(div), steps.data_ptr(),
-        ptr(drone), ptr(actions), ptr(start), ptr(ws), stream_of(tr)),
-        "apg_quad_lstm_closed_loop_env")
-    out = dict(div=div, steps=steps)
-    if want_trajectory:
-        out.update(drone=drone, actions=actions, start_states=start)
-    return out
+    ws = fl.new(lib().apg_quad_lstm_workspace_floats())
+    env, _keep = _learnt_env(learnt)
+    check(lib().apg_quad_lstm_closed_loop(
+        fl.ref, ptr(h0s), ptr(c0s), float(dt), ctypes.byref(params), env,
+        ctypes.byref(pol), B, 10, ptr(ws), stream_of(fl.tr)),
+        "apg_quad_lstm_closed_loop")
+    return fl.out
 
 
 def wing_mlp_closed_loop(net, targets, dt, params, mean, std, data_dt=0.05,
@@ -2033,14 +2012,14 @@ def wing_mlp_closed_loop(net, targets, dt, params, mean, std, data_dt=0.05,
         if tuple(res[0].shape) != (64, 16) or tuple(res[2].shape) != (12, 64):
             raise ValueError("closed loop expects the 16 -> 64 -> 12 residual network")
         model = _capi.ApgLearntResidual(None, *[t.data_ptr() for t in res])
-    check(lib().apg_wing_mlp_closed_loop_env(
+    check(lib().apg_wing_mlp_closed_loop(
         ptr(tg), n_targets, ptr(s0), float(dt), ctypes.byref(params), I9,
         None if model is None else ctypes.byref(model),
         ctypes.byref(pol), mean, std, float(data_dt), int(data_horizon), B, T,
         float(thresh_div), float(thresh_stable), int(test_time),
         ptr(div_linear), ptr(div_pass), ptr(div_fail), steps.data_ptr(),
         ptr(drone), ptr(seen), ptr(ws), stream_of(tg)),
-        "apg_wing_mlp_closed_loop_env")
+        "apg_wing_mlp_closed_loop")
     out = dict(div_linear=div_linear, div_pass=div_pass, div_fail=div_fail,
                steps=steps)
     if want_trajectory:

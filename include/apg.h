@@ -626,63 +626,52 @@ int apg_quad_mlp_rollout_train_step(
  * QuadEvaluator.follow_trajectory("rand") (scripts/evaluate_drone.py:81-194)
  * for B reference trajectories in one launch - per step the H-row reference
  * window (Random.get_ref_traj, neural_control/trajectory/random_traj.py:60-79),
- * QuadDataset.prepare_data (dataset.py:155-204), the policy (first 4 outputs of
- * `policy->w_out`, so a concurrent-mode Net works unchanged), sigmoid, clip,
- * FlightmareDynamics, the divergence from the projected reference and the
- * attitude check (drone_env.py:59-72); on failure either stop (test_time) or
- * reset to the reference state.  traj [L][9][B] = (position, euler, velocity)
- * rows, L > H.  T = min(max_steps, L + 1) iterations.
+ * the controller, the environment's step, the divergence from the projected
+ * reference and the attitude check (drone_env.py:59-72); on failure either stop
+ * (test_time) or reset to the reference state.  The rule is stated once, in
+ * csrc/quad_flight_rule.h; every quadrotor controller below flies it.
+ * ApgQuadFlight = the reference, the rule's numbers and the log:
+ * traj [L][9][B] = (position, euler, velocity) rows, L > H.
+ * T = min(max_steps, L + 1) iterations.
  * Outputs: div [T][B] (rows >= steps[b] are not written), steps [B];
  * optional (NULL to skip) drone [T+1][12][B] (state after each step, row 0 =
- * start), actions [T][4][B], start_states [T][12][B] (state the policy saw,
- * i.e. after a reset).  workspace: apg_quad_mlp_workspace_floats(). */
-int apg_quad_mlp_closed_loop(const float *traj, int L, float dt,
-                             const ApgQuadParams *params,
-                             const ApgMlpPolicy *policy, int B, int H,
-                             int max_steps, float thresh_div,
-                             float thresh_stable, int test_time, float *div,
-                             int *steps, float *drone, float *actions,
-                             float *start_states, float *workspace,
-                             apg_stream_t stream);
-/* ... with the environment a caller chooses: `learnt` NULL = FlightmareDynamics
- * (the function above), else the LEARNT simulator of train_dynamics()
+ * start), actions [T][4][B], start_states [T][12][B] (state the controller saw,
+ * i.e. after a reset). */
+typedef struct ApgQuadFlight {
+  const float *traj;
+  int L, max_steps;
+  float thresh_div, thresh_stable;
+  int test_time;
+  float *div;
+  int *steps;
+  float *drone, *actions, *start_states;
+} ApgQuadFlight;
+
+/* The MLP controller: per step QuadDataset.prepare_data (dataset.py:155-204),
+ * the policy (first 4 outputs of `policy->w_out`, so a concurrent-mode Net works
+ * unchanged), sigmoid, clip.  The environment: `learnt` NULL =
+ * FlightmareDynamics on `params`, else the LEARNT simulator of train_dynamics()
  * (LearntDynamics, neural_control/dynamics/quad_dynamics_trained.py:10-69:
  * action transform, the analytic step on `params`, the relu residual) - what
  * QuadEvaluator flies after scripts/train_drone.py:44-45 swapped
- * eval_env.dynamics for the train dynamics. */
-int apg_quad_mlp_closed_loop_env(const float *traj, int L, float dt,
-                                 const ApgQuadParams *params,
-                                 const ApgLearntResidual *learnt,
-                                 const ApgMlpPolicy *policy, int B, int H,
-                                 int max_steps, float thresh_div,
-                                 float thresh_stable, int test_time, float *div,
-                                 int *steps, float *drone, float *actions,
-                                 float *start_states, float *workspace,
-                                 apg_stream_t stream);
+ * eval_env.dynamics for the train dynamics.
+ * workspace: apg_quad_mlp_workspace_floats(). */
+int apg_quad_mlp_closed_loop(const ApgQuadFlight *flight, float dt,
+                             const ApgQuadParams *params,
+                             const ApgLearntResidual *learnt,
+                             const ApgMlpPolicy *policy, int B, int H,
+                             float *workspace, apg_stream_t stream);
 
 /* The same closed loop for the LSTM controller (LSTM_NEW): hidden / cell
  * state h0 / c0 [8][B] carried through all steps (QuadEvaluator resets it once,
  * scripts/evaluate_drone.py:56-58).  workspace:
  * apg_quad_lstm_workspace_floats(). */
-int apg_quad_lstm_closed_loop(const float *traj, int L, const float *h0,
+int apg_quad_lstm_closed_loop(const ApgQuadFlight *flight, const float *h0,
                               const float *c0, float dt,
                               const ApgQuadParams *params,
+                              const ApgLearntResidual *learnt,
                               const ApgLstmPolicy *policy, int B, int H,
-                              int max_steps, float thresh_div,
-                              float thresh_stable, int test_time, float *div,
-                              int *steps, float *drone, float *actions,
-                              float *start_states, float *workspace,
-                              apg_stream_t stream);
-int apg_quad_lstm_closed_loop_env(const float *traj, int L, const float *h0,
-                                  const float *c0, float dt,
-                                  const ApgQuadParams *params,
-                                  const ApgLearntResidual *learnt,
-                                  const ApgLstmPolicy *policy, int B, int H,
-                                  int max_steps, float thresh_div,
-                                  float thresh_stable, int test_time, float *div,
-                                  int *steps, float *drone, float *actions,
-                                  float *start_states, float *workspace,
-                                  apg_stream_t stream);
+                              float *workspace, apg_stream_t stream);
 
 /* Batched shooting MPC - the role of the comparator the reference judges its
  * controllers against (neural_control/controllers/mpc.py: CasADi + IPOPT on a
@@ -713,27 +702,23 @@ int apg_quad_mpc_solve(const float *state0, const float *ref, int ref_cols, floa
                        const ApgQuadMpcOptions *opt, int B, int H, float *u,
                        float *cost_out, float *cost_trace, apg_stream_t stream);
 
-/* apg_quad_mlp_closed_loop_env with the policy replaced by "shift the warm
- * start, solve, apply u[0]" (first step: from u = 0.5): same window rule, the
- * solver sees the ABSOLUTE window rows (position, velocity), same divergence,
- * attitude check, test_time break or reset to the reference state (the warm
- * start is kept through a reset, as the reference keeps nlp_w0), same outputs
- * and shapes, plus cost [T][B] or NULL (cost_out of every solve).  `plant`
+/* apg_quad_mlp_closed_loop with the policy replaced by "shift the warm
+ * start, solve, apply u[0]" (first step: from u = 0.5): same flight, the
+ * solver sees the ABSOLUTE window rows (position, velocity); the warm start is
+ * kept through a reset, as the reference keeps nlp_w0.  Same outputs and
+ * shapes, plus cost [T][B] or NULL (cost_out of every solve).  `plant`
  * steps the flight (with `plant_learnt` != NULL through the learnt simulator),
  * `model` is what the solver plans with: the same pointer for the nominal
  * case, other parameters for the model-mismatch experiment.  H = 10.
  * workspace: apg_quad_mpc_workspace_floats() floats (read only when
  * plant_learnt is given; may be NULL otherwise). */
-int apg_quad_mpc_closed_loop(const float *traj, int L, float dt,
+int apg_quad_mpc_closed_loop(const ApgQuadFlight *flight, float dt,
                              const ApgQuadParams *plant,
                              const ApgLearntResidual *plant_learnt,
                              const ApgQuadParams *model,
                              const ApgQuadLossWeights *weights,
                              const ApgQuadMpcOptions *opt, int B, int H,
-                             int max_steps, float thresh_div, float thresh_stable,
-                             int test_time, float *div, int *steps, float *drone,
-                             float *actions, float *start_states, float *cost,
-                             float *workspace, apg_stream_t stream);
+                             float *cost, float *workspace, apg_stream_t stream);
 int apg_quad_mpc_workspace_floats(void);
 
 /* "Planes x planes" reduction GEMM on the matrix cores (fp32 accuracy):
@@ -877,10 +862,19 @@ int apg_wing_policy_bwd(const float *actions, const float *grad_actions,
  * = len(drone_traj); optional drone [T][16][B] (state after the step, action)
  * and seen [T][15][B] (state the policy saw - after a reset still the last
  * simulated one, as in the reference - and its target).
- * workspace: apg_wing_policy_workspace_floats(). */
+ * workspace: apg_wing_policy_workspace_floats().
+ * The environment: inertia and learnt both NULL = SimpleWingEnv on `params`;
+ * else a LEARNT one (LearntFixedWingDynamics.forward,
+ * neural_control/dynamics/fixed_wing_dynamics.py:270-326 - what
+ * SimpleWingEnv(train_dynamics) steps with after train_dynamics(),
+ * scripts/train_fixed_wing.py:42-43): `params` = the CURRENT values of the
+ * module's parameters, `inertia` = its 3x3 parameter `I` (HOST array of 9,
+ * row-major, used in full, as apg_wing_learnt_step_fwd), `learnt` = the residual
+ * network on [state, action] (linear_at is not read). */
 int apg_wing_mlp_closed_loop(const float *targets, int n_targets,
                              const float *state0, float dt,
-                             const ApgWingParams *params,
+                             const ApgWingParams *params, const float *inertia,
+                             const ApgLearntResidual *learnt,
                              const ApgWingPolicy *policy, const float *mean,
                              const float *std, float data_dt, int data_horizon,
                              int B, int max_steps, float thresh_div,
@@ -888,25 +882,6 @@ int apg_wing_mlp_closed_loop(const float *targets, int n_targets,
                              float *div_linear, float *div_pass, float *div_fail,
                              int *steps, float *drone, float *seen,
                              float *workspace, apg_stream_t stream);
-/* ... with a LEARNT environment (LearntFixedWingDynamics.forward,
- * neural_control/dynamics/fixed_wing_dynamics.py:270-326 - what
- * SimpleWingEnv(train_dynamics) steps with after train_dynamics(),
- * scripts/train_fixed_wing.py:42-43): `params` = the CURRENT values of the
- * module's parameters, `inertia` = its 3x3 parameter `I` (HOST array of 9,
- * row-major, used in full, as apg_wing_learnt_step_fwd), `learnt` = the residual
- * network on [state, action] (linear_at is not read).  inertia and learnt both
- * NULL: the function above. */
-int apg_wing_mlp_closed_loop_env(const float *targets, int n_targets,
-                                 const float *state0, float dt,
-                                 const ApgWingParams *params, const float *inertia,
-                                 const ApgLearntResidual *learnt,
-                                 const ApgWingPolicy *policy, const float *mean,
-                                 const float *std, float data_dt, int data_horizon,
-                                 int B, int max_steps, float thresh_div,
-                                 float thresh_stable, int test_time,
-                                 float *div_linear, float *div_pass, float *div_fail,
-                                 int *steps, float *drone, float *seen,
-                                 float *workspace, apg_stream_t stream);
 
 /* Weights of fixed_wing_mpc_loss, neural_control/drone_loss.py:72-82
  * (reference values: pos 10, action 0.1). */

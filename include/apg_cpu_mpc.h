@@ -20,16 +20,13 @@ int apg_quad_mpc_solve_cpu(const float *state0, const float *ref, int ref_cols, 
                            const ApgQuadParams *model, const ApgQuadLossWeights *weights,
                            const ApgQuadMpcOptions *opt, int B, int H, float *u,
                            float *cost_out, float *cost_trace);
-int apg_quad_mpc_closed_loop_cpu(const float *traj, int L, float dt,
+int apg_quad_mpc_closed_loop_cpu(const ApgQuadFlight *flight, float dt,
                                  const ApgQuadParams *plant,
                                  const ApgLearntResidual *plant_learnt,
                                  const ApgQuadParams *model,
                                  const ApgQuadLossWeights *weights,
                                  const ApgQuadMpcOptions *opt, int B, int H,
-                                 int max_steps, float thresh_div, float thresh_stable,
-                                 int test_time, float *div, int *steps, float *drone,
-                                 float *actions, float *start_states, float *cost,
-                                 float *workspace);
+                                 float *cost, float *workspace);
 
 #ifdef __cplusplus
 }

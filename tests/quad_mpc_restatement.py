@@ -205,9 +205,10 @@ def twins():
         ctypes.POINTER(_capi.ApgQuadLossWeights), ctypes.POINTER(_capi.ApgQuadMpcOptions),
         I, I, P, P, P]
     lib.apg_quad_mpc_closed_loop_cpu.argtypes = [
-        P, I, F, ctypes.POINTER(_capi.ApgQuadParams), ctypes.POINTER(_capi.ApgLearntResidual),
-        ctypes.POINTER(_capi.ApgQuadParams), ctypes.POINTER(_capi.ApgQuadLossWeights),
-        ctypes.POINTER(_capi.ApgQuadMpcOptions), I, I, I, F, F, I, P, P, P, P, P, P, P]
+        ctypes.POINTER(_capi.ApgQuadFlight), F, ctypes.POINTER(_capi.ApgQuadParams),
+        ctypes.POINTER(_capi.ApgLearntResidual), ctypes.POINTER(_capi.ApgQuadParams),
+        ctypes.POINTER(_capi.ApgQuadLossWeights), ctypes.POINTER(_capi.ApgQuadMpcOptions),
+        I, I, P, P]
     lib.apg_cpu_last_error_string.restype = ctypes.c_char_p
     return lib
 
@@ -244,19 +245,20 @@ def twin_solve(tw, state0, ref, u0, dt, iters, modified_params=None):
 def twin_closed_loop(tw, traj, dt, iters, max_steps, thresh_div, thresh_stable, test_time,
                      plant_params=None, model_params=None):
     """apg_quad_mpc_closed_loop_cpu -> the dict `closed_loop` returns ([B, ...])."""
-    from apg_trajectory_tracking_amd import functional as F
+    from apg_trajectory_tracking_amd import _capi, functional as F
     B, L, _ = traj.shape
     T = min(max_steps, L + 1)
     tr = traj.float().permute(1, 2, 0).contiguous()
     div, cost_ = torch.zeros(T, B), torch.zeros(T, B)
     steps = torch.zeros(B, dtype=torch.int32)
     drone, actions, start = torch.zeros(T + 1, 12, B), torch.zeros(T, 4, B), torch.zeros(T, 12, B)
+    flight = _capi.ApgQuadFlight(
+        tr.data_ptr(), L, max_steps, thresh_div, thresh_stable, test_time, div.data_ptr(),
+        steps.data_ptr(), drone.data_ptr(), actions.data_ptr(), start.data_ptr())
     rc = tw.apg_quad_mpc_closed_loop_cpu(
-        tr.data_ptr(), L, dt, ctypes.byref(_params(plant_params)), None,
+        ctypes.byref(flight), dt, ctypes.byref(_params(plant_params)), None,
         ctypes.byref(_params(model_params)), ctypes.byref(F.quad_loss_weights()),
-        ctypes.byref(_options(iters)), B, H, max_steps, thresh_div, thresh_stable,
-        test_time, div.data_ptr(), steps.data_ptr(), drone.data_ptr(), actions.data_ptr(),
-        start.data_ptr(), cost_.data_ptr(), None)
+        ctypes.byref(_options(iters)), B, H, cost_.data_ptr(), None)
     assert rc == 0, tw.apg_cpu_last_error_string()
     return dict(div=div.t(), cost=cost_.t(), steps=steps.long(), drone=drone.permute(2, 0, 1),
                 actions=actions.permute(2, 0, 1), start=start.permute(2, 0, 1))

@@ -1170,9 +1170,12 @@ def test_kernels_written_for_two_waves_per_simd_get_them():
             "25mlp_rollout_bwd_tm_kernelE": 2, "25mlp_concurrent_fwd_kernelILb0E": 2,
             "25mlp_concurrent_fwd_kernelILb1E": 2, "28mlp_concurrent_bwd_tm_kernelILb0E": 2,
             "28mlp_concurrent_bwd_tm_kernelILb1E": 2, "22wing_policy_fwd_kernelE": 4,
-            "22wing_policy_bwd_kernelE": 4}
+            "22wing_policy_bwd_kernelE": 4,
+            "22mlp_closed_loop_kernelILb0E": 2, "22mlp_closed_loop_kernelILb1E": 2,
+            "23lstm_closed_loop_kernelILb0E": 2, "23lstm_closed_loop_kernelILb1E": 2}
     no_scratch = ("lstm_rollout_fwd_kernel", "lstm_rollout_bwd_kernel", "lstm_gate_wgrad_kernel",
-                  "quad_rollout_rows_kernel", "wing_rollout_pk_kernel")
+                  "quad_rollout_rows_kernel", "wing_rollout_pk_kernel",
+                  "mlp_closed_loop_kernel", "lstm_closed_loop_kernel")
     assert len(res) > 100
     for frag, occ in want.items():
         hits = [v for k, v in res.items() if frag in k]
