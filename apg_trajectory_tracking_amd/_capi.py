@@ -179,6 +179,12 @@ class ApgCartpoleLearnt(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in CARTPOLE_LEARNT_FIELDS + ("w1", "b1", "w2")]
 
 
+class ApgCartpoleMpcOptions(ctypes.Structure):
+    """include/apg.h: the cart-pole shooting MPC's iteration count and step rule."""
+    _fields_ = [("iters", ctypes.c_int), ("beta", ctypes.c_float),
+                ("alpha", ctypes.c_float)]
+
+
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 _F = ctypes.c_float
@@ -341,6 +347,13 @@ SIGNATURES = {
         ctypes.POINTER(ApgQuadLossWeights), ctypes.POINTER(ApgQuadMpcOptions), _I, _I,
         _P, _P, _P],
     "apg_quad_mpc_workspace_floats": [],
+    "apg_cartpole_mpc_solve": [
+        _P, _P, _F, ctypes.POINTER(ApgCartpoleParams),
+        ctypes.POINTER(ApgCartpoleMpcOptions), _I, _I, _P, _P, _P, _P],
+    "apg_cartpole_mpc_closed_loop": [
+        _P, _F, ctypes.POINTER(ApgCartpoleParams), ctypes.POINTER(ApgCartpoleLearnt),
+        ctypes.POINTER(ApgCartpoleParams), ctypes.POINTER(ApgCartpoleMpcOptions),
+        _I, _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P],
     "apg_reduce_loss_partials": [_P, _I, _P, _P],
     "apg_loss_partials_count": [_I],
     "apg_stream_copy": [_P, _P, ctypes.c_longlong, _P],

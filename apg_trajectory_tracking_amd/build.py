@@ -14,7 +14,7 @@ LIB = os.path.join(CSRC, "libapg_hip.so")
 SOURCES = ["common.hip", "quad.hip", "wing.hip", "cartpole.hip", "lstm.hip",
            "mlp_rollout.hip", "mlp_concurrent.hip", "mlp_wing.hip", "wing_learnt.hip",
            "linear_wgrad.hip", "planes_gemm.hip", "mlp_cartpole.hip",
-           "cartpole_learnt.hip", "quad_mpc.hip"]
+           "cartpole_learnt.hip", "quad_mpc.hip", "cartpole_mpc.hip"]
 # -fno-slp-vectorize: hipcc's SLP pass packs neighbouring f32 ops into
 # v_pk_fma/mul/add_f32; on gfx950 a packed op issues no faster than two plain
 # ones here and needs v_mov shuffles to form register pairs - measured on

@@ -1,5 +1,6 @@
-"""Drop-in for `neural_control.controllers.mpc.MPC` on the quadrotor: the
-comparator the reference judges its learnt controllers against, batched.
+"""Drop-in for `neural_control.controllers.mpc.MPC` on the quadrotor and the
+cart-pole: the comparator the reference judges its learnt controllers against,
+batched.
 
     mpc = MPC(horizon=10, dt=0.1, dynamics="flightmare")
     action = mpc.predict_actions(current_state, ref_states)    # [1, 4]
@@ -23,44 +24,104 @@ Two deliberate differences:
 `QuadEvaluator(MPC(...), environment)` flies whole batches of reference
 trajectories with the solver inside the closed-loop kernel
 (functional.quad_mpc_closed_loop): plant = the evaluator's environment, model =
-this object's parameters."""
+this object's parameters.
+
+The cart-pole (scripts/evaluate_cartpole.py:399-407):
+
+    mpc = MPC(horizon=10, dt=0.05, dynamics="cartpole")
+    action = mpc.predict_actions(current_state)                # [1, 1]
+
+Kept from the reference (_initParamsCartpole, mpc.py:87-100): the action box
+[-1, 1], the start u = 0, the warm start by shifting, `modified_params`, and
+the model of its CasADi twin (CartpoleDynamicsMPC.simulate_cartpole,
+neural_control/dynamics/cartpole_dynamics.py:239-278): the angle is advanced as
+theta + dt theta_dot, without the atan2 wrap of the torch step, inside the
+horizon.  The cost is the TRAINING loss on the training reference
+(cartpole_loss_mpc against make_reference), so that the MPC optimum and a
+policy's loss are the same quantity (functional.cartpole_policy_optimality_gap).
+Two deliberate differences from the reference's NLP follow from that:
+  * the reference's NLP has no action cost (here 0.01 sum u^2);
+  * the reference's NLP uses a `linspace` reference over H + 2 points and drops
+    the last stage's state cost (here: the state fading to zero over H rows,
+    every row with its cost).
+The solver is the same first-order single shooting (apg_cartpole_mpc_solve).
+`evaluate_cartpole.Evaluator(MPC(...), env)` flies whole batches of episodes
+with the solver inside the closed-loop kernel
+(functional.cartpole_mpc_closed_loop)."""
 import numpy as np
 import torch
 
 from .. import functional as F
+from ..dynamics.cartpole_dynamics import CartpoleDynamics
 from ..dynamics.quad_dynamics_flightmare import FlightmareDynamics
 
-DYNAMICS = ("flightmare",)
+DYNAMICS = ("flightmare", "cartpole")
 
 
 class MPC:
 
     def __init__(self, horizon=10, dt=0.1, dynamics="flightmare", modified_params={},
-                 iters=10, beta=None, alpha_thrust=None, alpha_rate=None, device=None,
-                 **kwargs):
+                 iters=10, beta=None, alpha_thrust=None, alpha_rate=None, alpha=None,
+                 device=None, **kwargs):
         if dynamics not in DYNAMICS:
             raise NotImplementedError(
                 f"MPC dynamics {dynamics!r}: implemented here: {', '.join(DYNAMICS)} "
-                "(the quadrotor; no fixed-wing or cart-pole MPC)")
+                "(the quadrotor and the cart-pole; no fixed-wing MPC)")
         if horizon not in (5, 10):
             raise ValueError("the batched MPC is built for horizon 5 or 10")
         self.horizon = horizon
         self.dt = dt
         self.dynamics_model = dynamics
-        self.model = FlightmareDynamics(modified_params=modified_params)
+        if dynamics == "cartpole":
+            self.model = CartpoleDynamics(modified_params)
+            self.options = dict(iters=iters, beta=beta, alpha=alpha)
+        else:
+            self.model = FlightmareDynamics(modified_params=modified_params)
+            self.options = dict(iters=iters, beta=beta, alpha_thrust=alpha_thrust,
+                                alpha_rate=alpha_rate)
         self.params = self.model.params
-        self.options = dict(iters=iters, beta=beta, alpha_thrust=alpha_thrust,
-                            alpha_rate=alpha_rate)
         self.device = device
-        self.warm_start = None      # [B,H,4]: the previous solution, not yet shifted
-        self.last_cost = None
-
-    def reset(self):
-        """Forget the warm start: the next call starts from u = 0.5."""
+        # [B,H,4] ([B,H,1] cart-pole): the previous solution, not yet shifted
         self.warm_start = None
         self.last_cost = None
 
-    def predict_actions(self, current_state, ref_states):
+    def reset(self):
+        """Forget the warm start: the next call starts from u = 0.5 (the
+        cart-pole: u = 0)."""
+        self.warm_start = None
+        self.last_cost = None
+
+    def _shifted_warm_start(self, B):
+        if self.warm_start is None or self.warm_start.shape[0] != B:
+            return None
+        w = self.warm_start
+        return torch.cat((w[:, 1:], w[:, -1:]), 1)
+
+    def _predict_cartpole(self, current_state):
+        """current_state [4] (numpy) -> np.ndarray [1,1], what the reference's
+        Evaluator wraps in torch.tensor([...]); a tensor [B,4] -> tensor [B,1]."""
+        numpy_in = not torch.is_tensor(current_state)
+        dev = torch.device(self.device or
+                           ("cuda" if numpy_in else current_state.device))
+        s = torch.as_tensor(np.asarray(current_state, dtype=np.float32) if numpy_in
+                            else current_state).to(dev, torch.float32)
+        if s.dim() == 1:
+            s = s[None]
+        if s.dim() != 2 or s.shape[1] != 4:
+            raise ValueError(f"state [4] or [B,4] expected, got {tuple(s.shape)}")
+        res = F.cartpole_mpc_solve(s, self.dt, self.params,
+                                   u0=self._shifted_warm_start(s.shape[0]),
+                                   horizon=self.horizon, **self.options)
+        self.warm_start, self.last_cost = res["u"], res["cost"]
+        action = res["u"][:, 0]
+        return action.cpu().numpy() if numpy_in else action
+
+    def predict_actions(self, current_state, ref_states=None):
+        if self.dynamics_model == "cartpole":
+            return self._predict_cartpole(current_state)
+        return self._predict_quad(current_state, ref_states)
+
+    def _predict_quad(self, current_state, ref_states):
         """current_state [12] + ref_states [H,9] (numpy, rows as
         `preprocess_quad` lays them out: columns 0:3 position, 6:9 velocity) ->
         np.ndarray [1,4] like the reference; [B,12] + [B,H,9] tensors -> tensor
@@ -76,11 +137,8 @@ class MPC:
             s, r = s[None], r[None]
         if r.shape[1:] != (self.horizon, 9) or s.shape != (r.shape[0], 12):
             raise ValueError(f"state [B,12] and reference rows [B,{self.horizon},9] expected")
-        u0 = None
-        if self.warm_start is not None and self.warm_start.shape[0] == s.shape[0]:
-            w = self.warm_start
-            u0 = torch.cat((w[:, 1:], w[:, -1:]), 1)
-        res = F.quad_mpc_solve(s, r, self.dt, self.params, u0=u0, **self.options)
+        res = F.quad_mpc_solve(s, r, self.dt, self.params,
+                               u0=self._shifted_warm_start(s.shape[0]), **self.options)
         self.warm_start, self.last_cost = res["u"], res["cost"]
         action = res["u"][:, 0]
         return action.cpu().numpy() if numpy_in else action

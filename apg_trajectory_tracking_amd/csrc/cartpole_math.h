@@ -37,7 +37,12 @@ struct CartAux {  // what the adjoint needs from the forward evaluation
   float s, co, den_x, den_t, xacc, thacc, force;
 };
 
-// state = [x, x_dot, theta, theta_dot], in place.
+// state = [x, x_dot, theta, theta_dot], in place.  WRAP = false: the angle is
+// advanced as theta + dt theta_dot, without the atan2 wrap (what the
+// reference's CasADi twin integrates, cartpole_dynamics.py:239-278; the
+// planning model of cartpole_mpc_math.h).  d atan2(sin a, cos a)/da = 1, so
+// cart_step_adjoint serves both.
+template <bool WRAP = true>
 __host__ __device__ __forceinline__ CartAux cart_step(float (&st)[4], float a,
                                              const CartConst &c) {
   CartAux x;
@@ -50,12 +55,16 @@ __host__ __device__ __forceinline__ CartAux cart_step(float (&st)[4], float a,
             4.f * x.force - 4.f * c.mu * xd) / x.den_x;
   x.thacc = (-c.pml3 * (thd * thd) * x.s * x.co + c.tm_g6 * x.s +
              6.f * (x.force - c.mu * xd) * x.co) / x.den_t;
-  float sd, cd;
-  sincosf(thd * c.dt, &sd, &cd);
-  const float ns = x.s * cd + x.co * sd, nc = x.co * cd - x.s * sd;
+  if (WRAP) {
+    float sd, cd;
+    sincosf(thd * c.dt, &sd, &cd);
+    const float ns = x.s * cd + x.co * sd, nc = x.co * cd - x.s * sd;
+    st[2] = atan2f(ns, nc);
+  } else {
+    st[2] = st[2] + thd * c.dt;
+  }
   st[0] = st[0] + xd * c.dt;
   st[1] = xd + x.xacc * c.dt;
-  st[2] = atan2f(ns, nc);
   st[3] = thd + x.thacc * c.dt;
   return x;
 }

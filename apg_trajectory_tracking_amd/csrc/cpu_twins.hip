@@ -14,6 +14,7 @@
 #include "apg_cpu.h"
 #include "cartpole_learnt_math.h"
 #include "cartpole_math.h"
+#include "cartpole_mpc_math.h"
 #include "quad_math.h"
 #include "quad_mpc_math.h"
 #include "wing_math.h"
@@ -738,6 +739,104 @@ int apg_quad_mpc_closed_loop_cpu(const ApgQuadFlight *flight, float dt,
         cm, *weights, *opt, rule,
         MpcFlightLog{flight->div, flight->drone, flight->actions, flight->start_states, cost,
                      Bs, b});
+  return APG_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------- shooting MPC, cart-pole
+// apg_cpu_mpc.h: the solver and the flight of cartpole_mpc_math.h looped over
+// the batch
+namespace {
+
+template <int H>
+void cart_mpc_solve_batch(const float *state0, const float *u0, const CartConst &c,
+                          const ApgCartpoleMpcOptions &o, int B, float *u, float *cost_out,
+                          float *cost_trace) {
+  const size_t Bs = (size_t)B;
+  for (size_t b = 0; b < Bs; ++b) {
+    float s0[4], ul[H];
+    for (int i = 0; i < 4; ++i) s0[i] = state0[i * Bs + b];
+    for (int k = 0; k < H; ++k) ul[k] = u0 ? u0[k * Bs + b] : 0.f;
+    const float J = cart_mpc_solve<H>(s0, ul, c, o, [&](int i, float Ji) {
+      if (cost_trace) cost_trace[(size_t)i * Bs + b] = Ji;
+    });
+    if (cost_out) cost_out[b] = J;
+    if (u)
+      for (int k = 0; k < H; ++k) u[k * Bs + b] = ul[k];
+  }
+}
+
+template <int H>
+void cart_mpc_loop_batch(const float *state0, const CartConst &cp, const float *rows,
+                         const CartConst &cm, const ApgCartpoleMpcOptions &o,
+                         const CartFlightRule &rule, int B, int *steps, int *upright,
+                         double *vel_sum, double *vel_sq, float *states, float *actions,
+                         float *cost) {
+  const size_t Bs = (size_t)B;
+  for (size_t b = 0; b < Bs; ++b) {
+    float s0[4];
+    for (int i = 0; i < 4; ++i) s0[i] = state0[i * Bs + b];
+    const CartFlightBook f = cart_mpc_flight<H>(
+        s0, [&](float (&s)[4], float a) { cart_learnt_step(s, a, cp, rows); },
+        [](bool alive) { return alive; }, cm, o, rule,
+        CartMpcFlightLog{states, actions, cost, Bs, b}, true);
+    steps[b] = f.steps, upright[b] = f.upright ? 1 : 0;
+    vel_sum[b] = f.vel_sum, vel_sq[b] = f.vel_sq;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int apg_cartpole_mpc_solve_cpu(const float *state0, const float *u0, float dt,
+                               const ApgCartpoleParams *model,
+                               const ApgCartpoleMpcOptions *opt, int B, int H, float *u,
+                               float *cost_out, float *cost_trace) {
+  if (B < 0) return fail("B must be >= 0 (got %d)", B);
+  if (const char *e = cart_mpc_check(model, opt, H)) return fail("%s", e);
+  if (B == 0) return APG_OK;
+  if (!state0) return fail("state0 is NULL");
+  const CartConst c = make_const(*model, dt);
+  if (H == 5)
+    cart_mpc_solve_batch<5>(state0, u0, c, *opt, B, u, cost_out, cost_trace);
+  else
+    cart_mpc_solve_batch<10>(state0, u0, c, *opt, B, u, cost_out, cost_trace);
+  return APG_OK;
+}
+
+int apg_cartpole_mpc_closed_loop_cpu(const float *state0, float dt,
+                                     const ApgCartpoleParams *plant,
+                                     const ApgCartpoleLearnt *plant_learnt,
+                                     const ApgCartpoleParams *model,
+                                     const ApgCartpoleMpcOptions *opt, int B, int H,
+                                     int max_steps, int mode, float thresh_div, int burn_in,
+                                     int *steps, int *upright, double *vel_sum,
+                                     double *vel_sq, float *states, float *actions,
+                                     float *cost) {
+  if (const char *e = cart_mpc_check(model, opt, H)) return fail("%s", e);
+  if (!plant && !plant_learnt) return fail("plant is NULL");
+  if (const char *e = cart_mpc_check_learnt(plant_learnt)) return fail("%s", e);
+  if (const char *e = cart_flight_check(B, max_steps, mode)) return fail("%s", e);
+  if (!state0 || !steps || !upright || !vel_sum || !vel_sq) return fail("NULL buffer");
+  CartConst cp;
+  std::vector<float> rows;
+  if (plant_learnt) {
+    CartLearntParams p;
+    learnt_setup(*plant_learnt, dt, p, cp, rows);
+  } else {
+    cp = make_const(*plant, dt);
+  }
+  const float *r = plant_learnt ? rows.data() : nullptr;   // NULL: cart_step alone
+  const CartConst cm = make_const(*model, dt);
+  const CartFlightRule rule{max_steps, mode, burn_in, thresh_div};
+  if (H == 5)
+    cart_mpc_loop_batch<5>(state0, cp, r, cm, *opt, rule, B, steps, upright, vel_sum, vel_sq,
+                           states, actions, cost);
+  else
+    cart_mpc_loop_batch<10>(state0, cp, r, cm, *opt, rule, B, steps, upright, vel_sum, vel_sq,
+                            states, actions, cost);
   return APG_OK;
 }
 

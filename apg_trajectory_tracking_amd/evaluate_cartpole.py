@@ -13,7 +13,12 @@ Same names, arguments and statistics as the reference:
   * `Evaluator.evaluate_in_environment` / `evaluate_swingup` return the same
     dict (or, with return_success, the same per-flight values).
 There is no renderer, no image / sequence controller and no dynamics
-comparison (`eval_dyn`) here."""
+comparison (`eval_dyn`) here.
+
+With a `controllers.MPC(dynamics="cartpole")` controller - the comparator of
+scripts/evaluate_cartpole.py:399-407 - the same Evaluator flies the batch with
+the solver inside the kernel (apg_cartpole_mpc_closed_loop): the plant is the
+environment's dynamics, the model the MPC object's parameters."""
 import numpy as np
 import torch
 
@@ -140,7 +145,29 @@ class Evaluator:
                          for _ in range(nr_iters)])
 
     # ------------------------------------------------------------ one launch
+    def _fly_mpc(self, starts, max_steps, mode, burn_in):
+        mpc, env = self.controller, self.eval_env
+        if mpc.dynamics_model != "cartpole":
+            raise ValueError("the cart-pole evaluator needs MPC(dynamics='cartpole')")
+        if float(mpc.dt) != float(env.dt):
+            raise ValueError(f"MPC dt {mpc.dt} and environment dt {env.dt} differ: "
+                             "the closed loop has one step length")
+        learnt = _is_learnt(env.dynamics)
+        dev = torch.device(mpc.device or (
+            next(env.dynamics.parameters()).device if learnt else "cuda"))
+        out = F.cartpole_mpc_closed_loop(
+            torch.from_numpy(starts).to(dev), env.dt,
+            None if learnt else env.dynamics.params, model_params=mpc.params,
+            learnt=env.dynamics if learnt else None, max_steps=max_steps, mode=mode,
+            thresh_div=env.thresh_div, burn_in=burn_in, want_trajectory=True,
+            horizon=mpc.horizon, **mpc.options)
+        self.last_flights = out
+        return out
+
     def _fly(self, starts, max_steps, mode, burn_in):
+        from .controllers.mpc import MPC
+        if isinstance(self.controller, MPC):
+            return self._fly_mpc(starts, max_steps, mode, burn_in)
         net = self.controller.net
         dev = next(net.parameters()).device
         dyn = self.eval_env.dynamics

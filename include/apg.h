@@ -1089,6 +1089,61 @@ int apg_cartpole_learnt_mlp_closed_loop(const float *state0, float dt,
                                         float *actions, float *workspace,
                                         apg_stream_t stream);
 
+/* ------------------------------------------------ cartpole, shooting MPC --- */
+/* Batched shooting MPC for the cart-pole - the comparator of the reference's
+ * cart-pole evaluation (scripts/evaluate_cartpole.py:399-407: MPC(horizon=10,
+ * dt=0.05, dynamics="cartpole")), by the method of apg_quad_mpc_solve: single
+ * shooting with projected heavy-ball descent, one trajectory per lane, every
+ * iteration in the registers of that lane (csrc/cartpole_mpc_math.h).  Kept
+ * from the reference (neural_control/controllers/mpc.py:87-100): the action
+ * box [-1, 1], the start u = 0, the warm start by shifting, and the model of
+ * its CasADi twin (cartpole_dynamics.py:239-278): the step of
+ * apg_cartpole_step_fwd with the angle advanced as theta + dt theta_dot, no
+ * atan2 wrap inside the horizon.  The cost is the training loss on the
+ * training reference (apg_cartpole_rollout_fwd_bwd's):
+ *   J = sum_k (s_k - ref_k)^2 . [0, 3, 10, 1] + 0.01 sum_k u_k^2,
+ *   ref_k = state0 (1 - k / (H - 1)) for k < H - 1, the last row 0
+ * (the reference's NLP has no action cost, a linspace reference over H + 2
+ * points and no state cost on the last stage).
+ *   u <- clamp(u - m, -1, 1),  m <- beta m + alpha dJ/du   (m = 0 at the start
+ *   of a solve; a fixed number of iterations)
+ * Reference defaults: iters 10, beta 0.5, alpha 5e-4. */
+typedef struct ApgCartpoleMpcOptions {
+  int iters;
+  float beta, alpha;
+} ApgCartpoleMpcOptions;
+
+/* One solve per trajectory, SoA only: state0 [4][B]; u0 [H][B] the start (a
+ * shifted earlier solution) or NULL: u = 0; u [H][B] the solution (may be u0);
+ * cost_out [B] = J(u); cost_trace [iters + 1][B]: row i = J before iteration
+ * i, row iters = cost_out.  A NULL output drops its writes.  H = 5 or 10. */
+int apg_cartpole_mpc_solve(const float *state0, const float *u0, float dt,
+                           const ApgCartpoleParams *model, const ApgCartpoleMpcOptions *opt,
+                           int B, int H, float *u, float *cost_out, float *cost_trace,
+                           apg_stream_t stream);
+
+/* apg_cartpole_mlp_closed_loop with the policy replaced by "shift the warm
+ * start (rows move up, the last one is repeated), solve, apply u[0]" (first
+ * step: from u = 0): the same modes, thresh_div and burn_in, the same rule for
+ * which steps are recorded, when a balance episode stops, the upright flag and
+ * the fp64 sums, the same outputs and shapes, plus cost [T][B] or NULL
+ * (cost_out of every solve); rows of steps not taken are not written.  The
+ * plant is the environment: the wrapped step of apg_cartpole_step_fwd on
+ * `plant` - or, with plant_learnt != NULL (`plant` is then not read and may be
+ * NULL; the residual must be given), LearntCartpoleDynamics.forward - followed
+ * by CartPoleEnv._step's theta wrap.  `model` is what the solver plans with:
+ * the plant's parameters for the nominal case, others for the model-mismatch
+ * experiment.  The cart position is NOT zeroed between steps (that is
+ * Net.forward's side effect in the network controller's loop).  H = 5 or 10,
+ * B >= 1, max_steps >= 1. */
+int apg_cartpole_mpc_closed_loop(const float *state0, float dt, const ApgCartpoleParams *plant,
+                                 const ApgCartpoleLearnt *plant_learnt,
+                                 const ApgCartpoleParams *model,
+                                 const ApgCartpoleMpcOptions *opt, int B, int H, int max_steps,
+                                 int mode, float thresh_div, int burn_in, int *steps,
+                                 int *upright, double *vel_sum, double *vel_sq, float *states,
+                                 float *actions, float *cost, apg_stream_t stream);
+
 /* --------------------------------------------------------------- misc --- */
 /* loss[0] = fixed-order sum of partials[0..n) (one small kernel). */
 int apg_reduce_loss_partials(const float *partials, int n, float *loss,

@@ -5,7 +5,10 @@
  * per-lane header of the kernels (csrc/quad_mpc_math.h) looped over the batch,
  * signatures of apg.h minus the stream.  The closed loop flies the analytic
  * plant only: `plant_learnt` must be NULL (the learnt simulator's step is a
- * device function), `workspace` is not used (may be NULL).
+ * device function), `workspace` is not used (may be NULL).  The cart-pole
+ * twins (apg_cartpole_mpc_solve, apg_cartpole_mpc_closed_loop; per-lane header
+ * csrc/cartpole_mpc_math.h) fly the learnt plant as well: `plant_learnt` then
+ * holds HOST pointers.
  */
 #ifndef APG_CPU_MPC_H_
 #define APG_CPU_MPC_H_
@@ -27,6 +30,20 @@ int apg_quad_mpc_closed_loop_cpu(const ApgQuadFlight *flight, float dt,
                                  const ApgQuadLossWeights *weights,
                                  const ApgQuadMpcOptions *opt, int B, int H,
                                  float *cost, float *workspace);
+
+int apg_cartpole_mpc_solve_cpu(const float *state0, const float *u0, float dt,
+                               const ApgCartpoleParams *model,
+                               const ApgCartpoleMpcOptions *opt, int B, int H, float *u,
+                               float *cost_out, float *cost_trace);
+int apg_cartpole_mpc_closed_loop_cpu(const float *state0, float dt,
+                                     const ApgCartpoleParams *plant,
+                                     const ApgCartpoleLearnt *plant_learnt,
+                                     const ApgCartpoleParams *model,
+                                     const ApgCartpoleMpcOptions *opt, int B, int H,
+                                     int max_steps, int mode, float thresh_div, int burn_in,
+                                     int *steps, int *upright, double *vel_sum,
+                                     double *vel_sq, float *states, float *actions,
+                                     float *cost);
 
 #ifdef __cplusplus
 }
