@@ -179,6 +179,13 @@ class ApgCartpoleLearnt(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in CARTPOLE_LEARNT_FIELDS + ("w1", "b1", "w2")]
 
 
+class ApgWingLearnt(ctypes.Structure):
+    """Device pointers to a LearntFixedWingDynamics module's live tensors: theta
+    [41] (ApgWingParams order), inertia [9], the residual's four tensors."""
+    _fields_ = [(n, ctypes.c_void_p) for n in (
+        "theta", "inertia", "w1", "b1", "w2", "b2")]
+
+
 class ApgCartpoleMpcOptions(ctypes.Structure):
     """include/apg.h: the cart-pole shooting MPC's iteration count and step rule."""
     _fields_ = [("iters", ctypes.c_int), ("beta", ctypes.c_float),
@@ -289,6 +296,10 @@ SIGNATURES = {
     "apg_wing_learnt_step_bwd": [
         _P, _P, _F, ctypes.POINTER(ApgWingParams), ctypes.POINTER(ctypes.c_float),
         _I, _P, _P, _P, _P, _P, _P],
+    "apg_wing_learnt_rollout_workspace_floats": [_I],
+    "apg_wing_learnt_rollout_fwd_bwd": [
+        _P, _P, _P, _F, ctypes.POINTER(ApgWingLearnt),
+        ctypes.POINTER(ApgWingLossWeights), _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
     "apg_wing_mlp_closed_loop": [
         _P, _I, _P, _F, ctypes.POINTER(ApgWingParams), ctypes.POINTER(ctypes.c_float),
         ctypes.POINTER(ApgLearntResidual),

@@ -12,11 +12,13 @@
 #include <vector>
 
 #include "apg_cpu.h"
+#include "apg_cpu_wing_learnt.h"
 #include "cartpole_learnt_math.h"
 #include "cartpole_math.h"
 #include "cartpole_mpc_math.h"
 #include "quad_math.h"
 #include "quad_mpc_math.h"
+#include "wing_learnt_math.h"
 #include "wing_math.h"
 
 using namespace apg;
@@ -650,6 +652,80 @@ int apg_cartpole_learnt_rollout_fwd_bwd_cpu(const float *state0, const float *ac
     }
     if (grad_state0)
       for (int i = 0; i < 4; ++i) grad_state0[ix.vec(b, i, 4)] = lam[i] + g0[i];
+    out.add(b, B, l);
+  }
+  out.finish(B);
+  return APG_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------- rollout through the learnt fixed wing
+// apg_cpu_wing_learnt.h: wing_learnt_rollout_kernel (wing_learnt.hip) lane for
+// lane - the table and the packed unit rows built as its pack kernel does
+extern "C" {
+
+int apg_wing_learnt_rollout_fwd_bwd_cpu(const float *state0, const float *actions,
+                                        const float *ref, float dt, const ApgWingLearnt *model,
+                                        const ApgWingLossWeights *weights, int B, int H,
+                                        int layout, float *loss_partials, float *loss,
+                                        float *grad_actions, float *grad_state0,
+                                        float *states_out, float *workspace) {
+  (void)workspace;
+  if (B < 0) return fail("B must be >= 0 (got %d)", B);
+  if (layout != APG_LAYOUT_AOS && layout != APG_LAYOUT_SOA)
+    return fail("unknown layout %d", layout);
+  if (!model || !model->theta || !model->inertia || !model->w1 || !model->b1 || !model->w2 ||
+      !model->b2)
+    return fail("model or one of its pointers is NULL");
+  if (!weights) return fail("weights is NULL");
+  if (int e = check_h(H)) return e;
+  if (B == 0) {
+    if (loss) *loss = 0.f;
+    return APG_OK;
+  }
+  if (!state0 || !actions || !ref || !loss_partials || !grad_actions)
+    return fail("state0 / actions / ref / loss_partials / grad_actions must not be NULL");
+  const WingGeneralConst k = wing_learnt_table(model->theta, model->inertia, dt);
+  std::vector<float> rows(kWingResFloats);
+  for (int t = 0; t < kWingResFloats; ++t)
+    rows[t] = wing_residual_packed(t, model->w1, model->b1, model->w2, model->b2);
+  const float *rw = rows.data();
+  const ApgWingLossWeights &w = *weights;
+  const Idx ix{layout, (size_t)B};
+  LossOut out{loss_partials, loss};
+  std::vector<float> pre((size_t)H * 12);
+  for (int b = 0; b < B; ++b) {
+    float s[12], l = 0.f;
+    for (int i = 0; i < 12; ++i) s[i] = state0[ix.vec(b, i, 12)];
+    for (int n = 0; n < H; ++n) {
+      float a[4], lp = 0.f, la = 0.f;
+      for (int j = 0; j < 4; ++j) a[j] = actions[ix.seq(b, n, j, H, 4)];
+      for (int i = 0; i < 12; ++i) pre[n * 12 + i] = s[i];
+      wing_learnt_step(s, a, k, rw);
+      if (states_out)
+        for (int i = 0; i < 12; ++i) states_out[ix.seq(b, n, i, H, 12)] = s[i];
+      for (int i = 0; i < 3; ++i) {
+        const float dp = s[i] - ref[ix.seq(b, n, i, H, 3)], d = a[1 + i] - 0.5f;
+        lp += dp * dp, la += d * d;
+      }
+      l += w.pos * lp + w.action * la;
+    }
+    float lam[12] = {0.f}, nxt[3] = {s[0], s[1], s[2]};
+    for (int n = H - 1; n >= 0; --n) {
+      float a[4], sp[12];
+      for (int j = 0; j < 4; ++j) a[j] = actions[ix.seq(b, n, j, H, 4)];
+      for (int i = 0; i < 12; ++i) sp[i] = pre[n * 12 + i];
+      for (int i = 0; i < 3; ++i)
+        lam[i] += 2.f * w.pos * (nxt[i] - ref[ix.seq(b, n, i, H, 3)]);
+      float ga[4] = {0.f, 2.f * w.action * (a[1] - 0.5f), 2.f * w.action * (a[2] - 0.5f),
+                     2.f * w.action * (a[3] - 0.5f)};
+      wing_learnt_step_adjoint(lam, ga, sp, a, k, rw);
+      for (int j = 0; j < 4; ++j) grad_actions[ix.seq(b, n, j, H, 4)] = ga[j];
+      for (int i = 0; i < 3; ++i) nxt[i] = sp[i];
+    }
+    if (grad_state0)
+      for (int i = 0; i < 12; ++i) grad_state0[ix.vec(b, i, 12)] = lam[i];
     out.add(b, B, l);
   }
   out.finish(B);

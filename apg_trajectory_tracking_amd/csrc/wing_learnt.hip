@@ -20,10 +20,27 @@
 // Sums over the batch: one partial row per wave (shuffle tree), then a second
 // tiny kernel adds the rows in a fixed order - no float atomics, so the same
 // inputs give the same bits.
+//
+// The controller phase through the learnt simulator
+// (TrainFixedWing.train_controller_model, scripts/train_fixed_wing.py:90-110,
+// with the module of fixed_wing_dynamics.py:270-326 as train dynamics) is one
+// fused launch, apg_wing_learnt_rollout_fwd_bwd: H x forward (physics + the
+// 16 -> 64 -> 12 residual network on the pre-step state and the raw action),
+// fixed_wing_mpc_loss and the reverse sweep down to dL/dactions and
+// dL/dstate0; the simulator is frozen there, so no parameter gradient leaves
+// it.  Per-lane arithmetic: wing_learnt_math.h.  Every parameter is read on
+// the DEVICE from the module's own tensors: a small pack kernel in front
+// builds the step table (make_general_const's content) and the residual's
+// unit rows into the caller's workspace, and the rollout reads both through
+// the constant address space where it uses them (wave-uniform scalar loads:
+// no VGPR and no vector memory instruction per weight or coefficient).  One
+// lane = one trajectory; the pre-step states of the reverse sweep are stashed
+// in LDS as [k][12][lane]; the hidden layer is recomputed unit by unit in the
+// reverse sweep, so no lane ever holds the 64 hidden values.
 #include <stddef.h>
 
 #include "apg_device.h"
-#include "wing_math.h"
+#include "wing_learnt_math.h"
 
 namespace apg {
 namespace {
@@ -82,6 +99,94 @@ __global__ __launch_bounds__(64) void wing_learnt_reduce_kernel(
   float acc = 0.f;
   for (int w = 0; w < waves; ++w) acc += wave_partials[(size_t)w * kWingParamGrads + i];
   out[i] = acc;
+}
+
+// ------------------------------------- rollout through the learnt simulator --
+struct WingLearntRolloutArgs {
+  const float *state0, *actions, *ref;
+  float *loss_partials, *grad_actions, *grad_state0, *states_out;
+  const float *pack;            // [table | residual rows | b2], see the pack kernel
+  ApgWingLossWeights w;
+  int B, H;
+};
+
+// [WingGeneralConst, padded to 128 floats | 64 unit rows of 32 | b2, padded to
+// 16] from the module's live tensors.  Thread 0 builds the table (the double-
+// precision 3x3 inverse among it); all threads re-order the weights.
+__global__ __launch_bounds__(256) void wing_learnt_rollout_pack_kernel(ApgWingLearnt m, float dt,
+                                                                       float *__restrict__ pack) {
+  if (threadIdx.x == 0) {
+    *reinterpret_cast<WingGeneralConst *>(pack) = wing_learnt_table(m.theta, m.inertia, dt);
+    for (int i = (int)(sizeof(WingGeneralConst) / sizeof(float)); i < kWingLearntTableFloats; ++i)
+      pack[i] = 0.f;
+  }
+  for (int t = threadIdx.x; t < kWingResFloats; t += blockDim.x)
+    pack[kWingLearntTableFloats + t] = wing_residual_packed(t, m.w1, m.b1, m.w2, m.b2);
+}
+
+template <int LAYOUT>
+__global__ __launch_bounds__(kWave) void wing_learnt_rollout_kernel(WingLearntRolloutArgs A) {
+  extern __shared__ float stash[];
+  const int lane = threadIdx.x;
+  const int b = blockIdx.x * kWave + lane;
+  const bool live = b < A.B;
+  const int bb = live ? b : A.B - 1;
+  const int H = A.H;
+  // (APG_LAUNDER: stops the compiler from hoisting the table's ~70 scalar
+  // loads out of the step loops, where they would not fit the SGPR file)
+  typedef __attribute__((address_space(4))) const float *cfloat_ptr;
+  WingGeneralConstK *kp = (WingGeneralConstK *)A.pack;
+  cfloat_ptr rows = (cfloat_ptr)(A.pack + kWingLearntTableFloats);
+#define APG_LAUNDER(p) asm volatile("" : "+s"(p))
+  const float w_pos = A.w.pos, w_act = A.w.action;
+  auto ST = [&](int k, int i) -> float & { return stash[(k * 12 + i) * kWave + lane]; };
+  float s[12];
+  load_state<LAYOUT, 12>(A.state0, A.B, bb, s);
+  float loss = 0.f;
+  for (int k = 0; k < H; ++k) {
+    float a[4], rp[3];
+    load_seq<LAYOUT, 4>(A.actions, A.B, H, 4, bb, k, 0, a);
+    load_seq<LAYOUT, 3>(A.ref, A.B, H, 3, bb, k, 0, rp);
+#pragma unroll
+    for (int i = 0; i < 12; ++i) ST(k, i) = s[i];
+    APG_LAUNDER(kp);
+    APG_LAUNDER(rows);
+    wing_learnt_step(s, a, *kp, rows);
+    if (A.states_out && live) store_seq<LAYOUT, 12>(A.states_out, A.B, H, 12, b, k, 0, s);
+    float lp = 0.f, la = 0.f;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const float dp = s[i] - rp[i], d = a[1 + i] - 0.5f;
+      lp += dp * dp, la += d * d;
+    }
+    loss += w_pos * lp + w_act * la;
+  }
+  write_wave_partial(A.loss_partials, live ? loss : 0.f, (A.B + kWave - 1) / kWave);
+
+  float lam[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) lam[i] = 0.f;
+  float nxt[3] = {s[0], s[1], s[2]};   // position after step k
+  for (int k = H - 1; k >= 0; --k) {
+    float a[4], rp[3], pre[12];
+    load_seq<LAYOUT, 4>(A.actions, A.B, H, 4, bb, k, 0, a);
+    load_seq<LAYOUT, 3>(A.ref, A.B, H, 3, bb, k, 0, rp);
+#pragma unroll
+    for (int i = 0; i < 12; ++i) pre[i] = ST(k, i);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) lam[i] += 2.f * w_pos * (nxt[i] - rp[i]);
+    float ga[4] = {0.f, 2.f * w_act * (a[1] - 0.5f), 2.f * w_act * (a[2] - 0.5f),
+                   2.f * w_act * (a[3] - 0.5f)};
+    APG_LAUNDER(kp);
+    APG_LAUNDER(rows);
+    wing_learnt_step_adjoint(lam, ga, pre, a, *kp, rows);
+    if (live) store_seq<LAYOUT, 4>(A.grad_actions, A.B, H, 4, b, k, 0, ga);
+    // the state after step k - 1 is the state before step k
+#pragma unroll
+    for (int i = 0; i < 3; ++i) nxt[i] = pre[i];
+  }
+  if (A.grad_state0 && live) store_state<LAYOUT, 12>(A.grad_state0, A.B, b, lam);
+#undef APG_LAUNDER
 }
 
 int check_learnt(const void *state, const void *action, const void *params,
@@ -151,6 +256,71 @@ int apg_wing_learnt_step_bwd(const float *state, const float *action, float dt,
   hipLaunchKernelGGL(wing_learnt_reduce_kernel, dim3(1), dim3(64), 0, st, workspace,
                      blocks * 4, grad_params);
   return check_launch("wing_learnt_step_bwd");
+}
+
+int apg_wing_learnt_rollout_workspace_floats(int B) {
+  return B <= 0 ? 0 : kWingLearntPackFloats;
+}
+
+int apg_wing_learnt_rollout_fwd_bwd(const float *state0, const float *actions, const float *ref,
+                                    float dt, const ApgWingLearnt *model,
+                                    const ApgWingLossWeights *weights, int B, int H, int layout,
+                                    float *loss_partials, float *loss, float *grad_actions,
+                                    float *grad_state0, float *states_out, float *workspace,
+                                    apg_stream_t stream) {
+  if (B < 0) { set_error("B must be >= 0 (got %d)", B); return APG_ERR_ARG; }
+  if (layout != APG_LAYOUT_SOA && layout != APG_LAYOUT_AOS) {
+    set_error("unknown layout %d", layout);
+    return APG_ERR_ARG;
+  }
+  if (!model || !model->theta || !model->inertia || !model->w1 || !model->b1 || !model->w2 ||
+      !model->b2) {
+    set_error("model or one of its pointers is NULL");
+    return APG_ERR_ARG;
+  }
+  if (!weights) { set_error("weights is NULL"); return APG_ERR_ARG; }
+  if (H < 1 || H > APG_MAX_HORIZON) {
+    set_error("H must be in [1, %d] (got %d)", APG_MAX_HORIZON, H);
+    return APG_ERR_ARG;
+  }
+  if (B > 0 && (!state0 || !actions || !ref || !loss_partials || !grad_actions || !workspace)) {
+    set_error("state0 / actions / ref / loss_partials / grad_actions / workspace "
+              "must not be NULL");
+    return APG_ERR_ARG;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (B == 0) {
+    if (loss && hipMemsetAsync(loss, 0, sizeof(float), st) != hipSuccess)
+      return check_launch("memset(loss)");
+    return APG_OK;
+  }
+  hipLaunchKernelGGL(wing_learnt_rollout_pack_kernel, dim3(1), dim3(256), 0, st, *model, dt,
+                     workspace);
+  WingLearntRolloutArgs A;
+  A.state0 = state0, A.actions = actions, A.ref = ref;
+  A.loss_partials = loss_partials, A.grad_actions = grad_actions;
+  A.grad_state0 = grad_state0, A.states_out = states_out;
+  A.pack = workspace, A.w = *weights;
+  A.B = B, A.H = H;
+  // every pre-step state is kept: 3 KB per step and wave, 144 KB at H = 48
+  const size_t lds = (size_t)H * 12 * kWave * sizeof(float);
+  const dim3 grid(grid_for(B, kWave)), block(kWave);
+#define APG_WING_LEARNT_LAUNCH(L)                                                       \
+  do {                                                                                  \
+    if (lds > 64 * 1024 &&                                                              \
+        hipFuncSetAttribute((const void *)wing_learnt_rollout_kernel<L>,                \
+                            hipFuncAttributeMaxDynamicSharedMemorySize,                 \
+                            (int)lds) != hipSuccess)                                    \
+      return check_launch("hipFuncSetAttribute(wing_learnt_rollout)");                  \
+    hipLaunchKernelGGL(wing_learnt_rollout_kernel<L>, grid, block, lds, st, A);         \
+  } while (0)
+  if (layout == APG_LAYOUT_SOA) APG_WING_LEARNT_LAUNCH(APG_LAYOUT_SOA);
+  else APG_WING_LEARNT_LAUNCH(APG_LAYOUT_AOS);
+#undef APG_WING_LEARNT_LAUNCH
+  if (int e = check_launch("wing_learnt_rollout_fwd_bwd")) return e;
+  if (loss)
+    return launch_reduce_partials(loss_partials, apg_loss_partials_count(B), loss, st);
+  return APG_OK;
 }
 
 }  // extern "C"

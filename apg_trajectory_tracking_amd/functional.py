@@ -462,6 +462,90 @@ def wing_rollout_loss(state0, action_seq, ref, dt, params, weights=None,
                                   weights or wing_loss_weights(), layout)
 
 
+# ------------------------------------------ through LearntFixedWingDynamics
+def wing_learnt_fusable(dyn):
+    """Whether `dyn` has the shape the fused learnt rollout is written for: a
+    LearntFixedWingDynamics with the 16 -> 64 -> 12 residual network."""
+    from .dynamics.fixed_wing_dynamics import LearntFixedWingDynamics
+    return (isinstance(dyn, LearntFixedWingDynamics)
+            and tuple(dyn.linear_state_1.weight.shape) == (64, 16)
+            and tuple(dyn.linear_state_1.bias.shape) == (64,)
+            and tuple(dyn.linear_state_2.weight.shape) == (12, 64)
+            and tuple(dyn.linear_state_2.bias.shape) == (12,)
+            and tuple(dyn.I.shape) == (3, 3))
+
+
+def _wing_learnt_tensors(dyn):
+    """The six tensors of ApgWingLearnt: theta (the 41 ApgWingParams entries,
+    gathered ON THE DEVICE from the module's [1] parameters - no host read),
+    the 3x3 parameter I and the residual's weights and biases."""
+    if not wing_learnt_fusable(dyn):
+        raise ValueError("fused rollout expects a LearntFixedWingDynamics with the "
+                         "16 -> 64 -> 12 residual network")
+    tensors = [dyn._theta().detach(), dyn.I.detach(),
+               dyn.linear_state_1.weight.detach(), dyn.linear_state_1.bias.detach(),
+               dyn.linear_state_2.weight.detach(), dyn.linear_state_2.bias.detach()]
+    return [t if t.is_contiguous() else t.contiguous() for t in tensors]
+
+
+def wing_learnt_rollout_fwd_bwd(dyn, state0, actions, ref, dt, weights=None,
+                                layout="aos", want_states=False,
+                                want_grad_state0=True):
+    """wing_rollout_fwd_bwd through the LearntFixedWingDynamics `dyn`
+    (apg_wing_learnt_rollout_fwd_bwd): H x (physics on the module's live
+    parameters + residual network) + fixed_wing_mpc_loss + adjoint down to
+    dL/dactions and dL/dstate0 in one fused launch.  The module's tensors are
+    read on the device when the launch runs, never differentiated."""
+    lay = _layout(layout)
+    if lay == LAYOUT_PACKED:
+        raise ValueError("the learnt fixed-wing rollout takes 'aos' or 'soa' tensors")
+    weights = weights or wing_loss_weights()
+    tensors = _wing_learnt_tensors(dyn)
+    require_device(state0, actions, ref, *tensors)
+    B, H, A = _seq_shape(actions, lay)
+    Br, Hr, C = _seq_shape(ref, lay)
+    if A != 4 or C != 3 or _state_batch(state0, lay) != B or (Br, Hr) != (B, H):
+        raise ValueError("inconsistent rollout shapes")
+    o = _alloc_outs(None, state0.device, B, H, 12, 4, lay, state0, actions,
+                    want_grad_state0, want_states, True)
+    ws = torch.empty(max(lib().apg_wing_learnt_rollout_workspace_floats(B), 1),
+                     dtype=torch.float32, device=state0.device)
+    model = _capi.ApgWingLearnt(*[t.data_ptr() for t in tensors])
+    check(lib().apg_wing_learnt_rollout_fwd_bwd(
+        ptr(state0), ptr(actions), ptr(ref), float(dt), ctypes.byref(model),
+        ctypes.byref(weights), B, H, lay, ptr(o["loss_partials"]), ptr(o["loss"]),
+        ptr(o["grad_actions"]), ptr(o["grad_state0"]), ptr(o["states"]), ptr(ws),
+        stream_of(state0)), "apg_wing_learnt_rollout_fwd_bwd")
+    return o
+
+
+class _WingLearntRolloutLoss(torch.autograd.Function):
+    """loss = fixed_wing_mpc_loss(unroll(learnt_dyn, state0, action_seq), ref,
+    action_seq) as ONE fused rollout; gradients w.r.t. action_seq / state0 only."""
+
+    @staticmethod
+    def forward(ctx, state0, action_seq, ref, dt, dyn, weights):
+        s, a, r = _f32c(state0), _f32c(action_seq), _f32c(ref)
+        res = wing_learnt_rollout_fwd_bwd(
+            dyn, s, a, r, dt, weights, want_grad_state0=ctx.needs_input_grad[0])
+        ctx.save_for_backward(res["grad_actions"], res["grad_state0"])
+        return res["loss"].reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        ga, gs = ctx.saved_tensors
+        ga = ga * g if ctx.needs_input_grad[1] else None
+        gs = gs * g if (gs is not None and ctx.needs_input_grad[0]) else None
+        return gs, ga, None, None, None, None
+
+
+def wing_learnt_rollout_loss(dyn, state0, action_seq, ref, dt, weights=None):
+    """The controller phase through the learnt fixed-wing simulator (frozen
+    there: its parameters receive no gradient)."""
+    return _WingLearntRolloutLoss.apply(state0, action_seq, ref, dt, dyn,
+                                        weights or wing_loss_weights())
+
+
 # -------------------------------------------------------------- cartpole
 def cartpole_rollout_fwd_bwd(state0, actions, dt, params, layout="aos",
                              want_grad_state0=True, want_states=False,

@@ -158,10 +158,37 @@ class TrainFixedWing(TrainBase):
             self.delta_t_train, self.train_dynamics.params, index=index)
         return self._step_direct(loss, grads, flat)
 
+    fused_learnt = True   # controller phase through LearntFixedWingDynamics
+
+    def _fusable_learnt(self):
+        """The fused learnt rollout serves the stock LearntFixedWingDynamics
+        (16 -> 64 -> 12 residual) whose tensors all live on the device the
+        controller trains on, up to the kernel's horizon limit."""
+        from . import _capi
+        d = self.train_dynamics
+        if not (self.fused_learnt and F.wing_learnt_fusable(d)
+                and 1 <= self.horizon <= _capi.MAX_HORIZON):
+            return False
+        devs = {p.device for p in d.parameters()}
+        net = getattr(self, "net", None)
+        if isinstance(net, torch.nn.Module):
+            devs |= {p.device for p in net.parameters()}
+        return len(devs) == 1
+
     def train_controller_model(
         self, current_state, action_seq, in_ref_state, ref_states
     ):
         self.optimizer_controller.zero_grad()
+        if self._fusable_learnt():
+            # learnt simulator, frozen in this phase: the whole unroll through
+            # LearntFixedWingDynamics.forward + loss + backward to the actions
+            # as one fused rollout (apg_wing_learnt_rollout_fwd_bwd); the
+            # simulator's own parameters get no gradient here
+            # (optimizer_controller does not own them)
+            loss = F.wing_learnt_rollout_loss(
+                self.train_dynamics, current_state, action_seq, ref_states,
+                self.delta_t_train)
+            return self._step(loss)
         if not self.analytic_train_dynamics():
             # learnt simulator (LearntFixedWingDynamics): unroll through its
             # own forward, step by step, as the reference does (:94-106)

@@ -923,6 +923,38 @@ int apg_wing_learnt_step_bwd(const float *state, const float *action, float dt,
                              float *grad_action, float *grad_params,
                              float *workspace, apg_stream_t stream);
 
+/* The controller phase through the learnt simulator as ONE fused rollout:
+ * TrainFixedWing.train_controller_model (scripts/train_fixed_wing.py:90-110)
+ * with LearntFixedWingDynamics (fixed_wing_dynamics.py:270-326) as train
+ * dynamics.  Per trajectory: H x forward,
+ *   s' = simulate_fixed_wing(s, a) + W2 relu(W1 [s; a] + b1) + b2
+ * (the residual on the PRE-step state and the raw action), fixed_wing_mpc_loss
+ * with `weights`, and the reverse sweep down to dL/dactions and dL/dstate0.
+ * The simulator is frozen in this phase: no parameter gradient is produced.
+ * Tensors and layouts (APG_LAYOUT_AOS / APG_LAYOUT_SOA) as
+ * apg_wing_rollout_fwd_bwd; grad_state0, states_out and loss may be NULL;
+ * B == 0 zeroes `loss` and returns; H in [1, APG_MAX_HORIZON] (every pre-step
+ * state is kept in LDS: 3 KB per step and wave, 144 KB at H = 48).
+ * Every parameter is read ON THE DEVICE when the launch runs - no host read,
+ * no synchronisation, graph-capturable, always the optimizer's latest values:
+ * a pack kernel in front builds the step table (the double-precision 3x3
+ * inverse, cos / sin of epsilon, the c / b pre-multiplications) and the
+ * residual's unit rows into `workspace`
+ * (apg_wing_learnt_rollout_workspace_floats(B) device floats, which the same
+ * stream's next call may re-use).  A singular `I` therefore cannot be reported
+ * as an error: it yields non-finite outputs.  Argument errors (NULL model
+ * pointers among them) are reported before any HIP call. */
+typedef struct ApgWingLearnt {       /* every pointer a DEVICE pointer to the module's live tensors */
+  const float *theta;                /* [41], ApgWingParams field order; I_* slots ignored */
+  const float *inertia;              /* [9], the parameter I row-major, used in full */
+  const float *w1, *b1, *w2, *b2;    /* [64][16], [64], [12][64], [12] */
+} ApgWingLearnt;
+int apg_wing_learnt_rollout_workspace_floats(int B);
+int apg_wing_learnt_rollout_fwd_bwd(const float *state0, const float *actions, const float *ref,
+    float dt, const ApgWingLearnt *model, const ApgWingLossWeights *weights, int B, int H,
+    int layout, float *loss_partials, float *loss, float *grad_actions, float *grad_state0,
+    float *states_out, float *workspace, apg_stream_t stream);
+
 /* Fused rollout of TrainFixedWing.train_controller_model
  * (scripts/train_fixed_wing.py:90-110) with fixed_wing_mpc_loss.
  *   ref [B,H,3] linear reference (WingDataset._compute_target_pos,
