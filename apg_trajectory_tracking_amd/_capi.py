@@ -186,6 +186,18 @@ class ApgWingLearnt(ctypes.Structure):
         "theta", "inertia", "w1", "b1", "w2", "b2")]
 
 
+# include/apg.h, APG_WING_FIT_*: where each tensor's cotangent starts in the flat
+# gradient of apg_wing_learnt_fit_fwd_bwd (theta [41], I [9], dW1 [64][16], db1
+# [64], dW2 [12][64], db2 [12])
+WING_FIT_G_THETA = 0
+WING_FIT_G_I = 41
+WING_FIT_G_W1 = 50
+WING_FIT_G_B1 = 1074
+WING_FIT_G_W2 = 1138
+WING_FIT_G_B2 = 1906
+WING_FIT_GRADS = 1918
+
+
 class ApgCartpoleMpcOptions(ctypes.Structure):
     """include/apg.h: the cart-pole shooting MPC's iteration count and step rule."""
     _fields_ = [("iters", ctypes.c_int), ("beta", ctypes.c_float),
@@ -300,6 +312,11 @@ SIGNATURES = {
     "apg_wing_learnt_rollout_fwd_bwd": [
         _P, _P, _P, _F, ctypes.POINTER(ApgWingLearnt),
         ctypes.POINTER(ApgWingLossWeights), _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
+    "apg_wing_learnt_fit_grad_count": [],
+    "apg_wing_learnt_fit_workspace_floats": [_I],
+    "apg_wing_learnt_fit_fwd_bwd": [
+        _P, _P, _F, ctypes.POINTER(ApgWingLearnt), _P, ctypes.POINTER(ApgWingParams),
+        _F, _I, _P, _P, _P, _P, _P],
     "apg_wing_mlp_closed_loop": [
         _P, _I, _P, _F, ctypes.POINTER(ApgWingParams), ctypes.POINTER(ctypes.c_float),
         ctypes.POINTER(ApgLearntResidual),

@@ -134,6 +134,7 @@ def build_cpu(force=False, verbose=False):
     deps = [src, os.path.join(REPO, "include", "apg_cpu.h"),
             os.path.join(REPO, "include", "apg_cpu_learnt.h"),
             os.path.join(REPO, "include", "apg_cpu_wing_learnt.h"),
+            os.path.join(REPO, "include", "apg_cpu_wing_fit.h"),
             os.path.join(REPO, "include", "apg_cpu_mpc.h"), __file__] + _headers()
     if (not force and os.path.exists(LIB_CPU)
             and os.path.getmtime(LIB_CPU) >= max(os.path.getmtime(d) for d in deps)):

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "apg_cpu.h"
+#include "apg_cpu_wing_fit.h"
 #include "apg_cpu_wing_learnt.h"
 #include "cartpole_learnt_math.h"
 #include "cartpole_math.h"
@@ -729,6 +730,82 @@ int apg_wing_learnt_rollout_fwd_bwd_cpu(const float *state0, const float *action
     out.add(b, B, l);
   }
   out.finish(B);
+  return APG_OK;
+}
+
+// apg_cpu_wing_fit.h: wing_learnt_fit_kernel (wing_learnt.hip) lane for lane,
+// the batch summed in order; the regulariser as its reduction kernel adds it
+int apg_wing_learnt_fit_fwd_bwd_cpu(const float *state, const float *action, float dt,
+                                    const ApgWingLearnt *model, const float *target,
+                                    const ApgWingParams *eval_params, float l2_lambda, int B,
+                                    float *loss_partials, float *loss, float *grad,
+                                    float *workspace) {
+  (void)workspace;
+  if (B < 0) return fail("B must be >= 0 (got %d)", B);
+  if (!model || !model->theta || !model->inertia || !model->w1 || !model->b1 || !model->w2 ||
+      !model->b2)
+    return fail("model or one of its pointers is NULL");
+  if ((target != nullptr) == (eval_params != nullptr))
+    return fail("exactly one of target / eval_params must be given");
+  if (!(l2_lambda >= 0.f)) return fail("l2_lambda must be >= 0");
+  if (!grad) return fail("grad is NULL");
+  for (int i = 0; i < kWingFitGrads; ++i) grad[i] = 0.f;
+  if (B == 0) {
+    if (loss) *loss = 0.f;
+    return APG_OK;
+  }
+  if (!state || !action || !loss_partials)
+    return fail("state / action / loss_partials must not be NULL");
+  const WingGeneralConst k = wing_learnt_table(model->theta, model->inertia, dt);
+  const WingConst ke = eval_params ? make_const(*eval_params, dt) : WingConst{};
+  std::vector<float> rows(kWingResFloats), acc(kWingFitRow, 0.f);
+  for (int t = 0; t < kWingResFloats; ++t)
+    rows[t] = wing_residual_packed(t, model->w1, model->b1, model->w2, model->b2);
+  const float *rw = rows.data();
+  LossOut out{loss_partials, loss};
+  for (int b = 0; b < B; ++b) {
+    float s[12], a[4], tgt[12], lam[12], z[16];
+    for (int i = 0; i < 12; ++i) s[i] = z[i] = state[(size_t)b * 12 + i];
+    for (int i = 0; i < 4; ++i) a[i] = z[12 + i] = action[(size_t)b * 4 + i];
+    if (eval_params) {
+      for (int i = 0; i < 12; ++i) tgt[i] = s[i];
+      wing_step(tgt, a, ke);
+    } else {
+      for (int i = 0; i < 12; ++i) tgt[i] = target[(size_t)b * 12 + i];
+    }
+    WingParamGrads pg;
+    for (int i = 0; i < kWingParamGrads; ++i) pg.v[i] = 0.f;
+    const float l = wing_learnt_fit_sample(s, a, tgt, k, rw, lam, pg);
+    for (int i = 0; i < kWingParamGrads; ++i) acc[i] += pg.v[i];
+    for (int o = 0; o < 12; ++o) acc[kWingParamGrads + o] += lam[o];
+    for (int m = 0; m < kWingResHidden; ++m) {
+      float gw[kWingFitUnit] = {0.f};
+      wing_residual_unit_grads(rw + m * kWingResRow, z, lam, gw);
+      for (int j = 0; j < kWingFitUnit; ++j)
+        acc[kWingFitHead + j * kWingResHidden + m] += gw[j];
+    }
+    out.add(b, B, l);
+  }
+  out.finish(B);
+  float norms[4] = {0.f, 0.f, 0.f, 0.f};
+  if (l2_lambda > 0.f) {
+    const float *tens[4] = {model->w2, model->b2, model->w1, model->b1};
+    const int count[4] = {12 * kWingResHidden, 12, kWingResHidden * 16, kWingResHidden};
+    for (int q = 0; q < 4; ++q) {
+      float ss = 0.f;
+      for (int t = 0; t < count[q]; ++t) ss = fmaf(tens[q][t], tens[q][t], ss);
+      norms[q] = sqrtf(ss);
+    }
+    if (loss) *loss += l2_lambda * (((norms[0] + norms[1]) + norms[2]) + norms[3]);
+  }
+  for (int c = 0; c < kWingFitRow; ++c) {
+    const int dest = wing_fit_dest(c);
+    if (dest < 0) continue;
+    grad[dest] = acc[c] + (l2_lambda > 0.f
+                               ? wing_fit_l2_grad(dest, l2_lambda, model->w1, model->b1,
+                                                  model->w2, model->b2, norms)
+                               : 0.f);
+  }
   return APG_OK;
 }
 

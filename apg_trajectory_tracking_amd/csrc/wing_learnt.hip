@@ -37,6 +37,13 @@
 // lane = one trajectory; the pre-step states of the reverse sweep are stashed
 // in LDS as [k][12][lane]; the hidden layer is recomputed unit by unit in the
 // reverse sweep, so no lane ever holds the 64 hidden values.
+//
+// The simulator-fit phase (TrainBase.train_dynamics_model,
+// scripts/train_base.py:160-186) for the same module is
+// apg_wing_learnt_fit_fwd_bwd: prediction on the live parameters, the target
+// (given, or the analytic step computed in the same lane), the squared error,
+// and the batch-summed cotangent of all 50 + 1868 parameters in one flat
+// buffer, regulariser included - see "the simulator fit's step" below.
 #include <stddef.h>
 
 #include "apg_device.h"
@@ -189,6 +196,199 @@ __global__ __launch_bounds__(kWave) void wing_learnt_rollout_kernel(WingLearntRo
 #undef APG_LAUNDER
 }
 
+// ------------------------------------------------ the simulator fit's step --
+// TrainBase.train_dynamics_model (scripts/train_base.py:160-186) for this
+// module as three launches behind one entry point: pack (the table, the rows
+// and the four weight norms from the live tensors), the fit kernel (forward,
+// target, loss, reverse sweep, every parameter's cotangent summed over the
+// WORKGROUP), and a reduction over the workgroups' rows that also adds the
+// regulariser.  No float atomics: a wave sums its 64 samples (the physical
+// cotangents and db2 by a shuffle tree; the weights' by lane m = hidden unit m
+// looping over the wave's samples in LDS), the four waves of a workgroup are
+// added in wave order in LDS, the rows by a fixed tree.
+static_assert(kWingFitGW1 == APG_WING_FIT_G_W1 && kWingFitGB1 == APG_WING_FIT_G_B1 &&
+                  kWingFitGW2 == APG_WING_FIT_G_W2 && kWingFitGB2 == APG_WING_FIT_G_B2 &&
+                  kWingFitGrads == APG_WING_FIT_GRADS && APG_WING_FIT_G_I == 41,
+              "apg.h publishes these offsets");
+constexpr int kFitBlock = 256, kFitWaves = kFitBlock / kWave;
+constexpr int kFitSample = 28;                    // z (16), lam (12) per sample
+// a wave's LDS: its samples [28][64] first, its 29 weight planes [29][64] after
+constexpr int kFitWaveLds = kWingFitUnit * kWave;
+static_assert(kFitSample <= kWingFitUnit, "the weight planes re-use the sample planes");
+// workspace: [pack | norms (4), padded to 16 | rows]
+constexpr int kFitNorms = kWingLearntPackFloats, kFitRows = kFitNorms + 16;
+
+// wing_learnt_rollout_pack_kernel's content plus |W2|, |b2|, |W1|, |b1|
+// (2-norms; per-thread strided sums, then a fixed tree)
+__global__ __launch_bounds__(256) void wing_learnt_fit_pack_kernel(ApgWingLearnt m, float dt,
+                                                                   float *__restrict__ ws) {
+  __shared__ float part[4][256];
+  if (threadIdx.x == 0) {
+    *reinterpret_cast<WingGeneralConst *>(ws) = wing_learnt_table(m.theta, m.inertia, dt);
+    for (int i = (int)(sizeof(WingGeneralConst) / sizeof(float)); i < kWingLearntTableFloats; ++i)
+      ws[i] = 0.f;
+  }
+  for (int t = threadIdx.x; t < kWingResFloats; t += blockDim.x)
+    ws[kWingLearntTableFloats + t] = wing_residual_packed(t, m.w1, m.b1, m.w2, m.b2);
+  const float *tens[4] = {m.w2, m.b2, m.w1, m.b1};
+  const int count[4] = {12 * kWingResHidden, 12, kWingResHidden * 16, kWingResHidden};
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    float acc = 0.f;
+    for (int t = threadIdx.x; t < count[q]; t += 256) acc = fmaf(tens[q][t], tens[q][t], acc);
+    part[q][threadIdx.x] = acc;
+  }
+  for (int half = 128; half >= 1; half >>= 1) {
+    __syncthreads();
+    if ((int)threadIdx.x < half)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) part[q][threadIdx.x] += part[q][threadIdx.x + half];
+  }
+  if (threadIdx.x < 4) ws[kFitNorms + threadIdx.x] = sqrtf(part[threadIdx.x][0]);
+}
+
+struct WingFitArgs {
+  const float *state, *action, *target;   // target NULL: the analytic step on `eval`
+  const float *ws;                        // the pack
+  float *loss_partials, *rows;
+  WingConst eval;
+  int B;
+};
+
+template <bool EVAL>
+__global__ __launch_bounds__(kFitBlock) void wing_learnt_fit_kernel(WingFitArgs A) {
+  __shared__ float smp[kFitWaves][kFitWaveLds];
+  __shared__ float head[kFitWaves][kWingFitHead];
+  typedef __attribute__((address_space(4))) const float *cfloat_ptr;
+  WingGeneralConstK *kp = (WingGeneralConstK *)A.ws;
+  cfloat_ptr rows = (cfloat_ptr)(A.ws + kWingLearntTableFloats);
+  const int lane = threadIdx.x & (kWave - 1), wl = threadIdx.x >> 6;
+  const int b = blockIdx.x * kFitBlock + threadIdx.x;
+  const bool live = b < A.B;
+  const int bb = live ? b : A.B - 1;
+  WingParamGrads pg;
+#pragma unroll
+  for (int i = 0; i < kWingParamGrads; ++i) pg.v[i] = 0.f;
+  float s[12], a[4], tgt[12], lam[12];
+  load_state<APG_LAYOUT_AOS, 12>(A.state, A.B, bb, s);
+  load_state<APG_LAYOUT_AOS, 4>(A.action, A.B, bb, a);
+  if constexpr (EVAL) {
+#pragma unroll
+    for (int i = 0; i < 12; ++i) tgt[i] = s[i];
+    const WingConst &ke = A.eval;
+    wing_step(tgt, a, ke);
+  } else {
+    load_state<APG_LAYOUT_AOS, 12>(A.target, A.B, bb, tgt);
+  }
+  float loss = wing_learnt_fit_sample(s, a, tgt, *kp, rows, lam, pg);
+  // a dead lane adds nothing: zero seed, zero cotangents
+  if (!live) {
+    loss = 0.f;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) lam[i] = 0.f;
+#pragma unroll
+    for (int i = 0; i < kWingParamGrads; ++i) pg.v[i] = 0.f;
+  }
+  write_wave_partial(A.loss_partials, loss, (A.B + kWave - 1) / kWave);
+#pragma unroll
+  for (int i = 0; i < kWingParamGrads; ++i) {
+    const float v = wave_sum(pg.v[i]);
+    if (lane == 0) head[wl][i] = v;
+  }
+#pragma unroll
+  for (int o = 0; o < 12; ++o) {
+    const float v = wave_sum(lam[o]);   // db2
+    if (lane == 0) head[wl][kWingParamGrads + o] = v;
+  }
+  if (lane < 2) head[wl][kWingParamGrads + 12 + lane] = 0.f;
+  // the wave's samples into its LDS planes, then lane m = hidden unit m over
+  // all 64 (each wave reads and writes its own planes only)
+  float *mine = smp[wl];
+#pragma unroll
+  for (int j = 0; j < 12; ++j) mine[j * kWave + lane] = s[j];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) mine[(12 + j) * kWave + lane] = a[j];
+#pragma unroll
+  for (int o = 0; o < 12; ++o) mine[(16 + o) * kWave + lane] = lam[o];
+  __syncthreads();
+  float w[kWingResRow], gw[kWingFitUnit];
+  {
+    const float4 *src = reinterpret_cast<const float4 *>(A.ws + kWingLearntTableFloats +
+                                                         lane * kWingResRow);
+#pragma unroll
+    for (int q = 0; q < kWingResRow / 4; ++q) {
+      const float4 v = src[q];
+      w[4 * q] = v.x, w[4 * q + 1] = v.y, w[4 * q + 2] = v.z, w[4 * q + 3] = v.w;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < kWingFitUnit; ++j) gw[j] = 0.f;
+#pragma unroll 2
+  for (int n = 0; n < kWave; ++n) {
+    float zn[16], ln[12];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) zn[j] = mine[j * kWave + n];
+#pragma unroll
+    for (int o = 0; o < 12; ++o) ln[o] = mine[(16 + o) * kWave + n];
+    wing_residual_unit_grads(w, zn, ln, gw);
+  }
+  __syncthreads();   // (uniform trip count above: every wave is done reading)
+#pragma unroll
+  for (int j = 0; j < kWingFitUnit; ++j) mine[j * kWave + lane] = gw[j];
+  __syncthreads();
+  // the four waves in wave order -> one row per workgroup
+  float *row = A.rows + (size_t)blockIdx.x * kWingFitRow;
+  for (int c = threadIdx.x; c < kWingFitRow; c += kFitBlock) {
+    float acc;
+    if (c < kWingFitHead) {
+      acc = head[0][c];
+#pragma unroll
+      for (int v = 1; v < kFitWaves; ++v) acc += head[v][c];
+    } else {
+      acc = smp[0][c - kWingFitHead];
+#pragma unroll
+      for (int v = 1; v < kFitWaves; ++v) acc += smp[v][c - kWingFitHead];
+    }
+    row[c] = acc;
+  }
+}
+
+// grad[dest(c)] = sum over the workgroups' rows of element c (+ the
+// regulariser's gradient); kFitSplit threads per element: thread r adds rows
+// r, r + kFitSplit, ... in order, then a fixed tree over the kFitSplit sums.
+// Thread 0 of workgroup 0 adds the penalty to the loss, which the loss
+// reduction in front of this launch has written.
+constexpr int kFitCols = 32, kFitSplit = 8;
+__global__ __launch_bounds__(kFitCols * kFitSplit) void wing_learnt_fit_reduce_kernel(
+    const float *__restrict__ ws, int nrows, ApgWingLearnt m, float l2_lambda,
+    float *__restrict__ grad, float *__restrict__ loss) {
+  __shared__ float part[kFitSplit][kFitCols];
+  const int col = threadIdx.x % kFitCols, r = threadIdx.x / kFitCols;
+  const int c = blockIdx.x * kFitCols + col;          // kWingFitRow = 60 x 32
+  const float *rows = ws + kFitRows;
+  float acc = 0.f;
+#pragma unroll 4
+  for (int i = r; i < nrows; i += kFitSplit) acc += rows[(size_t)i * kWingFitRow + c];
+  part[r][col] = acc;
+  __syncthreads();
+  if (r == 0) {
+    const float v = ((part[0][col] + part[1][col]) + (part[2][col] + part[3][col])) +
+                    ((part[4][col] + part[5][col]) + (part[6][col] + part[7][col]));
+    const int dest = wing_fit_dest(c);
+    if (dest >= 0) {
+      float reg = 0.f;
+      if (l2_lambda > 0.f)
+        reg = wing_fit_l2_grad(dest, l2_lambda, m.w1, m.b1, m.w2, m.b2, ws + kFitNorms);
+      grad[dest] = v + reg;
+    }
+  }
+  if (l2_lambda > 0.f && loss && blockIdx.x == 0 && threadIdx.x == 0) {
+    const float *n = ws + kFitNorms;
+    loss[0] += l2_lambda * (((n[0] + n[1]) + n[2]) + n[3]);
+  }
+}
+static_assert(kWingFitRow % kFitCols == 0, "whole workgroups of columns");
+
 int check_learnt(const void *state, const void *action, const void *params,
                  const float *inertia, int B) {
   if (B < 0) { set_error("B must be >= 0 (got %d)", B); return APG_ERR_ARG; }
@@ -321,6 +521,64 @@ int apg_wing_learnt_rollout_fwd_bwd(const float *state0, const float *actions, c
   if (loss)
     return launch_reduce_partials(loss_partials, apg_loss_partials_count(B), loss, st);
   return APG_OK;
+}
+
+int apg_wing_learnt_fit_grad_count(void) { return kWingFitGrads; }
+
+int apg_wing_learnt_fit_workspace_floats(int B) {
+  return B <= 0 ? 0 : kFitRows + grid_for(B, kFitBlock) * kWingFitRow;
+}
+
+int apg_wing_learnt_fit_fwd_bwd(const float *state, const float *action, float dt,
+                                const ApgWingLearnt *model, const float *target,
+                                const ApgWingParams *eval_params, float l2_lambda, int B,
+                                float *loss_partials, float *loss, float *grad,
+                                float *workspace, apg_stream_t stream) {
+  if (B < 0) { set_error("B must be >= 0 (got %d)", B); return APG_ERR_ARG; }
+  if (!model || !model->theta || !model->inertia || !model->w1 || !model->b1 || !model->w2 ||
+      !model->b2) {
+    set_error("model or one of its pointers is NULL");
+    return APG_ERR_ARG;
+  }
+  if ((target != nullptr) == (eval_params != nullptr)) {
+    set_error("exactly one of target / eval_params must be given");
+    return APG_ERR_ARG;
+  }
+  if (!(l2_lambda >= 0.f)) { set_error("l2_lambda must be >= 0"); return APG_ERR_ARG; }
+  if (!grad) { set_error("grad is NULL"); return APG_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  if (B == 0) {
+    if (hipMemsetAsync(grad, 0, kWingFitGrads * sizeof(float), st) != hipSuccess ||
+        (loss && hipMemsetAsync(loss, 0, sizeof(float), st) != hipSuccess))
+      return check_launch("memset(grad, loss)");
+    return APG_OK;
+  }
+  if (!state || !action || !loss_partials || !workspace) {
+    set_error("state / action / loss_partials / workspace must not be NULL");
+    return APG_ERR_ARG;
+  }
+  hipLaunchKernelGGL(wing_learnt_fit_pack_kernel, dim3(1), dim3(256), 0, st, *model, dt,
+                     workspace);
+  WingFitArgs A;
+  A.state = state, A.action = action, A.target = target;
+  A.ws = workspace, A.loss_partials = loss_partials, A.rows = workspace + kFitRows;
+  A.B = B;
+  const int blocks = grid_for(B, kFitBlock);
+  if (eval_params) {
+    A.eval = make_const(*eval_params, dt);
+    hipLaunchKernelGGL(wing_learnt_fit_kernel<true>, dim3(blocks), dim3(kFitBlock), 0, st, A);
+  } else {
+    A.eval = WingConst{};
+    hipLaunchKernelGGL(wing_learnt_fit_kernel<false>, dim3(blocks), dim3(kFitBlock), 0, st, A);
+  }
+  if (int e = check_launch("wing_learnt_fit_fwd_bwd")) return e;
+  if (loss)
+    if (int e = launch_reduce_partials(loss_partials, apg_loss_partials_count(B), loss, st))
+      return e;
+  hipLaunchKernelGGL(wing_learnt_fit_reduce_kernel, dim3(kWingFitRow / kFitCols),
+                     dim3(kFitCols * kFitSplit), 0, st, workspace, blocks, *model, l2_lambda,
+                     grad, loss);
+  return check_launch("wing_learnt_fit_reduce");
 }
 
 }  // extern "C"

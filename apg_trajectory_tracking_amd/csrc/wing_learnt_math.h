@@ -186,5 +186,103 @@ __host__ __device__ __forceinline__ void wing_learnt_step_adjoint(float (&lam)[1
   for (int i = 0; i < 4; ++i) ga[i] += dz[12 + i];
 }
 
+// ------------------------------------------------- the simulator fit's step --
+// TrainBase.train_dynamics_model (scripts/train_base.py:160-186) on this
+// module: loss = sum (forward(s, a) - target)^2 and the cotangent of EVERY
+// parameter.  The flat gradient (apg.h: APG_WING_FIT_*): the 41 + 9 physical
+// cotangents in apg_wing_learnt_step_bwd's layout, then dW1 [64][16], db1
+// [64], dW2 [12][64], db2 [12].
+constexpr int kWingFitGW1 = kWingParamGrads;                        // 50
+constexpr int kWingFitGB1 = kWingFitGW1 + kWingResHidden * 16;      // 1074
+constexpr int kWingFitGW2 = kWingFitGB1 + kWingResHidden;           // 1138
+constexpr int kWingFitGB2 = kWingFitGW2 + 12 * kWingResHidden;      // 1906
+constexpr int kWingFitGrads = kWingFitGB2 + 12;                     // 1918
+// A partial row as the kernel sums it: [50 physical | db2 (12) | 0 0 | 29
+// planes of 64: plane j < 16 = dW1[.][j], plane 16 + o = dW2[o][.], plane 28 =
+// db1] - hidden unit m owns element m of every plane.
+constexpr int kWingFitUnit = 29;                                    // a unit's cotangents
+constexpr int kWingFitHead = 64;
+constexpr int kWingFitRow = kWingFitHead + kWingFitUnit * kWingResHidden;   // 1920
+
+// element c of a partial row -> its place in the flat gradient (-1: padding)
+__host__ __device__ __forceinline__ int wing_fit_dest(int c) {
+  if (c < kWingParamGrads) return c;
+  if (c < kWingParamGrads + 12) return kWingFitGB2 + (c - kWingParamGrads);
+  if (c < kWingFitHead) return -1;
+  const int j = (c - kWingFitHead) / kWingResHidden, m = (c - kWingFitHead) % kWingResHidden;
+  if (j < 16) return kWingFitGW1 + m * 16 + j;
+  if (j < 28) return kWingFitGW2 + (j - 16) * kWingResHidden + m;
+  return kWingFitGB1 + m;
+}
+
+// One sample of the fit: pred = forward(s, a) on the live table and rows,
+// returns sum (pred - tgt)^2; lam = 2 (pred - tgt) (the seed of the reverse
+// sweep, which the residual's cotangents need as it stands); pg += the
+// physical cotangents.  dL/dstate and dL/daction are not produced.
+template <typename KT, typename P>
+__host__ __device__ __forceinline__ float wing_learnt_fit_sample(const float (&s)[12],
+                                                                 const float (&a)[4],
+                                                                 const float (&tgt)[12],
+                                                                 KT &k, P rows,
+                                                                 float (&lam)[12],
+                                                                 WingParamGrads &pg) {
+  float z[16], r[12], sd[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) z[i] = s[i], r[i] = 0.f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) z[12 + i] = a[i];
+  wing_residual_add(r, z, rows);
+  WingAux x;
+  wing_rates(s, a, k, x, sd);
+  float loss = 0.f, lp[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) {
+    const float d = ((s[i] + k.dt * sd[i]) + r[i]) - tgt[i];   // wing_learnt_step's sum
+    loss = fmaf(d, d, loss);
+    lam[i] = lp[i] = 2.f * d;
+  }
+  float ga[4] = {0.f, 0.f, 0.f, 0.f};
+  wing_step_adjoint(lp, ga, s, x, sd, k, pg);
+  return loss;
+}
+
+// gw += hidden unit's 29 cotangents for one sample (z, lam): gw[j < 16] =
+// dW1[m][j], gw[16 + o] = dW2[o][m], gw[28] = db1[m]; w = the unit's packed row
+// (relu'(0) = 0, as torch's threshold backward)
+__host__ __device__ __forceinline__ void wing_residual_unit_grads(const float *w,
+                                                                  const float (&z)[16],
+                                                                  const float (&lam)[12],
+                                                                  float (&gw)[kWingFitUnit]) {
+  float h = w[kWingResB1];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) h = fmaf(w[j], z[j], h);
+  float dh = 0.f;
+#pragma unroll
+  for (int o = 0; o < 12; ++o) dh = fmaf(w[kWingResW2 + o], lam[o], dh);
+  dh = h > 0.f ? dh : 0.f;
+  h = fmaxf(h, 0.f);
+#pragma unroll
+  for (int j = 0; j < 16; ++j) gw[j] = fmaf(dh, z[j], gw[j]);
+#pragma unroll
+  for (int o = 0; o < 12; ++o) gw[16 + o] = fmaf(lam[o], h, gw[16 + o]);
+  gw[28] += dh;
+}
+
+// the regulariser's gradient l2_lambda t / |t| (0 where |t| = 0, as torch's
+// norm backward) for element `dest` of the flat gradient; norms = |W2|, |b2|,
+// |W1|, |b1| (the order of _residual_weight_norm)
+__host__ __device__ __forceinline__ float wing_fit_l2_grad(int dest, float l2_lambda,
+                                                           const float *w1, const float *b1,
+                                                           const float *w2, const float *b2,
+                                                           const float *norms) {
+  if (dest < kWingFitGW1) return 0.f;
+  float t, n;
+  if (dest < kWingFitGB1) t = w1[dest - kWingFitGW1], n = norms[2];
+  else if (dest < kWingFitGW2) t = b1[dest - kWingFitGB1], n = norms[3];
+  else if (dest < kWingFitGB2) t = w2[dest - kWingFitGW2], n = norms[0];
+  else t = b2[dest - kWingFitGB2], n = norms[1];
+  return n > 0.f ? l2_lambda * (t / n) : 0.f;
+}
+
 }  // namespace
 }  // namespace apg

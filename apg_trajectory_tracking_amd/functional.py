@@ -546,6 +546,61 @@ def wing_learnt_rollout_loss(dyn, state0, action_seq, ref, dt, weights=None):
                                         weights or wing_loss_weights())
 
 
+def wing_learnt_fit_fwd_bwd(dyn, state, action, dt, target=None, eval_params=None,
+                            l2_lambda=0.0):
+    """One step of the simulator fit (TrainBase.train_dynamics_model) on the
+    LearntFixedWingDynamics `dyn`, fused (apg_wing_learnt_fit_fwd_bwd):
+    loss = sum (dyn(state, action, dt) - target)^2 + l2_lambda x the residual's
+    four weight norms, and its gradient for EVERY parameter of `dyn` as one
+    flat tensor (wing_learnt_fit_grad_views hands out the per-parameter views).
+    The target is `target` [B,12], or the analytic step with `eval_params`
+    (an ApgWingParams, e.g. FixedWingDynamics.params) - exactly one of the two.
+    The module's tensors are read on the device when the launches run: no host
+    read, no synchronisation, capturable in a graph."""
+    tensors = _wing_learnt_tensors(dyn)
+    state, action = _f32c(state), _f32c(action)
+    if target is not None:
+        target = _f32c(target)
+    require_device(state, action, target, *tensors)
+    if state.dim() != 2 or state.shape[1] != 12 or action.shape != (state.shape[0], 4):
+        raise ValueError("state [B,12] / action [B,4] expected")
+    if target is not None and target.shape != state.shape:
+        raise ValueError("target [B,12] expected")
+    B, dev = state.shape[0], state.device
+    grad = torch.empty(_capi.WING_FIT_GRADS, dtype=torch.float32, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    parts = torch.empty(_capi.loss_partials_count(B), dtype=torch.float32, device=dev)
+    ws = torch.empty(max(lib().apg_wing_learnt_fit_workspace_floats(B), 1),
+                     dtype=torch.float32, device=dev)
+    model = _capi.ApgWingLearnt(*[t.data_ptr() for t in tensors])
+    check(lib().apg_wing_learnt_fit_fwd_bwd(
+        ptr(state), ptr(action), float(dt), ctypes.byref(model), ptr(target),
+        None if eval_params is None else ctypes.byref(eval_params), float(l2_lambda), B,
+        ptr(parts), ptr(loss), ptr(grad), ptr(ws), stream_of(state)),
+        "apg_wing_learnt_fit_fwd_bwd")
+    return dict(loss=loss, grad=grad)
+
+
+def wing_learnt_fit_grad_views(dyn, grad):
+    """The flat gradient of wing_learnt_fit_fwd_bwd as one view per parameter,
+    in the order (and shapes) of dyn.named_parameters(): `I` [3,3], each
+    `cfg.<name>` [1], the residual's four tensors.  Views, not copies:
+    `p.grad = view` costs no launch."""
+    at = {"I": (_capi.WING_FIT_G_I, (3, 3)),
+          "linear_state_1.weight": (_capi.WING_FIT_G_W1, (64, 16)),
+          "linear_state_1.bias": (_capi.WING_FIT_G_B1, (64,)),
+          "linear_state_2.weight": (_capi.WING_FIT_G_W2, (12, 64)),
+          "linear_state_2.bias": (_capi.WING_FIT_G_B2, (12,))}
+    views = []
+    for name, p in dyn.named_parameters():
+        if name.startswith("cfg."):
+            off, shape = _capi.WING_PARAM_FIELDS.index(name[4:]), (1,)
+        else:
+            off, shape = at[name]
+        views.append(grad[off:off + p.numel()].view(shape))
+    return views
+
+
 # -------------------------------------------------------------- cartpole
 def cartpole_rollout_fwd_bwd(state0, actions, dt, params, layout="aos",
                              want_grad_state0=True, want_states=False,

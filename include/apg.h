@@ -955,6 +955,43 @@ int apg_wing_learnt_rollout_fwd_bwd(const float *state0, const float *actions, c
     int layout, float *loss_partials, float *loss, float *grad_actions, float *grad_state0,
     float *states_out, float *workspace, apg_stream_t stream);
 
+/* The simulator-fit phase for the same module as ONE call:
+ * TrainBase.train_dynamics_model (scripts/train_base.py:160-186) with
+ * LearntFixedWingDynamics as train dynamics, up to (not including) the
+ * optimizer step.  AoS state [B,12] / action [B,4].
+ *   pred   = simulate_fixed_wing(s, a; live theta, full 3x3 I)
+ *            + W2 relu(W1 [s; a] + b1) + b2
+ *   target = `target` [B,12] (device), or - target NULL - the analytic step
+ *            with `eval_params` (a HOST struct: make_const / sparse inertia, as
+ *            apg_wing_step_fwd computes it).  Exactly one of the two is given.
+ *   loss   = sum_b sum_i (pred - target)^2
+ *            + l2_lambda (|W2| + |b2| + |W1| + |b1|)   (four 2-norms; l2_lambda >= 0)
+ *   grad   = d loss / d parameter, summed over the batch, ONE flat buffer of
+ *            apg_wing_learnt_fit_grad_count() = APG_WING_FIT_GRADS floats:
+ *            [0, 41) the physical cotangents in ApgWingParams order and [41, 50)
+ *            dL/dI row-major, exactly apg_wing_learnt_step_bwd's grad_params (I_*
+ *            and g: 0); then dW1 [64][16], db1 [64], dW2 [12][64], db2 [12] at the
+ *            offsets below.  A tensor of norm 0 gets no regulariser gradient (as
+ *            torch's norm backward): a fresh, zero-initialised residual is fine.
+ * loss_partials: apg_loss_partials_count(B) floats; loss may be NULL.
+ * workspace: apg_wing_learnt_fit_workspace_floats(B) device floats.  B == 0
+ * zeroes loss and grad and returns.  Every model parameter is read ON THE DEVICE
+ * when the launches run (no host read, no synchronisation, graph-capturable);
+ * no float atomics: the same inputs give the same bits. */
+#define APG_WING_FIT_G_THETA 0
+#define APG_WING_FIT_G_I 41
+#define APG_WING_FIT_G_W1 50
+#define APG_WING_FIT_G_B1 1074
+#define APG_WING_FIT_G_W2 1138
+#define APG_WING_FIT_G_B2 1906
+#define APG_WING_FIT_GRADS 1918
+int apg_wing_learnt_fit_grad_count(void);
+int apg_wing_learnt_fit_workspace_floats(int B);
+int apg_wing_learnt_fit_fwd_bwd(const float *state, const float *action, float dt,
+    const ApgWingLearnt *model, const float *target, const ApgWingParams *eval_params,
+    float l2_lambda, int B, float *loss_partials, float *loss, float *grad,
+    float *workspace, apg_stream_t stream);
+
 /* Fused rollout of TrainFixedWing.train_controller_model
  * (scripts/train_fixed_wing.py:90-110) with fixed_wing_mpc_loss.
  *   ref [B,H,3] linear reference (WingDataset._compute_target_pos,
