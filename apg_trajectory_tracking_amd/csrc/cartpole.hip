@@ -9,6 +9,7 @@
 // the whole batch; the kernel exists for parity and API completeness.
 #include "apg_device.h"
 #include "cartpole_math.h"
+#include "cartpole_rollout_math.h"
 
 namespace apg {
 namespace {
@@ -49,7 +50,8 @@ struct CartRolloutArgs {
   int B, H;
 };
 
-// Per-step stash in LDS as [k][4][lane]: the pre-step state.
+// cartpole_rollout_math.h with the analytic step; the per-step stash in LDS as
+// [k][4][lane]: the pre-step state.
 template <int LAYOUT>
 __global__ __launch_bounds__(APG_ROLLOUT_BLOCK) void cart_rollout_kernel(
     CartRolloutArgs A) {
@@ -60,61 +62,32 @@ __global__ __launch_bounds__(APG_ROLLOUT_BLOCK) void cart_rollout_kernel(
   const int bb = live ? b : A.B - 1;
   const CartConst c = A.c;
   const int H = A.H;
-  const float wq[4] = {0.f, 3.f, 10.f, 1.f};  // drone_loss.py:136
-  // make_reference: ref_k = s0 * (1 - 1/(H-1) * k), k < H-1; last row zero
-  const double inv = H > 1 ? 1.0 / (double)(H - 1) : 0.0;
+  auto action = [&](int k) {
+    float a[1];
+    load_seq<LAYOUT, 1>(A.actions, A.B, H, 1, bb, k, 0, a);
+    return a[0];
+  };
   auto ST = [&](int k, int i) -> float & {
     return stash[(k * 4 + i) * APG_ROLLOUT_BLOCK + lane];
   };
-  float s0[4], s[4];
+  float s0[4], s[4], lam[4];
   load_state<LAYOUT, 4>(A.state0, A.B, bb, s0);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) s[i] = s0[i];
-  float loss = 0.f;
-  for (int k = 0; k < H; ++k) {
-    float a[1];
-    load_seq<LAYOUT, 1>(A.actions, A.B, H, 1, bb, k, 0, a);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) ST(k, i) = s[i];
-    cart_step(s, a[0], c);
-    if (A.states_out && live)
-      store_seq<LAYOUT, 4>(A.states_out, A.B, H, 4, b, k, 0, s);
-    const float f = k < H - 1 ? (float)(1.0 - inv * (double)k) : 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float d = s[i] - s0[i] * f;
-      loss += (d * d) * wq[i];
-    }
-    loss += 0.01f * a[0] * a[0];
-  }
+  const float loss = cart_rollout_forward(
+      H, s0, s, action, ST, [&](float (&x)[4], float a) { cart_step(x, a, c); },
+      [&](int k, const float (&x)[4]) {
+        if (A.states_out && live) store_seq<LAYOUT, 4>(A.states_out, A.B, H, 4, b, k, 0, x);
+      });
   write_wave_partial(A.loss_partials, live ? loss : 0.f, (A.B + kWave - 1) / kWave);
-
-  float lam[4] = {0.f, 0.f, 0.f, 0.f}, g0[4] = {0.f, 0.f, 0.f, 0.f};
-  float nxt[4] = {s[0], s[1], s[2], s[3]};
-  for (int k = H - 1; k >= 0; --k) {
-    float a[1], pre[4];
-    load_seq<LAYOUT, 1>(A.actions, A.B, H, 1, bb, k, 0, a);
-    const float f = k < H - 1 ? (float)(1.0 - inv * (double)k) : 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      pre[i] = ST(k, i);
-      float seed = 2.f * wq[i] * (nxt[i] - s0[i] * f);
-      lam[i] += seed;
-      g0[i] -= seed * f;  // gradient through make_reference
-    }
-    float tmp[4] = {pre[0], pre[1], pre[2], pre[3]};
-    CartAux x = cart_step(tmp, a[0], c);
-    float ga[1] = {cart_step_adjoint(lam, pre[1], pre[3], x, c) +
-                   0.02f * a[0]};
-    if (live) store_seq<LAYOUT, 1>(A.grad_actions, A.B, H, 1, b, k, 0, ga);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) nxt[i] = pre[i];
-  }
-  if (A.grad_state0 && live) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) lam[i] += g0[i];
-    store_state<LAYOUT, 4>(A.grad_state0, A.B, b, lam);
-  }
+  cart_rollout_reverse(
+      H, s0, s, lam, action, ST,
+      [&](float (&l)[4], const float (&pre)[4], float a) {
+        return cart_step_adjoint(l, pre[1], pre[3], cart_step_aux(pre, a, c), c);
+      },
+      [&](int k, float g) {
+        const float ga[1] = {g};
+        if (live) store_seq<LAYOUT, 1>(A.grad_actions, A.B, H, 1, b, k, 0, ga);
+      });
+  if (A.grad_state0 && live) store_state<LAYOUT, 4>(A.grad_state0, A.B, b, lam);
 }
 
 // no-grad unroll (evaluation): states only

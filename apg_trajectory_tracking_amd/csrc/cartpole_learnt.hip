@@ -26,6 +26,7 @@
 
 #include "apg_device.h"
 #include "cartpole_learnt_math.h"
+#include "cartpole_rollout_math.h"
 
 namespace apg {
 namespace {
@@ -37,10 +38,8 @@ constexpr int kStepWaves = kStepBlock / kWave;
 
 // the residual's unit rows into LDS (all threads of the workgroup; barrier)
 __device__ __forceinline__ void stage_residual(float *rows, const ApgCartpoleLearnt &m) {
-  for (int t = threadIdx.x; t < kCartResFloats; t += blockDim.x) {
-    const int u = t / kCartResRow, j = t - u * kCartResRow;
-    rows[t] = j < 5 ? m.w1[u * 5 + j] : j == 5 ? m.b1[u] : m.w2[(j - 6) * kCartResHidden + u];
-  }
+  for (int t = threadIdx.x; t < kCartResFloats; t += blockDim.x)
+    rows[t] = cart_residual_packed(t, m.w1, m.b1, m.w2);
   __syncthreads();
 }
 
@@ -161,76 +160,38 @@ __global__ __launch_bounds__(APG_ROLLOUT_BLOCK) void cart_learnt_rollout_kernel(
   const int bb = live ? b : A.B - 1;
   const CartConst c = make_learnt_const(load_params(A.m), A.dt);
   const int H = A.H;
-  const float wq[4] = {0.f, 3.f, 10.f, 1.f};  // drone_loss.py:136
-  // make_reference: ref_k = s0 * (1 - 1/(H-1) * k), k < H-1; last row zero
-  const double inv = H > 1 ? 1.0 / (double)(H - 1) : 0.0;
+  auto action = [&](int k) {
+    float a[1];
+    load_seq<LAYOUT, 1>(A.actions, A.B, H, 1, bb, k, 0, a);
+    return a[0];
+  };
   auto ST = [&](int k, int i) -> float & {
     return stash[(k * 4 + i) * APG_ROLLOUT_BLOCK + lane];
   };
-  float s0[4], s[4];
+  float s0[4], s[4], lam[4];
   load_state<LAYOUT, 4>(A.state0, A.B, bb, s0);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) s[i] = s0[i];
-  float loss = 0.f;
-  for (int k = 0; k < H; ++k) {
-    float a[1];
-    load_seq<LAYOUT, 1>(A.actions, A.B, H, 1, bb, k, 0, a);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) ST(k, i) = s[i];
-    cart_learnt_step(s, a[0], c, rows);
-    if (A.states_out && live)
-      store_seq<LAYOUT, 4>(A.states_out, A.B, H, 4, b, k, 0, s);
-    const float f = k < H - 1 ? (float)(1.0 - inv * (double)k) : 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float d = s[i] - s0[i] * f;
-      loss += (d * d) * wq[i];
-    }
-    loss += 0.01f * a[0] * a[0];
-  }
+  const float loss = cart_rollout_forward(
+      H, s0, s, action, ST, [&](float (&x)[4], float a) { cart_learnt_step(x, a, c, rows); },
+      [&](int k, const float (&x)[4]) {
+        if (A.states_out && live) store_seq<LAYOUT, 4>(A.states_out, A.B, H, 4, b, k, 0, x);
+      });
   write_wave_partial(A.loss_partials, live ? loss : 0.f, (A.B + kWave - 1) / kWave);
-
-  float lam[4] = {0.f, 0.f, 0.f, 0.f}, g0[4] = {0.f, 0.f, 0.f, 0.f};
-  float nxt[4] = {s[0], s[1], s[2], s[3]};
-  for (int k = H - 1; k >= 0; --k) {
-    float a[1], pre[4];
-    load_seq<LAYOUT, 1>(A.actions, A.B, H, 1, bb, k, 0, a);
-    const float f = k < H - 1 ? (float)(1.0 - inv * (double)k) : 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      pre[i] = ST(k, i);
-      float seed = 2.f * wq[i] * (nxt[i] - s0[i] * f);
-      lam[i] += seed;
-      g0[i] -= seed * f;  // gradient through make_reference
-    }
-    float tmp[4] = {pre[0], pre[1], pre[2], pre[3]};
-    const CartAux x = cart_step(tmp, a[0], c);
-    float ga[1] = {cart_learnt_step_adjoint(lam, pre, a[0], x, c, rows) + 0.02f * a[0]};
-    if (live) store_seq<LAYOUT, 1>(A.grad_actions, A.B, H, 1, b, k, 0, ga);
-    // the state after step k-1 is the state before step k
-#pragma unroll
-    for (int i = 0; i < 4; ++i) nxt[i] = pre[i];
-  }
-  if (A.grad_state0 && live) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) lam[i] += g0[i];
-    store_state<LAYOUT, 4>(A.grad_state0, A.B, b, lam);
-  }
+  cart_rollout_reverse(
+      H, s0, s, lam, action, ST,
+      [&](float (&l)[4], const float (&pre)[4], float a) {
+        return cart_learnt_step_adjoint(l, pre, a, cart_step_aux(pre, a, c), c, rows);
+      },
+      [&](int k, float g) {
+        const float ga[1] = {g};
+        if (live) store_seq<LAYOUT, 1>(A.grad_actions, A.B, H, 1, b, k, 0, ga);
+      });
+  if (A.grad_state0 && live) store_state<LAYOUT, 4>(A.grad_state0, A.B, b, lam);
 }
 
 int check_model(const ApgCartpoleLearnt *m, bool need_residual) {
-  if (!m) { set_error("model is NULL"); return APG_ERR_ARG; }
-  if (!m->max_force_mag || !m->masspole || !m->length || !m->friction || !m->total_mass ||
-      !m->polemass_length) {
-    set_error("a physical parameter pointer is NULL");
-    return APG_ERR_ARG;
-  }
-  const bool any = m->w1 || m->b1 || m->w2, all = m->w1 && m->b1 && m->w2;
-  if (any != all || (need_residual && !all)) {
-    set_error("w1 / b1 / w2 must be all given%s", need_residual ? "" : " or all NULL");
-    return APG_ERR_ARG;
-  }
-  return APG_OK;
+  const char *e = cart_learnt_check(m, need_residual);
+  if (e) set_error("%s", e);
+  return e ? APG_ERR_ARG : APG_OK;
 }
 
 int check_step(const float *state, const float *action, const ApgCartpoleLearnt *m, int B) {

@@ -72,6 +72,30 @@ __host__ __device__ __forceinline__ void cart_param_adjoint(const float (&lam)[4
   g[5] += -2.f * th2 * s * gx + (3.f * c2 * x.thacc - 3.f * th2 * s * c) * gt;
 }
 
+// The pointer rule of ApgCartpoleLearnt, shared by the device entry points and
+// the twins; NULL: fine.  need_residual: w1 / b1 / w2 are all given; otherwise
+// all or none (none: the physics alone).
+inline const char *cart_learnt_check(const ApgCartpoleLearnt *m, bool need_residual) {
+  if (!m) return "model is NULL";
+  if (!m->max_force_mag || !m->masspole || !m->length || !m->friction || !m->total_mass ||
+      !m->polemass_length)
+    return "a physical parameter pointer is NULL";
+  const bool any = m->w1 || m->b1 || m->w2, all = m->w1 && m->b1 && m->w2;
+  if (any != all || (need_residual && !all))
+    return need_residual ? "w1 / b1 / w2 must be all given"
+                         : "w1 / b1 / w2 must be all given or all NULL";
+  return nullptr;
+}
+
+// element t of the packed residual (t < kCartResFloats): unit row t / 10, see
+// below
+__host__ __device__ __forceinline__ float cart_residual_packed(int t, const float *w1,
+                                                               const float *b1,
+                                                               const float *w2) {
+  const int u = t / kCartResRow, j = t - u * kCartResRow;
+  return j < 5 ? w1[u * 5 + j] : j == 5 ? b1[u] : w2[(j - 6) * kCartResHidden + u];
+}
+
 // Residual network on packed unit rows: row m = [W1[m][0..4], b1[m],
 // W2[0..3][m]] (10 floats; `rows` in LDS on the device).  The units
 // [m0, m1) of r = W2 relu(W1 z + b1) are added to out, z = [state; action].

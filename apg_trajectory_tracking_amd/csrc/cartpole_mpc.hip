@@ -7,7 +7,6 @@
 // sweep's stash for the reverse one (12 H) are 140 floats at H = 10 -
 // kernel_resources.json must show no scratch and no spill for every
 // instantiation (tests/test_cartpole_mpc_cpu.py).
-#include "cartpole_learnt_math.h"
 #include "cartpole_mpc_math.h"
 
 namespace apg {
@@ -65,11 +64,8 @@ __global__ __launch_bounds__(kCartMpcThreads) void cart_mpc_closed_loop_kernel(C
   __shared__ float rows[LEARNT ? kCartResFloats : 1];
   CartConst cp = A.cp;
   if constexpr (LEARNT) {
-    for (int t = threadIdx.x; t < kCartResFloats; t += kCartMpcThreads) {
-      const int u = t / kCartResRow, j = t - u * kCartResRow;
-      rows[t] = j < 5 ? A.m.w1[u * 5 + j] : j == 5 ? A.m.b1[u]
-                                                   : A.m.w2[(j - 6) * kCartResHidden + u];
-    }
+    for (int t = threadIdx.x; t < kCartResFloats; t += kCartMpcThreads)
+      rows[t] = cart_residual_packed(t, A.m.w1, A.m.b1, A.m.w2);
     cp = make_learnt_const(CartLearntParams{*A.m.max_force_mag, *A.m.masspole, *A.m.length,
                                             *A.m.friction, *A.m.total_mass,
                                             *A.m.polemass_length},

@@ -40,7 +40,7 @@
 // 5e-4 is a factor 2-4 below the stability limit.
 #pragma once
 #include "cart_flight_rule.h"
-#include "cartpole_math.h"
+#include "cartpole_learnt_math.h"
 
 namespace apg {
 namespace {
@@ -194,11 +194,11 @@ inline const char *cart_mpc_check(const ApgCartpoleParams *model,
   return nullptr;
 }
 
+// the optional learnt plant: NULL is "none", a given one carries its residual
 inline const char *cart_mpc_check_learnt(const ApgCartpoleLearnt *m) {
-  if (m && (!m->max_force_mag || !m->masspole || !m->length || !m->friction ||
-            !m->total_mass || !m->polemass_length || !m->w1 || !m->b1 || !m->w2))
-    return "learnt plant pointer is NULL (the residual must be given)";
-  return nullptr;
+  return m && cart_learnt_check(m, true)
+             ? "learnt plant pointer is NULL (the residual must be given)"
+             : nullptr;
 }
 
 }  // namespace

@@ -4,9 +4,10 @@
 // (hipcc --cuda-host-only) and looped over the batch.  Separate library,
 // separate symbol names, never loaded by the Python package: not a fallback.
 // The compositions (forward sweep, loss terms and their seeds, reverse sweep)
-// follow the rollout kernels of quad.hip / wing.hip / cartpole.hip lane for
-// lane; tests/test_cpu_twins.py pins them to the golden vectors and, on a GPU,
-// to the device entry points.
+// follow the rollout kernels of quad.hip / wing.hip lane for lane; the
+// cart-pole and plain fixed-wing ones are the kernels' own bodies
+// (cartpole_rollout_math.h, wing_rollout_math.h).  tests/test_cpu_twins.py pins
+// them to the golden vectors and, on a GPU, to the device entry points.
 #include <cstdarg>
 #include <cstdio>
 #include <vector>
@@ -17,10 +18,12 @@
 #include "cartpole_learnt_math.h"
 #include "cartpole_math.h"
 #include "cartpole_mpc_math.h"
+#include "cartpole_rollout_math.h"
 #include "quad_math.h"
 #include "quad_mpc_math.h"
 #include "wing_learnt_math.h"
 #include "wing_math.h"
+#include "wing_rollout_math.h"
 
 using namespace apg;
 
@@ -99,6 +102,58 @@ int run_deferred(const ApgDeferredLoss *d) {
   for (int i = 0; i < d->prev_count; ++i) s += d->prev_partials[i];
   *d->prev_loss = s;
   return APG_OK;
+}
+
+// cartpole_rollout_math.h / wing_rollout_math.h looped over the batch, the
+// stash a vector: what the rollout kernels do per lane
+template <class Step, class Adjoint>
+void cart_rollout_batch(const float *state0, const float *actions, int B, int H, const Idx &ix,
+                        LossOut out, float *grad_actions, float *grad_state0,
+                        float *states_out, Step &&step, Adjoint &&adjoint) {
+  std::vector<float> pre((size_t)H * 4);
+  auto ST = [&](int k, int i) -> float & { return pre[k * 4 + i]; };
+  for (int b = 0; b < B; ++b) {
+    auto action = [&](int k) { return actions[ix.seq(b, k, 0, H, 1)]; };
+    auto emit_state = [&](int k, const float (&x)[4]) {
+      for (int i = 0; states_out && i < 4; ++i) states_out[ix.seq(b, k, i, H, 4)] = x[i];
+    };
+    auto emit_grad = [&](int k, float g) { grad_actions[ix.seq(b, k, 0, H, 1)] = g; };
+    float s0[4], s[4], lam[4];
+    for (int i = 0; i < 4; ++i) s0[i] = state0[ix.vec(b, i, 4)];
+    out.add(b, B, cart_rollout_forward(H, s0, s, action, ST, step, emit_state));
+    cart_rollout_reverse(H, s0, s, lam, action, ST, adjoint, emit_grad);
+    for (int i = 0; grad_state0 && i < 4; ++i) grad_state0[ix.vec(b, i, 4)] = lam[i];
+  }
+  out.finish(B);
+}
+
+template <class Step, class Adjoint>
+void wing_rollout_batch(const float *state0, const float *actions, const float *ref,
+                        const ApgWingLossWeights &w, int B, int H, const Idx &ix, LossOut out,
+                        float *grad_actions, float *grad_state0, float *states_out,
+                        Step &&step, Adjoint &&adjoint) {
+  std::vector<float> pre((size_t)H * 12);
+  auto ST = [&](int k, int i) -> float & { return pre[k * 12 + i]; };
+  for (int b = 0; b < B; ++b) {
+    auto action = [&](int k, float (&a)[4]) {
+      for (int j = 0; j < 4; ++j) a[j] = actions[ix.seq(b, k, j, H, 4)];
+    };
+    auto rf = [&](int k, float (&rp)[3]) {
+      for (int i = 0; i < 3; ++i) rp[i] = ref[ix.seq(b, k, i, H, 3)];
+    };
+    auto emit_state = [&](int k, const float (&x)[12]) {
+      for (int i = 0; states_out && i < 12; ++i) states_out[ix.seq(b, k, i, H, 12)] = x[i];
+    };
+    auto emit_grad = [&](int k, const float (&ga)[4]) {
+      for (int j = 0; j < 4; ++j) grad_actions[ix.seq(b, k, j, H, 4)] = ga[j];
+    };
+    float s[12], lam[12];
+    for (int i = 0; i < 12; ++i) s[i] = state0[ix.vec(b, i, 12)];
+    out.add(b, B, wing_rollout_forward(H, s, w.pos, w.action, action, rf, ST, step, emit_state));
+    wing_rollout_reverse(H, s, lam, w.pos, w.action, action, rf, ST, adjoint, emit_grad);
+    for (int i = 0; grad_state0 && i < 12; ++i) grad_state0[ix.vec(b, i, 12)] = lam[i];
+  }
+  out.finish(B);
 }
 
 }  // namespace
@@ -310,49 +365,16 @@ int apg_wing_rollout_fwd_bwd_cpu(const float *state0, const float *actions,
   if (!ref || !loss_partials || !grad_actions)
     return fail("ref / loss_partials / grad_actions must not be NULL");
   const WingConst k = make_const(*params, dt);
-  const ApgWingLossWeights &w = *weights;
   const Idx ix{layout, (size_t)B};
-  LossOut out{loss_partials, loss};
-  std::vector<float> pre((size_t)H * 12), st((size_t)H * 12);
-  for (int b = 0; b < B; ++b) {
-    float s[12];
-    for (int i = 0; i < 12; ++i) s[i] = state0[ix.vec(b, i, 12)];
-    for (int n = 0; n < H; ++n) {
-      for (int i = 0; i < 12; ++i) pre[n * 12 + i] = s[i];
-      float a[4];
-      for (int j = 0; j < 4; ++j) a[j] = actions[ix.seq(b, n, j, H, 4)];
-      wing_step(s, a, k);
-      for (int i = 0; i < 12; ++i) st[n * 12 + i] = s[i];
-      if (states_out)
-        for (int i = 0; i < 12; ++i) states_out[ix.seq(b, n, i, H, 12)] = s[i];
-    }
-    // fixed_wing_mpc_loss (neural_control/drone_loss.py:72-82) with its seeds
-    float lam[12] = {0.f}, l = 0.f;
-    for (int n = H - 1; n >= 0; --n) {
-      float a[4], ga[4] = {0.f, 0.f, 0.f, 0.f}, lp = 0.f, la = 0.f, sp[12], sd[12];
-      for (int j = 0; j < 4; ++j) a[j] = actions[ix.seq(b, n, j, H, 4)];
-      for (int i = 0; i < 12; ++i) sp[i] = pre[n * 12 + i];
-      for (int i = 0; i < 3; ++i) {
-        const float dp = st[n * 12 + i] - ref[ix.seq(b, n, i, H, 3)];
-        lp += dp * dp;
-        lam[i] += 2.f * w.pos * dp;
-      }
-      for (int j = 1; j < 4; ++j) {
-        const float d = a[j] - 0.5f;
-        la += d * d;
-        ga[j] = 2.f * w.action * d;
-      }
-      l += w.pos * lp + w.action * la;
-      WingAux x;
-      wing_rates(sp, a, k, x, sd);
-      wing_step_adjoint(lam, ga, sp, x, sd, k);
-      for (int j = 0; j < 4; ++j) grad_actions[ix.seq(b, n, j, H, 4)] = ga[j];
-    }
-    if (grad_state0)
-      for (int i = 0; i < 12; ++i) grad_state0[ix.vec(b, i, 12)] = lam[i];
-    out.add(b, B, l);
-  }
-  out.finish(B);
+  wing_rollout_batch(
+      state0, actions, ref, *weights, B, H, ix, LossOut{loss_partials, loss}, grad_actions,
+      grad_state0, states_out, [&](float (&s)[12], const float (&a)[4]) { wing_step(s, a, k); },
+      [&](float (&lam)[12], float (&ga)[4], const float (&pre)[12], const float (&a)[4]) {
+        WingAux x;
+        float sd[12];
+        wing_rates(pre, a, k, x, sd);
+        wing_step_adjoint(lam, ga, pre, x, sd, k);
+      });
   return APG_OK;
 }
 
@@ -432,48 +454,12 @@ int apg_cartpole_rollout_fwd_bwd_cpu(const float *state0, const float *actions,
     return fail("loss_partials / grad_actions must not be NULL");
   const CartConst c = make_const(*params, dt);
   const Idx ix{layout, (size_t)B};
-  // cartpole_loss_mpc (neural_control/drone_loss.py:136-145) against
-  // make_reference (scripts/train_cartpole.py:103-110): the initial state
-  // fading linearly to zero over the horizon; the gradient flows through it
-  const float wq[4] = {0.f, 3.f, 10.f, 1.f};
-  const double inv = H > 1 ? 1.0 / (double)(H - 1) : 0.0;
-  LossOut out{loss_partials, loss};
-  std::vector<float> pre((size_t)H * 4), st((size_t)H * 4);
-  for (int b = 0; b < B; ++b) {
-    float s0[4], s[4], l = 0.f;
-    for (int i = 0; i < 4; ++i) s0[i] = s[i] = state0[ix.vec(b, i, 4)];
-    for (int k = 0; k < H; ++k) {
-      const float a = actions[ix.seq(b, k, 0, H, 1)];
-      for (int i = 0; i < 4; ++i) pre[k * 4 + i] = s[i];
-      cart_step(s, a, c);
-      const float f = k < H - 1 ? (float)(1.0 - inv * (double)k) : 0.f;
-      for (int i = 0; i < 4; ++i) {
-        st[k * 4 + i] = s[i];
-        if (states_out) states_out[ix.seq(b, k, i, H, 4)] = s[i];
-        const float d = s[i] - s0[i] * f;
-        l += (d * d) * wq[i];
-      }
-      l += 0.01f * a * a;
-    }
-    float lam[4] = {0.f, 0.f, 0.f, 0.f}, g0[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int k = H - 1; k >= 0; --k) {
-      const float a = actions[ix.seq(b, k, 0, H, 1)];
-      const float f = k < H - 1 ? (float)(1.0 - inv * (double)k) : 0.f;
-      for (int i = 0; i < 4; ++i) {
-        const float seed = 2.f * wq[i] * (st[k * 4 + i] - s0[i] * f);
-        lam[i] += seed;
-        g0[i] -= seed * f;
-      }
-      float tmp[4] = {pre[k * 4], pre[k * 4 + 1], pre[k * 4 + 2], pre[k * 4 + 3]};
-      const CartAux x = cart_step(tmp, a, c);
-      grad_actions[ix.seq(b, k, 0, H, 1)] =
-          cart_step_adjoint(lam, pre[k * 4 + 1], pre[k * 4 + 3], x, c) + 0.02f * a;
-    }
-    if (grad_state0)
-      for (int i = 0; i < 4; ++i) grad_state0[ix.vec(b, i, 4)] = lam[i] + g0[i];
-    out.add(b, B, l);
-  }
-  out.finish(B);
+  cart_rollout_batch(
+      state0, actions, B, H, ix, LossOut{loss_partials, loss}, grad_actions, grad_state0,
+      states_out, [&](float (&s)[4], float a) { cart_step(s, a, c); },
+      [&](float (&lam)[4], const float (&pre)[4], float a) {
+        return cart_step_adjoint(lam, pre[1], pre[3], cart_step_aux(pre, a, c), c);
+      });
   return APG_OK;
 }
 
@@ -511,22 +497,13 @@ bool learnt_setup(const ApgCartpoleLearnt &m, float dt, CartLearntParams &p, Car
   c = make_learnt_const(p, dt);
   if (!m.w1) return false;
   rows.resize(kCartResFloats);
-  for (int t = 0; t < kCartResFloats; ++t) {
-    const int u = t / kCartResRow, j = t - u * kCartResRow;
-    rows[t] = j < 5 ? m.w1[u * 5 + j] : j == 5 ? m.b1[u] : m.w2[(j - 6) * kCartResHidden + u];
-  }
+  for (int t = 0; t < kCartResFloats; ++t) rows[t] = cart_residual_packed(t, m.w1, m.b1, m.w2);
   return true;
 }
 
 int check_learnt(const ApgCartpoleLearnt *m, int B, bool need_residual) {
   if (B < 0) return fail("B must be >= 0 (got %d)", B);
-  if (!m) return fail("model is NULL");
-  if (!m->max_force_mag || !m->masspole || !m->length || !m->friction || !m->total_mass ||
-      !m->polemass_length)
-    return fail("a physical parameter pointer is NULL");
-  const bool any = m->w1 || m->b1 || m->w2, all = m->w1 && m->b1 && m->w2;
-  if (any != all || (need_residual && !all))
-    return fail("w1 / b1 / w2 must be all given%s", need_residual ? "" : " or all NULL");
+  if (const char *e = cart_learnt_check(m, need_residual)) return fail("%s", e);
   return APG_OK;
 }
 
@@ -615,47 +592,12 @@ int apg_cartpole_learnt_rollout_fwd_bwd_cpu(const float *state0, const float *ac
   std::vector<float> rows;
   learnt_setup(*model, dt, p, c, rows);
   const Idx ix{layout, (size_t)B};
-  // as apg_cartpole_rollout_fwd_bwd_cpu, each step the learnt one
-  const float wq[4] = {0.f, 3.f, 10.f, 1.f};
-  const double inv = H > 1 ? 1.0 / (double)(H - 1) : 0.0;
-  LossOut out{loss_partials, loss};
-  std::vector<float> pre((size_t)H * 4), st((size_t)H * 4);
-  for (int b = 0; b < B; ++b) {
-    float s0[4], s[4], l = 0.f;
-    for (int i = 0; i < 4; ++i) s0[i] = s[i] = state0[ix.vec(b, i, 4)];
-    for (int k = 0; k < H; ++k) {
-      const float a = actions[ix.seq(b, k, 0, H, 1)];
-      for (int i = 0; i < 4; ++i) pre[k * 4 + i] = s[i];
-      cart_learnt_step(s, a, c, rows.data());
-      const float f = k < H - 1 ? (float)(1.0 - inv * (double)k) : 0.f;
-      for (int i = 0; i < 4; ++i) {
-        st[k * 4 + i] = s[i];
-        if (states_out) states_out[ix.seq(b, k, i, H, 4)] = s[i];
-        const float d = s[i] - s0[i] * f;
-        l += (d * d) * wq[i];
-      }
-      l += 0.01f * a * a;
-    }
-    float lam[4] = {0.f, 0.f, 0.f, 0.f}, g0[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int k = H - 1; k >= 0; --k) {
-      const float a = actions[ix.seq(b, k, 0, H, 1)];
-      const float f = k < H - 1 ? (float)(1.0 - inv * (double)k) : 0.f;
-      for (int i = 0; i < 4; ++i) {
-        const float seed = 2.f * wq[i] * (st[k * 4 + i] - s0[i] * f);
-        lam[i] += seed;
-        g0[i] -= seed * f;
-      }
-      const float pk[4] = {pre[k * 4], pre[k * 4 + 1], pre[k * 4 + 2], pre[k * 4 + 3]};
-      float tmp[4] = {pk[0], pk[1], pk[2], pk[3]};
-      const CartAux x = cart_step(tmp, a, c);
-      grad_actions[ix.seq(b, k, 0, H, 1)] =
-          cart_learnt_step_adjoint(lam, pk, a, x, c, rows.data()) + 0.02f * a;
-    }
-    if (grad_state0)
-      for (int i = 0; i < 4; ++i) grad_state0[ix.vec(b, i, 4)] = lam[i] + g0[i];
-    out.add(b, B, l);
-  }
-  out.finish(B);
+  cart_rollout_batch(
+      state0, actions, B, H, ix, LossOut{loss_partials, loss}, grad_actions, grad_state0,
+      states_out, [&](float (&s)[4], float a) { cart_learnt_step(s, a, c, rows.data()); },
+      [&](float (&lam)[4], const float (&pre)[4], float a) {
+        return cart_learnt_step_adjoint(lam, pre, a, cart_step_aux(pre, a, c), c, rows.data());
+      });
   return APG_OK;
 }
 
@@ -692,44 +634,14 @@ int apg_wing_learnt_rollout_fwd_bwd_cpu(const float *state0, const float *action
   for (int t = 0; t < kWingResFloats; ++t)
     rows[t] = wing_residual_packed(t, model->w1, model->b1, model->w2, model->b2);
   const float *rw = rows.data();
-  const ApgWingLossWeights &w = *weights;
   const Idx ix{layout, (size_t)B};
-  LossOut out{loss_partials, loss};
-  std::vector<float> pre((size_t)H * 12);
-  for (int b = 0; b < B; ++b) {
-    float s[12], l = 0.f;
-    for (int i = 0; i < 12; ++i) s[i] = state0[ix.vec(b, i, 12)];
-    for (int n = 0; n < H; ++n) {
-      float a[4], lp = 0.f, la = 0.f;
-      for (int j = 0; j < 4; ++j) a[j] = actions[ix.seq(b, n, j, H, 4)];
-      for (int i = 0; i < 12; ++i) pre[n * 12 + i] = s[i];
-      wing_learnt_step(s, a, k, rw);
-      if (states_out)
-        for (int i = 0; i < 12; ++i) states_out[ix.seq(b, n, i, H, 12)] = s[i];
-      for (int i = 0; i < 3; ++i) {
-        const float dp = s[i] - ref[ix.seq(b, n, i, H, 3)], d = a[1 + i] - 0.5f;
-        lp += dp * dp, la += d * d;
-      }
-      l += w.pos * lp + w.action * la;
-    }
-    float lam[12] = {0.f}, nxt[3] = {s[0], s[1], s[2]};
-    for (int n = H - 1; n >= 0; --n) {
-      float a[4], sp[12];
-      for (int j = 0; j < 4; ++j) a[j] = actions[ix.seq(b, n, j, H, 4)];
-      for (int i = 0; i < 12; ++i) sp[i] = pre[n * 12 + i];
-      for (int i = 0; i < 3; ++i)
-        lam[i] += 2.f * w.pos * (nxt[i] - ref[ix.seq(b, n, i, H, 3)]);
-      float ga[4] = {0.f, 2.f * w.action * (a[1] - 0.5f), 2.f * w.action * (a[2] - 0.5f),
-                     2.f * w.action * (a[3] - 0.5f)};
-      wing_learnt_step_adjoint(lam, ga, sp, a, k, rw);
-      for (int j = 0; j < 4; ++j) grad_actions[ix.seq(b, n, j, H, 4)] = ga[j];
-      for (int i = 0; i < 3; ++i) nxt[i] = sp[i];
-    }
-    if (grad_state0)
-      for (int i = 0; i < 12; ++i) grad_state0[ix.vec(b, i, 12)] = lam[i];
-    out.add(b, B, l);
-  }
-  out.finish(B);
+  wing_rollout_batch(
+      state0, actions, ref, *weights, B, H, ix, LossOut{loss_partials, loss}, grad_actions,
+      grad_state0, states_out,
+      [&](float (&s)[12], const float (&a)[4]) { wing_learnt_step(s, a, k, rw); },
+      [&](float (&lam)[12], float (&ga)[4], const float (&pre)[12], const float (&a)[4]) {
+        wing_learnt_step_adjoint(lam, ga, pre, a, k, rw);
+      });
   return APG_OK;
 }
 

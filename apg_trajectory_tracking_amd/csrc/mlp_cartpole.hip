@@ -190,11 +190,8 @@ __global__ __launch_bounds__(kMaxWaves * 64) void cart_closed_loop_kernel(
   CartConst cc = A.c;
   if constexpr (LEARNT) {
     float *rows = lds + kCartLds;
-    for (int t = threadIdx.x; t < kCartResFloats; t += blockDim.x) {
-      const int u = t / kCartResRow, j = t - u * kCartResRow;
-      rows[t] = j < 5 ? A.m.w1[u * 5 + j] : j == 5 ? A.m.b1[u]
-                                                   : A.m.w2[(j - 6) * kCartResHidden + u];
-    }
+    for (int t = threadIdx.x; t < kCartResFloats; t += blockDim.x)
+      rows[t] = cart_residual_packed(t, A.m.w1, A.m.b1, A.m.w2);
     cc = make_learnt_const(CartLearntParams{*A.m.max_force_mag, *A.m.masspole, *A.m.length,
                                             *A.m.friction, *A.m.total_mass,
                                             *A.m.polemass_length},
@@ -292,9 +289,7 @@ int closed_loop(const float *state0, float dt, const ApgCartpoleParams *params,
     set_error("%s / policy is NULL", learnt ? "model" : "params");
     return APG_ERR_ARG;
   }
-  if (learnt && (!learnt->max_force_mag || !learnt->masspole || !learnt->length ||
-                 !learnt->friction || !learnt->total_mass || !learnt->polemass_length ||
-                 !learnt->w1 || !learnt->b1 || !learnt->w2)) {
+  if (learnt && cart_learnt_check(learnt, true)) {
     set_error("learnt model pointer is NULL");
     return APG_ERR_ARG;
   }

@@ -48,6 +48,7 @@
 
 #include "apg_device.h"
 #include "wing_learnt_math.h"
+#include "wing_rollout_math.h"
 
 namespace apg {
 namespace {
@@ -131,6 +132,7 @@ __global__ __launch_bounds__(256) void wing_learnt_rollout_pack_kernel(ApgWingLe
     pack[kWingLearntTableFloats + t] = wing_residual_packed(t, m.w1, m.b1, m.w2, m.b2);
 }
 
+// wing_rollout_math.h through the learnt step
 template <int LAYOUT>
 __global__ __launch_bounds__(kWave) void wing_learnt_rollout_kernel(WingLearntRolloutArgs A) {
   extern __shared__ float stash[];
@@ -145,53 +147,34 @@ __global__ __launch_bounds__(kWave) void wing_learnt_rollout_kernel(WingLearntRo
   WingGeneralConstK *kp = (WingGeneralConstK *)A.pack;
   cfloat_ptr rows = (cfloat_ptr)(A.pack + kWingLearntTableFloats);
 #define APG_LAUNDER(p) asm volatile("" : "+s"(p))
-  const float w_pos = A.w.pos, w_act = A.w.action;
+  auto action = [&](int k, float (&a)[4]) {
+    load_seq<LAYOUT, 4>(A.actions, A.B, H, 4, bb, k, 0, a);
+  };
+  auto ref = [&](int k, float (&rp)[3]) { load_seq<LAYOUT, 3>(A.ref, A.B, H, 3, bb, k, 0, rp); };
   auto ST = [&](int k, int i) -> float & { return stash[(k * 12 + i) * kWave + lane]; };
-  float s[12];
+  float s[12], lam[12];
   load_state<LAYOUT, 12>(A.state0, A.B, bb, s);
-  float loss = 0.f;
-  for (int k = 0; k < H; ++k) {
-    float a[4], rp[3];
-    load_seq<LAYOUT, 4>(A.actions, A.B, H, 4, bb, k, 0, a);
-    load_seq<LAYOUT, 3>(A.ref, A.B, H, 3, bb, k, 0, rp);
-#pragma unroll
-    for (int i = 0; i < 12; ++i) ST(k, i) = s[i];
-    APG_LAUNDER(kp);
-    APG_LAUNDER(rows);
-    wing_learnt_step(s, a, *kp, rows);
-    if (A.states_out && live) store_seq<LAYOUT, 12>(A.states_out, A.B, H, 12, b, k, 0, s);
-    float lp = 0.f, la = 0.f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const float dp = s[i] - rp[i], d = a[1 + i] - 0.5f;
-      lp += dp * dp, la += d * d;
-    }
-    loss += w_pos * lp + w_act * la;
-  }
+  const float loss = wing_rollout_forward(
+      H, s, A.w.pos, A.w.action, action, ref, ST,
+      [&](float (&x)[12], const float (&a)[4]) {
+        APG_LAUNDER(kp);
+        APG_LAUNDER(rows);
+        wing_learnt_step(x, a, *kp, rows);
+      },
+      [&](int k, const float (&x)[12]) {
+        if (A.states_out && live) store_seq<LAYOUT, 12>(A.states_out, A.B, H, 12, b, k, 0, x);
+      });
   write_wave_partial(A.loss_partials, live ? loss : 0.f, (A.B + kWave - 1) / kWave);
-
-  float lam[12];
-#pragma unroll
-  for (int i = 0; i < 12; ++i) lam[i] = 0.f;
-  float nxt[3] = {s[0], s[1], s[2]};   // position after step k
-  for (int k = H - 1; k >= 0; --k) {
-    float a[4], rp[3], pre[12];
-    load_seq<LAYOUT, 4>(A.actions, A.B, H, 4, bb, k, 0, a);
-    load_seq<LAYOUT, 3>(A.ref, A.B, H, 3, bb, k, 0, rp);
-#pragma unroll
-    for (int i = 0; i < 12; ++i) pre[i] = ST(k, i);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) lam[i] += 2.f * w_pos * (nxt[i] - rp[i]);
-    float ga[4] = {0.f, 2.f * w_act * (a[1] - 0.5f), 2.f * w_act * (a[2] - 0.5f),
-                   2.f * w_act * (a[3] - 0.5f)};
-    APG_LAUNDER(kp);
-    APG_LAUNDER(rows);
-    wing_learnt_step_adjoint(lam, ga, pre, a, *kp, rows);
-    if (live) store_seq<LAYOUT, 4>(A.grad_actions, A.B, H, 4, b, k, 0, ga);
-    // the state after step k - 1 is the state before step k
-#pragma unroll
-    for (int i = 0; i < 3; ++i) nxt[i] = pre[i];
-  }
+  wing_rollout_reverse(
+      H, s, lam, A.w.pos, A.w.action, action, ref, ST,
+      [&](float (&l)[12], float (&ga)[4], const float (&pre)[12], const float (&a)[4]) {
+        APG_LAUNDER(kp);
+        APG_LAUNDER(rows);
+        wing_learnt_step_adjoint(l, ga, pre, a, *kp, rows);
+      },
+      [&](int k, const float (&ga)[4]) {
+        if (live) store_seq<LAYOUT, 4>(A.grad_actions, A.B, H, 4, b, k, 0, ga);
+      });
   if (A.grad_state0 && live) store_state<LAYOUT, 12>(A.grad_state0, A.B, b, lam);
 #undef APG_LAUNDER
 }

@@ -162,6 +162,62 @@ def _states_shape(B, H, S, lay):
     return (H, S, B)
 
 
+def _rollout_shape(state0, actions, lay, A, ref=None, ref_cols=None):
+    """-> (B, H, columns of ref) of a fused rollout's inputs: actions
+    [B, H, A], state0 of the same batch and, if given, ref [B, H, ref_cols]
+    (ref_cols None: any) in the layout `lay`."""
+    B, H, a_cols = _seq_shape(actions, lay)
+    Br, Hr, C = (B, H, ref_cols) if ref is None else _seq_shape(ref, lay)
+    if (a_cols != A or (ref_cols is not None and C != ref_cols)
+            or _state_batch(state0, lay) != B or (Br, Hr) != (B, H)):
+        raise ValueError("inconsistent rollout shapes")
+    return B, H, C
+
+
+def _rollout_outs(out, state0, actions, B, H, S, lay, want_grad_state0,
+                  want_states, want_loss=True):
+    """The output tensors of a fused rollout under the keys it returns them
+    by: taken from `out` where it carries one, allocated otherwise, None where
+    not wanted.  `states` has the layout's shape (packed: the quadrotor only)."""
+    out = out or {}
+
+    def get(key, shape, wanted=True):
+        if not wanted:
+            return None
+        t = out.get(key)
+        if t is None:
+            t = torch.empty(shape, dtype=torch.float32, device=state0.device)
+        return t
+    return dict(
+        loss=get("loss", (1,), want_loss),
+        loss_partials=get("loss_partials", (_capi.loss_partials_count(B),)),
+        grad_actions=get("grad_actions", actions.shape),
+        grad_state0=get("grad_state0", state0.shape, want_grad_state0),
+        states=get("states", _states_shape(B, H, S, lay), want_states),
+    )
+
+
+class _RolloutLoss(torch.autograd.Function):
+    """loss = mpc_loss(unroll(dyn, state0, action_seq), ...) as ONE fused
+    rollout: `run(state0, action_seq, want_grad_state0)` is the system's
+    *_rollout_fwd_bwd with everything else bound.  The gradients w.r.t.
+    action_seq / state0 are produced by the same launch and handed to autograd
+    in backward(); nothing else is differentiated."""
+
+    @staticmethod
+    def forward(ctx, state0, action_seq, run):
+        res = run(_f32c(state0), _f32c(action_seq), ctx.needs_input_grad[0])
+        ctx.save_for_backward(res["grad_actions"], res["grad_state0"])
+        return res["loss"].reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        ga, gs = ctx.saved_tensors
+        ga = ga * g if ctx.needs_input_grad[1] else None
+        gs = gs * g if (gs is not None and ctx.needs_input_grad[0]) else None
+        return gs, ga, None
+
+
 def quad_rollout_fwd_bwd(state0, actions, ref, dt, params, weights=None,
                          layout="aos", want_grad_state0=True,
                          want_states=False, want_loss=True, out=None):
@@ -174,32 +230,16 @@ def quad_rollout_fwd_bwd(state0, actions, ref, dt, params, weights=None,
     lay = _layout(layout)
     weights = weights or quad_loss_weights()
     require_device(state0, actions, ref)
-    B, H, A = _seq_shape(actions, lay)
-    Br, Hr, ref_cols = _seq_shape(ref, lay)
-    if A != 4 or _state_batch(state0, lay) != B or Br != B or Hr != H:
-        raise ValueError("inconsistent rollout shapes")
-    out = dict(out or {})
-    dev = state0.device
-
-    def get(key, shape, wanted=True):
-        if not wanted:
-            return None
-        t = out.get(key)
-        if t is None:
-            t = torch.empty(shape, dtype=torch.float32, device=dev)
-        return t
-    partials = get("loss_partials", (_capi.loss_partials_count(B),))
-    loss = get("loss", (1,), want_loss)
-    ga = get("grad_actions", actions.shape)
-    gs = get("grad_state0", state0.shape, want_grad_state0)
-    states = get("states", _states_shape(B, H, 12, lay), want_states)
+    B, H, ref_cols = _rollout_shape(state0, actions, lay, 4, ref)
+    o = _rollout_outs(out, state0, actions, B, H, 12, lay, want_grad_state0,
+                      want_states, want_loss)
     check(lib().apg_quad_rollout_fwd_bwd(
         ptr(state0), ptr(actions), ptr(ref), ref_cols, float(dt),
-        ctypes.byref(params), ctypes.byref(weights), B, H, lay, ptr(partials),
-        ptr(loss), ptr(ga), ptr(gs), ptr(states), None, stream_of(state0)),
+        ctypes.byref(params), ctypes.byref(weights), B, H, lay,
+        ptr(o["loss_partials"]), ptr(o["loss"]), ptr(o["grad_actions"]),
+        ptr(o["grad_state0"]), ptr(o["states"]), None, stream_of(state0)),
         "apg_quad_rollout_fwd_bwd")
-    return dict(loss=loss, loss_partials=partials, grad_actions=ga,
-                grad_state0=gs, states=states)
+    return o
 
 
 def quad_rollout_fwd(state0, actions, dt, params, layout="aos"):
@@ -214,32 +254,14 @@ def quad_rollout_fwd(state0, actions, dt, params, layout="aos"):
     return states
 
 
-class _QuadRolloutLoss(torch.autograd.Function):
-    """loss = quad_mpc_loss(unroll(dyn, state0, action_seq), ref, action_seq)
-    as ONE kernel; the gradients w.r.t. action_seq / state0 are produced by
-    the same launch and handed to autograd in backward()."""
-
-    @staticmethod
-    def forward(ctx, state0, action_seq, ref, dt, params, weights, layout):
-        s, a, r = _f32c(state0), _f32c(action_seq), _f32c(ref)
-        res = quad_rollout_fwd_bwd(
-            s, a, r, dt, params, weights, layout=layout,
-            want_grad_state0=ctx.needs_input_grad[0])
-        ctx.save_for_backward(res["grad_actions"], res["grad_state0"])
-        return res["loss"].reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        ga, gs = ctx.saved_tensors
-        ga = ga * g if ctx.needs_input_grad[1] else None
-        gs = gs * g if (gs is not None and ctx.needs_input_grad[0]) else None
-        return gs, ga, None, None, None, None, None
-
-
 def quad_rollout_loss(state0, action_seq, ref, dt, params, weights=None,
                       layout="aos"):
-    return _QuadRolloutLoss.apply(state0, action_seq, ref, dt, params,
-                                  weights or quad_loss_weights(), layout)
+    """loss = quad_mpc_loss(unroll(dyn, state0, action_seq), ref, action_seq)
+    as ONE kernel (_RolloutLoss)."""
+    return _RolloutLoss.apply(
+        state0, action_seq, lambda s, a, want: quad_rollout_fwd_bwd(
+            s, a, _f32c(ref), dt, params, weights, layout=layout,
+            want_grad_state0=want))
 
 
 # ------------------------------------------------------------ quad loss
@@ -269,57 +291,25 @@ def quad_learnt_rollout_fwd_bwd(dyn, state0, actions, ref, dt, weights=None,
         raise ValueError("the learnt-dynamics rollout takes 'aos' or 'soa' tensors")
     weights = weights or quad_loss_weights()
     require_device(state0, actions, ref)
-    B, H, A = _seq_shape(actions, lay)
-    Br, Hr, ref_cols = _seq_shape(ref, lay)
-    if A != 4 or _state_batch(state0, lay) != B or Br != B or Hr != H:
-        raise ValueError("inconsistent rollout shapes")
-    out = dict(out or {})
-    dev = state0.device
-
-    def get(key, shape, wanted=True):
-        if not wanted:
-            return None
-        t = out.get(key)
-        return t if t is not None else torch.empty(shape, dtype=torch.float32,
-                                                   device=dev)
-    partials = get("loss_partials", (_capi.loss_partials_count(B),))
-    loss = get("loss", (1,))
-    ga = get("grad_actions", actions.shape)
-    gs = get("grad_state0", state0.shape, want_grad_state0)
-    states = get("states", _states_shape(B, H, 12, lay), want_states)
+    B, H, ref_cols = _rollout_shape(state0, actions, lay, 4, ref)
+    o = _rollout_outs(out, state0, actions, B, H, 12, lay, want_grad_state0,
+                      want_states)
     model = _learnt_model(dyn)
     check(lib().apg_quad_learnt_rollout_fwd_bwd(
         ptr(state0), ptr(actions), ptr(ref), ref_cols, float(dt),
         ctypes.byref(dyn.params), ctypes.byref(model), ctypes.byref(weights), B, H,
-        lay, ptr(partials), ptr(loss), ptr(ga), ptr(gs), ptr(states),
-        stream_of(state0)), "apg_quad_learnt_rollout_fwd_bwd")
-    return dict(loss=loss, loss_partials=partials, grad_actions=ga,
-                grad_state0=gs, states=states)
-
-
-class _QuadLearntRolloutLoss(torch.autograd.Function):
-    """loss = quad_mpc_loss(unroll(learnt_dyn, state0, action_seq), ref,
-    action_seq) as ONE kernel; gradients w.r.t. action_seq / state0 only."""
-
-    @staticmethod
-    def forward(ctx, state0, action_seq, ref, dt, dyn, weights):
-        s, a, r = _f32c(state0), _f32c(action_seq), _f32c(ref)
-        res = quad_learnt_rollout_fwd_bwd(
-            dyn, s, a, r, dt, weights, want_grad_state0=ctx.needs_input_grad[0])
-        ctx.save_for_backward(res["grad_actions"], res["grad_state0"])
-        return res["loss"].reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        ga, gs = ctx.saved_tensors
-        ga = ga * g if ctx.needs_input_grad[1] else None
-        gs = gs * g if (gs is not None and ctx.needs_input_grad[0]) else None
-        return gs, ga, None, None, None, None
+        lay, ptr(o["loss_partials"]), ptr(o["loss"]), ptr(o["grad_actions"]),
+        ptr(o["grad_state0"]), ptr(o["states"]), stream_of(state0)),
+        "apg_quad_learnt_rollout_fwd_bwd")
+    return o
 
 
 def quad_learnt_rollout_loss(dyn, state0, action_seq, ref, dt, weights=None):
-    return _QuadLearntRolloutLoss.apply(state0, action_seq, ref, dt, dyn,
-                                        weights or quad_loss_weights())
+    """loss = quad_mpc_loss(unroll(learnt_dyn, state0, action_seq), ref,
+    action_seq) as ONE kernel; gradients w.r.t. action_seq / state0 only."""
+    return _RolloutLoss.apply(
+        state0, action_seq, lambda s, a, want: quad_learnt_rollout_fwd_bwd(
+            dyn, s, a, _f32c(ref), dt, weights, want_grad_state0=want))
 
 
 class _QuadLoss(torch.autograd.Function):
@@ -383,27 +373,6 @@ def quad_features(state):
 
 
 # ------------------------------------------------------------ fixed wing
-def _alloc_outs(out, dev, B, H, S, A, lay, state0, actions, want_grad_state0,
-                want_states, want_loss):
-    out = dict(out or {})
-
-    def get(key, shape, wanted=True):
-        if not wanted:
-            return None
-        t = out.get(key)
-        if t is None:
-            t = torch.empty(shape, dtype=torch.float32, device=dev)
-        return t
-    return dict(
-        loss_partials=get("loss_partials", (_capi.loss_partials_count(B),)),
-        loss=get("loss", (1,), want_loss),
-        grad_actions=get("grad_actions", actions.shape),
-        grad_state0=get("grad_state0", state0.shape, want_grad_state0),
-        states=get("states", (B, H, S) if lay == LAYOUT_AOS else (H, S, B),
-                   want_states),
-    )
-
-
 def wing_rollout_fwd_bwd(state0, actions, ref, dt, params, weights=None,
                          layout="aos", want_grad_state0=True,
                          want_states=False, want_loss=True, out=None):
@@ -412,12 +381,9 @@ def wing_rollout_fwd_bwd(state0, actions, ref, dt, params, weights=None,
     lay = _layout(layout)
     weights = weights or wing_loss_weights()
     require_device(state0, actions, ref)
-    B, H, A = _seq_shape(actions, lay)
-    Br, Hr, C = _seq_shape(ref, lay)
-    if A != 4 or C != 3 or _state_batch(state0, lay) != B or (Br, Hr) != (B, H):
-        raise ValueError("inconsistent rollout shapes")
-    o = _alloc_outs(out, state0.device, B, H, 12, 4, lay, state0, actions,
-                    want_grad_state0, want_states, want_loss)
+    B, H, _ = _rollout_shape(state0, actions, lay, 4, ref, 3)
+    o = _rollout_outs(out, state0, actions, B, H, 12, lay, want_grad_state0,
+                      want_states, want_loss)
     check(lib().apg_wing_rollout_fwd_bwd(
         ptr(state0), ptr(actions), ptr(ref), float(dt), ctypes.byref(params),
         ctypes.byref(weights), B, H, lay, ptr(o["loss_partials"]),
@@ -438,28 +404,12 @@ def wing_rollout_fwd(state0, actions, dt, params, layout="aos"):
     return states
 
 
-class _WingRolloutLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, state0, action_seq, ref, dt, params, weights, layout):
-        s, a, r = _f32c(state0), _f32c(action_seq), _f32c(ref)
-        res = wing_rollout_fwd_bwd(
-            s, a, r, dt, params, weights, layout=layout,
-            want_grad_state0=ctx.needs_input_grad[0])
-        ctx.save_for_backward(res["grad_actions"], res["grad_state0"])
-        return res["loss"].reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        ga, gs = ctx.saved_tensors
-        ga = ga * g if ctx.needs_input_grad[1] else None
-        gs = gs * g if (gs is not None and ctx.needs_input_grad[0]) else None
-        return gs, ga, None, None, None, None, None
-
-
 def wing_rollout_loss(state0, action_seq, ref, dt, params, weights=None,
                       layout="aos"):
-    return _WingRolloutLoss.apply(state0, action_seq, ref, dt, params,
-                                  weights or wing_loss_weights(), layout)
+    return _RolloutLoss.apply(
+        state0, action_seq, lambda s, a, want: wing_rollout_fwd_bwd(
+            s, a, _f32c(ref), dt, params, weights, layout=layout,
+            want_grad_state0=want))
 
 
 # ------------------------------------------ through LearntFixedWingDynamics
@@ -502,12 +452,9 @@ def wing_learnt_rollout_fwd_bwd(dyn, state0, actions, ref, dt, weights=None,
     weights = weights or wing_loss_weights()
     tensors = _wing_learnt_tensors(dyn)
     require_device(state0, actions, ref, *tensors)
-    B, H, A = _seq_shape(actions, lay)
-    Br, Hr, C = _seq_shape(ref, lay)
-    if A != 4 or C != 3 or _state_batch(state0, lay) != B or (Br, Hr) != (B, H):
-        raise ValueError("inconsistent rollout shapes")
-    o = _alloc_outs(None, state0.device, B, H, 12, 4, lay, state0, actions,
-                    want_grad_state0, want_states, True)
+    B, H, _ = _rollout_shape(state0, actions, lay, 4, ref, 3)
+    o = _rollout_outs(None, state0, actions, B, H, 12, lay, want_grad_state0,
+                      want_states)
     ws = torch.empty(max(lib().apg_wing_learnt_rollout_workspace_floats(B), 1),
                      dtype=torch.float32, device=state0.device)
     model = _capi.ApgWingLearnt(*[t.data_ptr() for t in tensors])
@@ -519,31 +466,14 @@ def wing_learnt_rollout_fwd_bwd(dyn, state0, actions, ref, dt, weights=None,
     return o
 
 
-class _WingLearntRolloutLoss(torch.autograd.Function):
-    """loss = fixed_wing_mpc_loss(unroll(learnt_dyn, state0, action_seq), ref,
-    action_seq) as ONE fused rollout; gradients w.r.t. action_seq / state0 only."""
-
-    @staticmethod
-    def forward(ctx, state0, action_seq, ref, dt, dyn, weights):
-        s, a, r = _f32c(state0), _f32c(action_seq), _f32c(ref)
-        res = wing_learnt_rollout_fwd_bwd(
-            dyn, s, a, r, dt, weights, want_grad_state0=ctx.needs_input_grad[0])
-        ctx.save_for_backward(res["grad_actions"], res["grad_state0"])
-        return res["loss"].reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        ga, gs = ctx.saved_tensors
-        ga = ga * g if ctx.needs_input_grad[1] else None
-        gs = gs * g if (gs is not None and ctx.needs_input_grad[0]) else None
-        return gs, ga, None, None, None, None
-
-
 def wing_learnt_rollout_loss(dyn, state0, action_seq, ref, dt, weights=None):
     """The controller phase through the learnt fixed-wing simulator (frozen
-    there: its parameters receive no gradient)."""
-    return _WingLearntRolloutLoss.apply(state0, action_seq, ref, dt, dyn,
-                                        weights or wing_loss_weights())
+    there: its parameters receive no gradient): loss = fixed_wing_mpc_loss(
+    unroll(learnt_dyn, state0, action_seq), ref, action_seq) as ONE fused
+    rollout; gradients w.r.t. action_seq / state0 only."""
+    return _RolloutLoss.apply(
+        state0, action_seq, lambda s, a, want: wing_learnt_rollout_fwd_bwd(
+            dyn, s, a, _f32c(ref), dt, weights, want_grad_state0=want))
 
 
 def wing_learnt_fit_fwd_bwd(dyn, state, action, dt, target=None, eval_params=None,
@@ -609,11 +539,9 @@ def cartpole_rollout_fwd_bwd(state0, actions, dt, params, layout="aos",
     (apg_cartpole_rollout_fwd_bwd)."""
     lay = _layout(layout)
     require_device(state0, actions)
-    B, H, A = _seq_shape(actions, lay)
-    if A != 1 or _state_batch(state0, lay) != B:
-        raise ValueError("inconsistent rollout shapes")
-    o = _alloc_outs(out, state0.device, B, H, 4, 1, lay, state0, actions,
-                    want_grad_state0, want_states, want_loss)
+    B, H, _ = _rollout_shape(state0, actions, lay, 1)
+    o = _rollout_outs(out, state0, actions, B, H, 4, lay, want_grad_state0,
+                      want_states, want_loss)
     check(lib().apg_cartpole_rollout_fwd_bwd(
         ptr(state0), ptr(actions), float(dt), ctypes.byref(params), B, H, lay,
         ptr(o["loss_partials"]), ptr(o["loss"]), ptr(o["grad_actions"]),
@@ -626,9 +554,7 @@ def cartpole_rollout_fwd(state0, actions, dt, params, layout="aos"):
     """No-grad H-step unroll (apg_cartpole_rollout_fwd): states [B,H,4]."""
     lay = _layout(layout)
     require_device(state0, actions)
-    B, H, A = _seq_shape(actions, lay)
-    if A != 1 or _state_batch(state0, lay) != B:
-        raise ValueError("inconsistent rollout shapes")
+    B, H, _ = _rollout_shape(state0, actions, lay, 1)
     states = torch.empty(_states_shape(B, H, 4, lay), dtype=torch.float32,
                          device=state0.device)
     check(lib().apg_cartpole_rollout_fwd(
@@ -637,25 +563,10 @@ def cartpole_rollout_fwd(state0, actions, dt, params, layout="aos"):
     return states
 
 
-class _CartpoleRolloutLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, state0, action_seq, dt, params):
-        s, a = _f32c(state0), _f32c(action_seq)
-        res = cartpole_rollout_fwd_bwd(
-            s, a, dt, params, want_grad_state0=ctx.needs_input_grad[0])
-        ctx.save_for_backward(res["grad_actions"], res["grad_state0"])
-        return res["loss"].reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        ga, gs = ctx.saved_tensors
-        ga = ga * g if ctx.needs_input_grad[1] else None
-        gs = gs * g if (gs is not None and ctx.needs_input_grad[0]) else None
-        return gs, ga, None, None
-
-
 def cartpole_rollout_loss(state0, action_seq, dt, params):
-    return _CartpoleRolloutLoss.apply(state0, action_seq, dt, params)
+    return _RolloutLoss.apply(
+        state0, action_seq, lambda s, a, want: cartpole_rollout_fwd_bwd(
+            s, a, dt, params, want_grad_state0=want))
 
 
 # ------------------------------------------ through LearntCartpoleDynamics
@@ -756,11 +667,9 @@ def cartpole_learnt_rollout_fwd_bwd(dyn, state0, actions, dt, layout="aos",
     if lay == LAYOUT_PACKED:
         raise ValueError("the learnt cart-pole rollout takes 'aos' or 'soa' tensors")
     require_device(state0, actions)
-    B, H, A = _seq_shape(actions, lay)
-    if A != 1 or _state_batch(state0, lay) != B:
-        raise ValueError("inconsistent rollout shapes")
-    o = _alloc_outs(out, state0.device, B, H, 4, 1, lay, state0, actions,
-                    want_grad_state0, want_states, want_loss)
+    B, H, _ = _rollout_shape(state0, actions, lay, 1)
+    o = _rollout_outs(out, state0, actions, B, H, 4, lay, want_grad_state0,
+                      want_states, want_loss)
     model = _cartpole_learnt_model(_cartpole_learnt_tensors(dyn))
     check(lib().apg_cartpole_learnt_rollout_fwd_bwd(
         ptr(state0), ptr(actions), float(dt), ctypes.byref(model), B, H, lay,
@@ -770,28 +679,13 @@ def cartpole_learnt_rollout_fwd_bwd(dyn, state0, actions, dt, layout="aos",
     return o
 
 
-class _CartpoleLearntRolloutLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, state0, action_seq, dt, dyn):
-        s, a = _f32c(state0), _f32c(action_seq)
-        res = cartpole_learnt_rollout_fwd_bwd(
-            dyn, s, a, dt, want_grad_state0=ctx.needs_input_grad[0])
-        ctx.save_for_backward(res["grad_actions"], res["grad_state0"])
-        return res["loss"].reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        ga, gs = ctx.saved_tensors
-        ga = ga * g if ctx.needs_input_grad[1] else None
-        gs = gs * g if (gs is not None and ctx.needs_input_grad[0]) else None
-        return gs, ga, None, None
-
-
 def cartpole_learnt_rollout_loss(dyn, state0, action_seq, dt):
     """loss = cartpole_loss_mpc(unroll(dyn, state0, action_seq),
     make_reference(state0), action_seq) as ONE kernel; gradients to
     action_seq and state0 (the simulator is frozen in the controller phase)."""
-    return _CartpoleLearntRolloutLoss.apply(state0, action_seq, dt, dyn)
+    return _RolloutLoss.apply(
+        state0, action_seq, lambda s, a, want: cartpole_learnt_rollout_fwd_bwd(
+            dyn, s, a, dt, want_grad_state0=want))
 
 
 # ------------------------------------------------------ pre-bound launches

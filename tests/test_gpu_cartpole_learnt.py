@@ -4,15 +4,16 @@ parameter gradient, the simulator fit, the fused controller phase and the
 closed loop in the learnt environment against the recordings of the REAL
 reference (G20, tests/golden/make_golden_cartpole_learnt.py), and the adapt
 flow (train_cartpole.train_norm_dynamics) end to end."""
+import ctypes
 import os
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import load_golden
+from conftest import load_golden, rel_err
 from test_cartpole_eval_cpu import check_against_case, golden_net
-from test_cartpole_learnt_cpu import DT, PHYS, close, fitted, g20
+from test_cartpole_learnt_cpu import DT, PHYS, _Model, close, fitted, fp, g20, tw  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -182,6 +183,75 @@ def test_zeroed_residual_matches_the_analytic_rollout(dev):
     la.backward()
     assert abs(ll.item() - la.item()) <= 1e-5 * abs(la.item())
     close(ga.grad.cpu(), gb.grad.cpu().numpy(), 1e-5)
+
+
+# Device against twin at short horizons: max |device - twin| / max |twin| per
+# output.  Each bar is TWO times the largest such error of the commit before
+# the rollout bodies moved into cartpole_rollout_math.h, measured on an MI355X
+# by rollout_twin_errors below on these inputs over H = 1, 2, 7 and both
+# layouts (the figures here); the factor two allows for the two
+# compilers re-associating differently after the move.
+ROLLOUT_TWIN_BARS = {
+    "analytic": dict(states=2 * 3.15e-7, loss=2 * 2.74e-7, loss_partials=2 * 2.82e-7,
+                     grad_actions=2 * 1.72e-7, grad_state0=2 * 1.97e-7),
+    "learnt": dict(states=2 * 3.03e-7, loss=2 * 1.83e-7, loss_partials=2 * 1.88e-7,
+                   grad_actions=2 * 2.25e-7, grad_state0=2 * 2.15e-7),
+}
+ROLLOUT_TWIN_B = 67          # one full wave and a ragged one
+
+
+def rollout_twin_errors(dev, tw, H, layout):
+    """{kernel: {output: error}} of the analytic and the learnt fused cart-pole
+    rollout against their host twins, every output requested."""
+    from apg_trajectory_tracking_amd import _capi, functional as F
+    from apg_trajectory_tracking_amd.dynamics.cartpole_dynamics import CartpoleDynamics
+    B = ROLLOUT_TWIN_B
+    gen = torch.Generator().manual_seed(100 + H)
+    s0 = (torch.rand(B, 4, generator=gen) * 2 - 1) * torch.tensor([1.0, 2.0, 1.5, 3.0])
+    acts = torch.rand(B, H, 1, generator=gen) * 2 - 1
+    soa = layout == "soa"
+    hs, ha = ((s0.t(), acts.permute(1, 2, 0)) if soa else (s0, acts))
+    hs, ha = hs.contiguous().numpy(), ha.contiguous().numpy()
+    m = fitted(g20())
+    par, host_model = CartpoleDynamics().params, _Model(m)
+    m = m.to(dev)
+    ds, da = torch.from_numpy(hs).to(dev), torch.from_numpy(ha).to(dev)
+    kw = dict(layout=layout, want_grad_state0=True, want_states=True, want_loss=True)
+    device = {"analytic": F.cartpole_rollout_fwd_bwd(ds, da, DT, par, **kw),
+              "learnt": F.cartpole_learnt_rollout_fwd_bwd(m, ds, da, DT, **kw)}
+    errs = {}
+    for kernel, fn, model in (
+            ("analytic", tw.apg_cartpole_rollout_fwd_bwd_cpu, par),
+            ("learnt", tw.apg_cartpole_learnt_rollout_fwd_bwd_cpu, host_model.struct)):
+        twin = dict(loss_partials=np.full(_capi.loss_partials_count(B), np.nan, np.float32),
+                    loss=np.full(1, np.nan, np.float32),
+                    grad_actions=np.full(ha.shape, np.nan, np.float32),
+                    grad_state0=np.full(hs.shape, np.nan, np.float32),
+                    states=np.full((H, 4, B) if soa else (B, H, 4), np.nan, np.float32))
+        assert fn(fp(hs), fp(ha), ctypes.c_float(DT), ctypes.byref(model), B, H,
+                  _capi.LAYOUT_SOA if soa else _capi.LAYOUT_AOS, fp(twin["loss_partials"]),
+                  fp(twin["loss"]), fp(twin["grad_actions"]), fp(twin["grad_state0"]),
+                  fp(twin["states"])) == 0
+        errs[kernel] = {}
+        for k, want in twin.items():
+            got = device[kernel][k].cpu().numpy()
+            assert got.shape == want.shape and np.isfinite(want).all(), (kernel, k)
+            errs[kernel][k] = rel_err(got, want)
+    return errs
+
+
+@pytest.mark.parametrize("layout", ["aos", "soa"])
+@pytest.mark.parametrize("H", [1, 2, 7])
+def test_rollout_kernels_vs_twins_at_short_horizons(dev, tw, H, layout):
+    """(4) both fused rollout kernels against their twins where make_reference's
+    fade degenerates (H = 1: inv = 0 and the only row is the zero row; H = 2:
+    one faded row, then the zero row) and at H = 7, B = 67, both layouts, all
+    five outputs."""
+    errs = rollout_twin_errors(dev, tw, H, layout)
+    print(H, layout, errs)
+    for kernel, bars in ROLLOUT_TWIN_BARS.items():
+        for k, bar in bars.items():
+            assert errs[kernel][k] <= bar, (kernel, k, errs[kernel][k], bar)
 
 
 @pytest.mark.parametrize("name", CASES)
