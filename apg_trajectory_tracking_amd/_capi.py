@@ -197,6 +197,19 @@ WING_FIT_G_W2 = 1138
 WING_FIT_G_B2 = 1906
 WING_FIT_GRADS = 1918
 
+# include/apg.h, APG_QUAD_FIT_*: the same for apg_quad_learnt_fit_fwd_bwd, in the
+# order of LearntDynamics.parameters() (linear_at [4][4], mass, inertia [3], kinv
+# [3], dW1 [64][16], db1 [64], dW2 [12][64], db2 [12])
+QUAD_FIT_G_LINEAR_AT = 0
+QUAD_FIT_G_MASS = 16
+QUAD_FIT_G_INERTIA = 17
+QUAD_FIT_G_KINV = 20
+QUAD_FIT_G_W1 = 23
+QUAD_FIT_G_B1 = 1047
+QUAD_FIT_G_W2 = 1111
+QUAD_FIT_G_B2 = 1879
+QUAD_FIT_GRADS = 1891
+
 
 class ApgCartpoleMpcOptions(ctypes.Structure):
     """include/apg.h: the cart-pole shooting MPC's iteration count and step rule."""
@@ -224,6 +237,11 @@ SIGNATURES = {
         _P, _P, _P, _I, _F, ctypes.POINTER(ApgQuadParams),
         ctypes.POINTER(ApgLearntResidual), ctypes.POINTER(ApgQuadLossWeights),
         _I, _I, _I, _P, _P, _P, _P, _P, _P],
+    "apg_quad_learnt_fit_grad_count": [],
+    "apg_quad_learnt_fit_workspace_floats": [_I],
+    "apg_quad_learnt_fit_fwd_bwd": [
+        _P, _P, _F, ctypes.POINTER(ApgQuadParams), ctypes.POINTER(ApgLearntResidual), _P,
+        ctypes.POINTER(ApgQuadParams), _F, _I, _P, _P, _P, _P, _P],
     "apg_quad_loss_fwd_bwd": [
         _P, _P, _I, _P, ctypes.POINTER(ApgQuadLossWeights), _I, _I, _I, _P,
         _P, _P, _P, _P],

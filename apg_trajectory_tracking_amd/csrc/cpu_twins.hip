@@ -13,12 +13,14 @@
 #include <vector>
 
 #include "apg_cpu.h"
+#include "apg_cpu_quad_fit.h"
 #include "apg_cpu_wing_fit.h"
 #include "apg_cpu_wing_learnt.h"
 #include "cartpole_learnt_math.h"
 #include "cartpole_math.h"
 #include "cartpole_mpc_math.h"
 #include "cartpole_rollout_math.h"
+#include "quad_fit_math.h"
 #include "quad_math.h"
 #include "quad_mpc_math.h"
 #include "wing_learnt_math.h"
@@ -717,6 +719,81 @@ int apg_wing_learnt_fit_fwd_bwd_cpu(const float *state, const float *action, flo
                                ? wing_fit_l2_grad(dest, l2_lambda, model->w1, model->b1,
                                                   model->w2, model->b2, norms)
                                : 0.f);
+  }
+  return APG_OK;
+}
+
+// apg_cpu_quad_fit.h: quad_learnt_fit_kernel (quad_fit.hip) lane for lane, the
+// batch summed in order; the regulariser as its reduction kernel adds it
+int apg_quad_learnt_fit_fwd_bwd_cpu(const float *state, const float *action, float dt,
+                                    const ApgQuadParams *params,
+                                    const ApgLearntResidual *model, const float *target,
+                                    const ApgQuadParams *eval_params, float l2_lambda, int B,
+                                    float *loss_partials, float *loss, float *grad,
+                                    float *workspace) {
+  (void)workspace;
+  if (B < 0) return fail("B must be >= 0 (got %d)", B);
+  if (!params) return fail("params is NULL");
+  if (!model || !model->linear_at || !model->w1 || !model->b1 || !model->w2 || !model->b2)
+    return fail("model or one of its pointers is NULL");
+  if ((target != nullptr) == (eval_params != nullptr))
+    return fail("exactly one of target / eval_params must be given");
+  if (!(l2_lambda >= 0.f)) return fail("l2_lambda must be >= 0");
+  if (!grad) return fail("grad is NULL");
+  for (int i = 0; i < kQuadFitGrads; ++i) grad[i] = 0.f;
+  if (B == 0) {
+    if (loss) *loss = 0.f;
+    return APG_OK;
+  }
+  if (!state || !action || !loss_partials)
+    return fail("state / action / loss_partials must not be NULL");
+  const QuadConst c = make_const(*params, dt);
+  const QuadConst ce = eval_params ? make_const(*eval_params, dt) : QuadConst{};
+  const QuadFitInertia q = make_fit_inertia(*params, dt);
+  std::vector<float> pack(kQuadPackFloats), acc(kQuadFitRow, 0.f);
+  for (int t = 0; t < kQuadPackFloats; ++t) pack[t] = quad_fit_packed(t, *model);
+  const float *pk = pack.data();
+  LossOut out{loss_partials, loss};
+  for (int b = 0; b < B; ++b) {
+    float s[12], a[4], tgt[12], lam[12], x[16], hd[kQuadFitHUsed];
+    for (int i = 0; i < 12; ++i) s[i] = state[(size_t)b * 12 + i];
+    for (int i = 0; i < 4; ++i) a[i] = action[(size_t)b * 4 + i];
+    const Trig t = make_trig(&s[3]);
+    if (eval_params) {
+      for (int i = 0; i < 12; ++i) tgt[i] = s[i];
+      quad_step(tgt, a, ce, t);
+    } else {
+      for (int i = 0; i < 12; ++i) tgt[i] = target[(size_t)b * 12 + i];
+    }
+    const float l = quad_learnt_fit_sample(s, a, tgt, c, t, pk, lam, x, hd);
+    for (int i = 0; i < kQuadFitHUsed; ++i) acc[i] += hd[i];
+    for (int m = 0; m < kResHidden; ++m) {
+      float gw[kResFitUnit] = {0.f};
+      residual_unit_grads<kQuadResW2, kQuadResB1>(pk + m * kQuadResRow, x, lam, gw);
+      for (int j = 0; j < kResFitUnit; ++j) acc[kQuadFitHead + j * kResHidden + m] += gw[j];
+    }
+    out.add(b, B, l);
+  }
+  out.finish(B);
+  float norms[4] = {0.f, 0.f, 0.f, 0.f};
+  if (l2_lambda > 0.f) {
+    const float *tens[4] = {model->w2, model->b2, model->w1, model->b1};
+    const int count[4] = {12 * kResHidden, 12, kResHidden * 16, kResHidden};
+    for (int k = 0; k < 4; ++k) {
+      float ss = 0.f;
+      for (int t = 0; t < count[k]; ++t) ss = fmaf(tens[k][t], tens[k][t], ss);
+      norms[k] = sqrtf(ss);
+    }
+    if (loss) *loss += l2_lambda * (((norms[0] + norms[1]) + norms[2]) + norms[3]);
+  }
+  for (int e = 0; e < kQuadFitRow; ++e) {
+    const int dest = quad_fit_dest(e);
+    if (dest < 0) continue;
+    grad[dest] = quad_fit_value(e, acc[e], q) +
+                 (l2_lambda > 0.f
+                      ? residual_l2_grad<kQuadFitGW1, kQuadFitGB1, kQuadFitGW2, kQuadFitGB2>(
+                            dest, l2_lambda, model->w1, model->b1, model->w2, model->b2, norms)
+                      : 0.f);
   }
   return APG_OK;
 }

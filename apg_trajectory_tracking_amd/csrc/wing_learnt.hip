@@ -213,21 +213,7 @@ __global__ __launch_bounds__(256) void wing_learnt_fit_pack_kernel(ApgWingLearnt
   }
   for (int t = threadIdx.x; t < kWingResFloats; t += blockDim.x)
     ws[kWingLearntTableFloats + t] = wing_residual_packed(t, m.w1, m.b1, m.w2, m.b2);
-  const float *tens[4] = {m.w2, m.b2, m.w1, m.b1};
-  const int count[4] = {12 * kWingResHidden, 12, kWingResHidden * 16, kWingResHidden};
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    float acc = 0.f;
-    for (int t = threadIdx.x; t < count[q]; t += 256) acc = fmaf(tens[q][t], tens[q][t], acc);
-    part[q][threadIdx.x] = acc;
-  }
-  for (int half = 128; half >= 1; half >>= 1) {
-    __syncthreads();
-    if ((int)threadIdx.x < half)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) part[q][threadIdx.x] += part[q][threadIdx.x + half];
-  }
-  if (threadIdx.x < 4) ws[kFitNorms + threadIdx.x] = sqrtf(part[threadIdx.x][0]);
+  residual_norms(m.w1, m.b1, m.w2, m.b2, part, ws + kFitNorms);
 }
 
 struct WingFitArgs {
@@ -349,14 +335,8 @@ __global__ __launch_bounds__(kFitCols * kFitSplit) void wing_learnt_fit_reduce_k
   const int col = threadIdx.x % kFitCols, r = threadIdx.x / kFitCols;
   const int c = blockIdx.x * kFitCols + col;          // kWingFitRow = 60 x 32
   const float *rows = ws + kFitRows;
-  float acc = 0.f;
-#pragma unroll 4
-  for (int i = r; i < nrows; i += kFitSplit) acc += rows[(size_t)i * kWingFitRow + c];
-  part[r][col] = acc;
-  __syncthreads();
+  const float v = fit_rows_sum<kWingFitRow>(rows, nrows, c, col, r, part);
   if (r == 0) {
-    const float v = ((part[0][col] + part[1][col]) + (part[2][col] + part[3][col])) +
-                    ((part[4][col] + part[5][col]) + (part[6][col] + part[7][col]));
     const int dest = wing_fit_dest(c);
     if (dest >= 0) {
       float reg = 0.f;
@@ -370,7 +350,8 @@ __global__ __launch_bounds__(kFitCols * kFitSplit) void wing_learnt_fit_reduce_k
     loss[0] += l2_lambda * (((n[0] + n[1]) + n[2]) + n[3]);
   }
 }
-static_assert(kWingFitRow % kFitCols == 0, "whole workgroups of columns");
+static_assert(kWingFitRow % kFitCols == 0 && kFitSplit == 8,
+              "whole workgroups of columns; fit_rows_sum adds eight sums");
 
 int check_learnt(const void *state, const void *action, const void *params,
                  const float *inertia, int B) {

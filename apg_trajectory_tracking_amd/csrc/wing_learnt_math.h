@@ -9,6 +9,7 @@
 // used: NoWingParamGrads).  Called per lane by wing_learnt.hip's fused rollout
 // and per trajectory by its host twin (csrc/cpu_twins.hip).
 #pragma once
+#include "residual_fit.h"
 #include "wing_math.h"
 
 namespace apg {
@@ -200,7 +201,7 @@ constexpr int kWingFitGrads = kWingFitGB2 + 12;                     // 1918
 // A partial row as the kernel sums it: [50 physical | db2 (12) | 0 0 | 29
 // planes of 64: plane j < 16 = dW1[.][j], plane 16 + o = dW2[o][.], plane 28 =
 // db1] - hidden unit m owns element m of every plane.
-constexpr int kWingFitUnit = 29;                                    // a unit's cotangents
+constexpr int kWingFitUnit = kResFitUnit;                           // a unit's cotangents
 constexpr int kWingFitHead = 64;
 constexpr int kWingFitRow = kWingFitHead + kWingFitUnit * kWingResHidden;   // 1920
 
@@ -246,42 +247,23 @@ __host__ __device__ __forceinline__ float wing_learnt_fit_sample(const float (&s
   return loss;
 }
 
-// gw += hidden unit's 29 cotangents for one sample (z, lam): gw[j < 16] =
-// dW1[m][j], gw[16 + o] = dW2[o][m], gw[28] = db1[m]; w = the unit's packed row
-// (relu'(0) = 0, as torch's threshold backward)
+// gw += hidden unit's 29 cotangents for one sample (residual_fit.h) on this
+// header's packed row
 __host__ __device__ __forceinline__ void wing_residual_unit_grads(const float *w,
                                                                   const float (&z)[16],
                                                                   const float (&lam)[12],
                                                                   float (&gw)[kWingFitUnit]) {
-  float h = w[kWingResB1];
-#pragma unroll
-  for (int j = 0; j < 16; ++j) h = fmaf(w[j], z[j], h);
-  float dh = 0.f;
-#pragma unroll
-  for (int o = 0; o < 12; ++o) dh = fmaf(w[kWingResW2 + o], lam[o], dh);
-  dh = h > 0.f ? dh : 0.f;
-  h = fmaxf(h, 0.f);
-#pragma unroll
-  for (int j = 0; j < 16; ++j) gw[j] = fmaf(dh, z[j], gw[j]);
-#pragma unroll
-  for (int o = 0; o < 12; ++o) gw[16 + o] = fmaf(lam[o], h, gw[16 + o]);
-  gw[28] += dh;
+  residual_unit_grads<kWingResW2, kWingResB1>(w, z, lam, gw);
 }
 
-// the regulariser's gradient l2_lambda t / |t| (0 where |t| = 0, as torch's
-// norm backward) for element `dest` of the flat gradient; norms = |W2|, |b2|,
-// |W1|, |b1| (the order of _residual_weight_norm)
+// the regulariser's gradient for element `dest` of the flat gradient
+// (residual_fit.h)
 __host__ __device__ __forceinline__ float wing_fit_l2_grad(int dest, float l2_lambda,
                                                            const float *w1, const float *b1,
                                                            const float *w2, const float *b2,
                                                            const float *norms) {
-  if (dest < kWingFitGW1) return 0.f;
-  float t, n;
-  if (dest < kWingFitGB1) t = w1[dest - kWingFitGW1], n = norms[2];
-  else if (dest < kWingFitGW2) t = b1[dest - kWingFitGB1], n = norms[3];
-  else if (dest < kWingFitGB2) t = w2[dest - kWingFitGW2], n = norms[0];
-  else t = b2[dest - kWingFitGB2], n = norms[1];
-  return n > 0.f ? l2_lambda * (t / n) : 0.f;
+  return residual_l2_grad<kWingFitGW1, kWingFitGB1, kWingFitGW2, kWingFitGB2>(
+      dest, l2_lambda, w1, b1, w2, b2, norms);
 }
 
 }  // namespace

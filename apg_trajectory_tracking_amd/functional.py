@@ -312,6 +312,88 @@ def quad_learnt_rollout_loss(dyn, state0, action_seq, ref, dt, weights=None):
             dyn, s, a, _f32c(ref), dt, weights, want_grad_state0=want))
 
 
+def quad_learnt_fusable(dyn):
+    """Whether `dyn` is what the fused quadrotor fit serves: a stock
+    LearntDynamics - the 4 x 4 action transform and the 16 -> 64 -> 12 residual
+    as float32 tensors on one device."""
+    from .dynamics.quad_dynamics_trained import LearntDynamics
+    if type(dyn) is not LearntDynamics:
+        return False
+    try:
+        tensors = [dyn.linear_at, dyn.linear_state_1.weight, dyn.linear_state_1.bias,
+                   dyn.linear_state_2.weight, dyn.linear_state_2.bias, dyn.mass,
+                   dyn.torch_inertia_vector, dyn.torch_kinv_vector]
+    except AttributeError:
+        return False
+    shapes = [(4, 4), (64, 16), (64,), (12, 64), (12,), (1,), (3,), (3,)]
+    return (all(isinstance(t, torch.Tensor) and t.dtype == torch.float32
+                and tuple(t.shape) == sh for t, sh in zip(tensors, shapes))
+            and len({t.device for t in tensors}) == 1
+            and len(list(dyn.parameters())) == 8)
+
+
+def _quad_learnt_tensors(dyn):
+    """The tensors ApgLearntResidual points to, contiguous, for the fused fit."""
+    if not quad_learnt_fusable(dyn):
+        raise ValueError("fused fit expects a LearntDynamics with the 4 x 4 action "
+                         "transform and the 16 -> 64 -> 12 residual network")
+    tensors = [dyn.linear_at.detach(),
+               dyn.linear_state_1.weight.detach(), dyn.linear_state_1.bias.detach(),
+               dyn.linear_state_2.weight.detach(), dyn.linear_state_2.bias.detach()]
+    return [t if t.is_contiguous() else t.contiguous() for t in tensors]
+
+
+def quad_learnt_fit_fwd_bwd(dyn, state, action, dt, target=None, eval_params=None,
+                            l2_lambda=0.0):
+    """One step of the simulator fit (TrainBase.train_dynamics_model) on the
+    LearntDynamics `dyn`, fused (apg_quad_learnt_fit_fwd_bwd):
+    loss = sum (dyn(state, action, dt) - target)^2 + l2_lambda x the residual's
+    four weight norms, and its gradient for EVERY parameter of `dyn` as one
+    flat tensor (quad_learnt_fit_grad_views hands out the per-parameter views).
+    The target is `target` [B,12], or the analytic step with `eval_params`
+    (an ApgQuadParams, e.g. FlightmareDynamics.params) - exactly one of the two.
+    The step runs on `dyn.params`, the constants of construction time, as the
+    module's forward does; its tensors are read on the device when the launches
+    run: no host read, no synchronisation, capturable in a graph."""
+    tensors = _quad_learnt_tensors(dyn)
+    state, action = _f32c(state), _f32c(action)
+    if target is not None:
+        target = _f32c(target)
+    require_device(state, action, target, *tensors)
+    if state.dim() != 2 or state.shape[1] != 12 or action.shape != (state.shape[0], 4):
+        raise ValueError("state [B,12] / action [B,4] expected")
+    if target is not None and target.shape != state.shape:
+        raise ValueError("target [B,12] expected")
+    B, dev = state.shape[0], state.device
+    grad = torch.empty(_capi.QUAD_FIT_GRADS, dtype=torch.float32, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    parts = torch.empty(_capi.loss_partials_count(B), dtype=torch.float32, device=dev)
+    ws = torch.empty(max(lib().apg_quad_learnt_fit_workspace_floats(B), 1),
+                     dtype=torch.float32, device=dev)
+    model = _capi.ApgLearntResidual(*[t.data_ptr() for t in tensors])
+    check(lib().apg_quad_learnt_fit_fwd_bwd(
+        ptr(state), ptr(action), float(dt), ctypes.byref(dyn.params), ctypes.byref(model),
+        ptr(target), None if eval_params is None else ctypes.byref(eval_params),
+        float(l2_lambda), B, ptr(parts), ptr(loss), ptr(grad), ptr(ws), stream_of(state)),
+        "apg_quad_learnt_fit_fwd_bwd")
+    return dict(loss=loss, grad=grad)
+
+
+def quad_learnt_fit_grad_views(dyn, grad):
+    """The flat gradient of quad_learnt_fit_fwd_bwd as one view per parameter,
+    in the order (and shapes) of dyn.named_parameters().  Views, not copies:
+    `p.grad = view` costs no launch."""
+    at = {"linear_at": _capi.QUAD_FIT_G_LINEAR_AT, "mass": _capi.QUAD_FIT_G_MASS,
+          "torch_inertia_vector": _capi.QUAD_FIT_G_INERTIA,
+          "torch_kinv_vector": _capi.QUAD_FIT_G_KINV,
+          "linear_state_1.weight": _capi.QUAD_FIT_G_W1,
+          "linear_state_1.bias": _capi.QUAD_FIT_G_B1,
+          "linear_state_2.weight": _capi.QUAD_FIT_G_W2,
+          "linear_state_2.bias": _capi.QUAD_FIT_G_B2}
+    return [grad[at[name]:at[name] + p.numel()].view(p.shape)
+            for name, p in dyn.named_parameters()]
+
+
 class _QuadLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, states, ref, actions, weights):

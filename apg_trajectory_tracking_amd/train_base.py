@@ -965,6 +965,21 @@ class TrainBase:
         self.results_dict["loss_dyn_per_step"].append(loss.detach())
         return loss
 
+    def _finish_fused_fit(self, loss, grad_views):
+        """The tail of a fused simulator-fit step (the train_dynamics_model
+        overrides of TrainDrone / TrainFixedWing): `grad_views` - one view of
+        the kernel's flat gradient per parameter, in train_dynamics.parameters()
+        order - become the .grad fields, then what the base method does after
+        loss.backward()."""
+        for p, g in zip(self.train_dynamics.parameters(), grad_views):
+            p.grad = g
+        loss = loss.reshape(())
+        if getattr(self, "grad_sync_dynamics", None) is not None:
+            loss = self.grad_sync_dynamics.sync(loss)   # replicas stay equal
+        self.optimizer_dynamics.step()
+        self.results_dict["loss_dyn_per_step"].append(loss.detach())
+        return loss
+
     def _pipelined_epoch(self, prepare, step, indices=None):
         """One epoch over the loader's index batches with the input pipeline
         one batch ahead: `prepare(index, out)` - the layout change with the row

@@ -245,14 +245,8 @@ class TrainFixedWing(TrainBase):
             res = F.wing_learnt_fit_fwd_bwd(
                 d, current_state, first_action, self.delta_t, target=target,
                 l2_lambda=lam)
-        for p, g in zip(d.parameters(), F.wing_learnt_fit_grad_views(d, res["grad"])):
-            p.grad = g
-        loss = res["loss"].reshape(())
-        if getattr(self, "grad_sync_dynamics", None) is not None:
-            loss = self.grad_sync_dynamics.sync(loss)   # replicas stay equal
-        self.optimizer_dynamics.step()
-        self.results_dict["loss_dyn_per_step"].append(loss.detach())
-        return loss
+        return self._finish_fused_fit(
+            res["loss"], F.wing_learnt_fit_grad_views(d, res["grad"]))
 
 
 def train_control(base_model, config, device=None):

@@ -181,6 +181,55 @@ int apg_quad_learnt_rollout_fwd_bwd(const float *state0, const float *actions,
                                     float *grad_actions, float *grad_state0,
                                     float *states_out, apg_stream_t stream);
 
+/* The simulator-fit phase for the same module as ONE call:
+ * TrainBase.train_dynamics_model (scripts/train_base.py:160-186) with
+ * LearntDynamics as train dynamics, up to (not including) the optimizer step.
+ * AoS state [B,12] / action [B,4].
+ *   a'     = linear_at a
+ *   pred   = quad_step(s, a'; params) + W2 relu(W1 [s; a'] + b1) + b2
+ *            (`params`: the HOST struct the module simulates with - its
+ *            construction-time kinv / inertia, as apg_quad_learnt_rollout_fwd_bwd
+ *            takes it; `model`: the module's live DEVICE tensors)
+ *   target = `target` [B,12] (device), or - target NULL - the analytic step on
+ *            the raw action with `eval_params` (a HOST struct).  Exactly one of
+ *            the two is given.
+ *   loss   = sum_b sum_i (pred - target)^2
+ *            + l2_lambda (|W2| + |b2| + |W1| + |b1|)   (four 2-norms; l2_lambda >= 0)
+ *   grad   = d loss / d parameter, summed over the batch, ONE flat buffer of
+ *            apg_quad_learnt_fit_grad_count() = APG_QUAD_FIT_GRADS floats in the
+ *            order of LearntDynamics.parameters(): linear_at [4][4], mass,
+ *            inertia [3], kinv [3], dW1 [64][16], db1 [64], dW2 [12][64], db2 [12]
+ *            at the offsets below.  With lam = 2 (pred - target):
+ *              dL/dkinv_i    = sum_b lam_w'i dt ((a'_i - 1/2) - w_i)
+ *              dL/dinertia_i = -(sum_b lam_w'i) dt rot_drag_i / inertia_i^2
+ *              dL/dmass      = 0 exactly
+ *            evaluated at the values of `params` (the reference's torch.diag
+ *            copies, quad_dynamics_trained.py:48-50).  A tensor of norm 0 gets no
+ *            regulariser gradient (as torch's norm backward): a fresh,
+ *            zero-initialised residual is fine.
+ * loss_partials: apg_loss_partials_count(B) floats; loss may be NULL.
+ * workspace: apg_quad_learnt_fit_workspace_floats(B) device floats.  B == 0
+ * zeroes loss and grad and returns.  Every model tensor is read ON THE DEVICE
+ * when the launches run (no host read, no synchronisation, graph-capturable);
+ * no float atomics: the same inputs give the same bits.  Argument errors (NULL
+ * model pointers, both or neither of target / eval_params, B < 0,
+ * l2_lambda < 0) are reported before any HIP call. */
+#define APG_QUAD_FIT_G_LINEAR_AT 0
+#define APG_QUAD_FIT_G_MASS 16
+#define APG_QUAD_FIT_G_INERTIA 17
+#define APG_QUAD_FIT_G_KINV 20
+#define APG_QUAD_FIT_G_W1 23
+#define APG_QUAD_FIT_G_B1 1047
+#define APG_QUAD_FIT_G_W2 1111
+#define APG_QUAD_FIT_G_B2 1879
+#define APG_QUAD_FIT_GRADS 1891
+int apg_quad_learnt_fit_grad_count(void);
+int apg_quad_learnt_fit_workspace_floats(int B);
+int apg_quad_learnt_fit_fwd_bwd(const float *state, const float *action, float dt,
+    const ApgQuadParams *params, const ApgLearntResidual *model, const float *target,
+    const ApgQuadParams *eval_params, float l2_lambda, int B, float *loss_partials,
+    float *loss, float *grad, float *workspace, apg_stream_t stream);
+
 /* No-grad unroll (eval / self-play): states_out[B,H,12] only. */
 int apg_quad_rollout_fwd(const float *state0, const float *actions, float dt,
                          const ApgQuadParams *params, int B, int H, int layout,
