@@ -211,6 +211,16 @@ QUAD_FIT_G_B2 = 1879
 QUAD_FIT_GRADS = 1891
 
 
+# include/apg.h, APG_CARTPOLE_LEARNT_*: the one layout of the learnt cart-pole's
+# parameter cotangents (apg_cartpole_learnt_step_bwd's grad_params and
+# apg_cartpole_learnt_fit_fwd_bwd's grad): the six CARTPOLE_LEARNT_FIELDS, then
+# dW1 [64][5], db1 [64], dW2 [4][64]
+CARTPOLE_LEARNT_G_W1 = 6
+CARTPOLE_LEARNT_G_B1 = 326
+CARTPOLE_LEARNT_G_W2 = 390
+CARTPOLE_LEARNT_GRADS = 646
+
+
 class ApgCartpoleMpcOptions(ctypes.Structure):
     """include/apg.h: the cart-pole shooting MPC's iteration count and step rule."""
     _fields_ = [("iters", ctypes.c_int), ("beta", ctypes.c_float),
@@ -377,6 +387,10 @@ SIGNATURES = {
                                      _P, _P],
     "apg_cartpole_learnt_step_bwd": [_P, _P, _F, ctypes.POINTER(ApgCartpoleLearnt), _I,
                                      _P, _P, _P, _P, _P, _P],
+    "apg_cartpole_learnt_fit_workspace_floats": [_I],
+    "apg_cartpole_learnt_fit_fwd_bwd": [
+        _P, _P, _F, ctypes.POINTER(ApgCartpoleLearnt), _P,
+        ctypes.POINTER(ApgCartpoleParams), _I, _P, _P, _P, _P, _P],
     "apg_cartpole_learnt_rollout_fwd_bwd": [
         _P, _P, _F, ctypes.POINTER(ApgCartpoleLearnt), _I, _I, _I, _P, _P, _P, _P, _P,
         _P],

@@ -13,9 +13,11 @@
 #include <vector>
 
 #include "apg_cpu.h"
+#include "apg_cpu_cartpole_fit.h"
 #include "apg_cpu_quad_fit.h"
 #include "apg_cpu_wing_fit.h"
 #include "apg_cpu_wing_learnt.h"
+#include "cartpole_fit_math.h"
 #include "cartpole_learnt_math.h"
 #include "cartpole_math.h"
 #include "cartpole_mpc_math.h"
@@ -600,6 +602,60 @@ int apg_cartpole_learnt_rollout_fwd_bwd_cpu(const float *state0, const float *ac
       [&](float (&lam)[4], const float (&pre)[4], float a) {
         return cart_learnt_step_adjoint(lam, pre, a, cart_step_aux(pre, a, c), c, rows.data());
       });
+  return APG_OK;
+}
+
+// apg_cpu_cartpole_fit.h: cartpole_fit_kernel (cartpole_fit.hip) lane for lane,
+// the batch summed in sample order into one partial row
+int apg_cartpole_learnt_fit_fwd_bwd_cpu(const float *state, const float *action, float dt,
+                                        const ApgCartpoleLearnt *model, const float *target,
+                                        const ApgCartpoleParams *eval_params, int B,
+                                        float *loss_partials, float *loss, float *grad,
+                                        float *workspace) {
+  (void)workspace;
+  if (int e = check_learnt(model, B, true)) return e;
+  if ((target != nullptr) == (eval_params != nullptr))
+    return fail("exactly one of target / eval_params must be given");
+  if (!grad) return fail("grad is NULL");
+  for (int i = 0; i < kCartLearntGrads; ++i) grad[i] = 0.f;
+  if (B == 0) {
+    if (loss) *loss = 0.f;
+    return APG_OK;
+  }
+  if (!state || !action || !loss_partials)
+    return fail("state / action / loss_partials must not be NULL");
+  CartLearntParams p;
+  CartConst c;
+  std::vector<float> rows;
+  learnt_setup(*model, dt, p, c, rows);
+  const CartConst ce = eval_params ? make_const(*eval_params, dt) : CartConst{};
+  std::vector<float> acc(kCartFitRow, 0.f);
+  LossOut out{loss_partials, loss};
+  for (int b = 0; b < B; ++b) {
+    float s[4], tgt[4], lam[4], g[kCartPhysGrads] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < 4; ++i) s[i] = state[(size_t)b * 4 + i];
+    const float a = action[b];
+    if (eval_params) {
+      for (int i = 0; i < 4; ++i) tgt[i] = s[i];
+      cart_step(tgt, a, ce);
+    } else {
+      for (int i = 0; i < 4; ++i) tgt[i] = target[(size_t)b * 4 + i];
+    }
+    const float l = cart_fit_sample(s, a, tgt, p, c, dt, rows.data(), lam, g);
+    for (int i = 0; i < kCartPhysGrads; ++i) acc[i] += g[i];
+    const float z[5] = {s[0], s[1], s[2], s[3], a};
+    for (int m = 0; m < kCartResHidden; ++m) {
+      float gw[kCartResRow] = {0.f};
+      cart_residual_unit_grads(&rows[m * kCartResRow], z, lam, gw);
+      for (int j = 0; j < kCartResRow; ++j) acc[kCartFitHead + j * kCartResHidden + m] += gw[j];
+    }
+    out.add(b, B, l);
+  }
+  out.finish(B);
+  for (int e = 0; e < kCartFitRow; ++e) {
+    const int dest = cart_fit_dest(e);
+    if (dest >= 0) grad[dest] = acc[e];
+  }
   return APG_OK;
 }
 

@@ -770,6 +770,83 @@ def cartpole_learnt_rollout_loss(dyn, state0, action_seq, dt):
             dyn, s, a, dt, want_grad_state0=want))
 
 
+def cartpole_learnt_fusable(dyn):
+    """Whether `dyn` is what the fused cart-pole fit serves: a stock
+    LearntCartpoleDynamics - the six physical [1] parameters and the
+    5 -> 64 -> 4 residual (no output bias) as contiguous float32 tensors on one
+    CUDA device."""
+    from .dynamics.cartpole_dynamics import LearntCartpoleDynamics
+    if type(dyn) is not LearntCartpoleDynamics:
+        return False
+    try:
+        tensors = _cartpole_learnt_tensors(dyn)
+        has_bias = dyn.linear_state_2.bias is not None
+    except (AttributeError, KeyError):
+        return False
+    shapes = [(1,)] * 6 + [(64, 5), (64,), (4, 64)]
+    return (not has_bias
+            and all(isinstance(t, torch.Tensor) and t.dtype == torch.float32
+                    and t.is_cuda and t.is_contiguous() and tuple(t.shape) == sh
+                    for t, sh in zip(tensors, shapes))
+            and len({t.device for t in tensors}) == 1
+            and len(list(dyn.parameters())) == 3 + len(dyn.cfg))
+
+
+def cartpole_learnt_fit_fwd_bwd(dyn, state, action, dt, target=None, eval_params=None):
+    """One step of the simulator fit (TrainBase.train_dynamics_model) on the
+    LearntCartpoleDynamics `dyn`, fused (apg_cartpole_learnt_fit_fwd_bwd):
+    loss = sum (dyn(state, action, dt) - target)^2 and its gradient for all 646
+    parameters that enter the module's forward as one flat tensor
+    (cartpole_learnt_fit_grad_views hands out the per-parameter views).  The
+    target is `target` [B,4], or the analytic step with `eval_params` (an
+    ApgCartpoleParams, e.g. CartpoleDynamics.params) - exactly one of the two.
+    The module's tensors are read on the device when the launches run: no host
+    read, no synchronisation, capturable in a graph."""
+    if not cartpole_learnt_fusable(dyn):
+        raise ValueError("fused fit expects a LearntCartpoleDynamics with [1] "
+                         "parameters and the 5 -> 64 -> 4 residual network as "
+                         "contiguous fp32 tensors on one CUDA device")
+    if (target is None) == (eval_params is None):
+        raise ValueError("exactly one of target / eval_params must be given")
+    tensors = [t.detach() for t in _cartpole_learnt_tensors(dyn)]
+    state, action = _f32c(state), _f32c(action)
+    if target is not None:
+        target = _f32c(target)
+    require_device(state, action, target, *tensors)
+    if state.dim() != 2 or state.shape[1] != 4 or action.shape != (state.shape[0], 1):
+        raise ValueError("state [B,4] / action [B,1] expected")
+    if target is not None and target.shape != state.shape:
+        raise ValueError("target [B,4] expected")
+    B, dev = state.shape[0], state.device
+    grad = torch.empty(_capi.CARTPOLE_LEARNT_GRADS, dtype=torch.float32, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    parts = torch.empty(_capi.loss_partials_count(B), dtype=torch.float32, device=dev)
+    ws = torch.empty(max(lib().apg_cartpole_learnt_fit_workspace_floats(B), 1),
+                     dtype=torch.float32, device=dev)
+    model = _cartpole_learnt_model(tensors)
+    check(lib().apg_cartpole_learnt_fit_fwd_bwd(
+        ptr(state), ptr(action), float(dt), ctypes.byref(model), ptr(target),
+        None if eval_params is None else ctypes.byref(eval_params), B, ptr(parts),
+        ptr(loss), ptr(grad), ptr(ws), stream_of(state)),
+        "apg_cartpole_learnt_fit_fwd_bwd")
+    return dict(loss=loss, grad=grad)
+
+
+def cartpole_learnt_fit_grad_views(dyn, grad):
+    """The flat gradient of cartpole_learnt_fit_fwd_bwd as one entry per
+    parameter, in the order of dyn.parameters(): a view of `grad` (no copy:
+    `p.grad = view` costs no launch) where autograd would leave a gradient,
+    None where it would not - the `cfg` keys that do not enter the physics and
+    every parameter with requires_grad False (`not_trainable`)."""
+    at = {"linear_state_1.weight": _capi.CARTPOLE_LEARNT_G_W1,
+          "linear_state_1.bias": _capi.CARTPOLE_LEARNT_G_B1,
+          "linear_state_2.weight": _capi.CARTPOLE_LEARNT_G_W2}
+    at.update(("cfg." + k, i) for i, k in enumerate(_capi.CARTPOLE_LEARNT_FIELDS))
+    return [grad[at[name]:at[name] + p.numel()].view(p.shape)
+            if name in at and p.requires_grad else None
+            for name, p in dyn.named_parameters()]
+
+
 # ------------------------------------------------------ pre-bound launches
 def reduce_loss_partials(partials, loss=None):
     """loss[0] = fixed-order sum of `partials` (apg_reduce_loss_partials)."""

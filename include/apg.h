@@ -1180,6 +1180,41 @@ int apg_cartpole_learnt_step_bwd(const float *state, const float *action, float 
                                  float *grad_action, float *grad_params, float *workspace,
                                  apg_stream_t stream);
 
+/* The simulator-fit phase for the same module as ONE call:
+ * TrainBase.train_dynamics_model (scripts/train_base.py:160-186) with
+ * LearntCartpoleDynamics as train dynamics, up to (not including) the optimizer
+ * step.  AoS state [B,4] / action [B,1].
+ *   pred   = simulate_cartpole(s, a) + W2 relu(W1 [s; a] + b1) on the module's
+ *            live DEVICE tensors (`model`; the residual must be given)
+ *   target = `target` [B,4] (device), or - target NULL - the analytic step of
+ *            apg_cartpole_step_fwd with `eval_params` (a HOST struct).  Exactly
+ *            one of the two is given.
+ *   loss   = sum_b sum_i (pred - target)^2
+ *   grad   = d loss / d parameter, summed over the batch (lam = 2 (pred -
+ *            target) per sample): apg_cartpole_learnt_param_count() =
+ *            APG_CARTPOLE_LEARNT_GRADS floats in the ONE layout of the module's
+ *            parameter cotangents, that of apg_cartpole_learnt_step_bwd's
+ *            grad_params: the six physical ones, then W1, b1, W2 at the offsets
+ *            below.
+ * There is no regulariser: the reference's penalty reads linear_state_2.bias,
+ * which this module does not have.
+ * loss_partials: apg_loss_partials_count(B) floats; loss may be NULL.
+ * workspace: apg_cartpole_learnt_fit_workspace_floats(B) device floats.  B == 0
+ * zeroes loss and grad and returns.  Every model tensor is read ON THE DEVICE
+ * when the launches run (no host read, no synchronisation, graph-capturable: a
+ * linear chain on one stream); no float atomics: the same inputs give the same
+ * bits.  Argument errors (B < 0, NULL pointers, a missing residual, both or
+ * neither of target / eval_params) are reported before any HIP call. */
+#define APG_CARTPOLE_LEARNT_G_W1 6
+#define APG_CARTPOLE_LEARNT_G_B1 326
+#define APG_CARTPOLE_LEARNT_G_W2 390
+#define APG_CARTPOLE_LEARNT_GRADS 646
+int apg_cartpole_learnt_fit_workspace_floats(int B);
+int apg_cartpole_learnt_fit_fwd_bwd(const float *state, const float *action, float dt,
+    const ApgCartpoleLearnt *model, const float *target,
+    const ApgCartpoleParams *eval_params, int B, float *loss_partials,
+    float *loss, float *grad, float *workspace, apg_stream_t stream);
+
 /* apg_cartpole_rollout_fwd_bwd through the learnt simulator: the controller
  * phase of TrainBase.run_dynamics (scripts/train_base.py:334-375) for the
  * cart-pole (scripts/train_cartpole.py:131-150, each step
