@@ -27,36 +27,44 @@ H = 10
 DRAGS = {"translational_drag": [.1, .2, .3], "rotational_drag": [.01, .02, .03]}
 
 
-def per_trajectory_cost(states, ref, u):
-    """quad_mpc_loss term by term with the batch axis kept: [B]."""
-    return (10 * ((states[:, :, :3] - ref[:, :, :3])**2).sum((1, 2))
-            + ((states[:, :, 6:9] - ref[:, :, 6:9])**2).sum((1, 2))
-            + 0.1 * (states[:, :, 9:12]**2).sum((1, 2))
-            + 0.1 * ((u[:, :, 1:] - .5)**2).sum((1, 2))
-            + 5 * ((u[:, :, 0] - .5)**2).sum(1))
+# the loss weights (pos, vel, av, rates, thrust) of torch_port.quad_mpc_loss
+WEIGHTS = (10.0, 1.0, 0.1, 0.1, 5.0)
 
 
-def cost_and_grad(model, state0, ref, u, dt):
+def per_trajectory_cost(states, ref, u, weights=None):
+    """quad_mpc_loss term by term with the batch axis kept: [B].  weights:
+    (pos, vel, av, rates, thrust), default the reference's."""
+    w_pos, w_vel, w_av, w_rates, w_thrust = WEIGHTS if weights is None else weights
+    return (w_pos * ((states[:, :, :3] - ref[:, :, :3])**2).sum((1, 2))
+            + w_vel * ((states[:, :, 6:9] - ref[:, :, 6:9])**2).sum((1, 2))
+            + w_av * (states[:, :, 9:12]**2).sum((1, 2))
+            + w_rates * ((u[:, :, 1:] - .5)**2).sum((1, 2))
+            + w_thrust * ((u[:, :, 0] - .5)**2).sum(1))
+
+
+def cost_and_grad(model, state0, ref, u, dt, weights=None):
     """(J [B], dJ/du [B,H,4]); the scalar differentiated is torch_port's own
     quad_mpc_loss over the batch (trajectories are independent, so its gradient
-    is every trajectory's own)."""
+    is every trajectory's own) - with `weights`, the sum of the weighted
+    per-trajectory costs."""
     a = u.detach().clone().requires_grad_(True)
     states = tp.unroll(model, state0, a, dt)
-    total = tp.quad_mpc_loss(states, ref, a)
+    total = (tp.quad_mpc_loss(states, ref, a) if weights is None
+             else per_trajectory_cost(states, ref, a, weights).sum())
     total.backward()
-    J = per_trajectory_cost(states.detach(), ref, a.detach())
+    J = per_trajectory_cost(states.detach(), ref, a.detach(), weights)
     total = float(total.detach())
     assert abs(float(J.sum()) - total) <= 1e-4 * abs(total)
     return J, a.grad
 
 
-def cost(model, state0, ref, u, dt):
+def cost(model, state0, ref, u, dt, weights=None):
     with torch.no_grad():
-        return per_trajectory_cost(tp.unroll(model, state0, u, dt), ref, u)
+        return per_trajectory_cost(tp.unroll(model, state0, u, dt), ref, u, weights)
 
 
 def solve_snapshots(dtype, state0, ref, u0, dt, snaps, modified_params=None, beta=BETA,
-                    alpha_thrust=ALPHA_THRUST, alpha_rate=ALPHA_RATE):
+                    alpha_thrust=ALPHA_THRUST, alpha_rate=ALPHA_RATE, weights=None):
     """One run of max(snaps) iterations -> {iters: what `solve` returns for that
     many iterations} (the iterates of a shorter solve are a prefix of a longer
     one's: nothing in the rule depends on the iteration count)."""
@@ -67,11 +75,11 @@ def solve_snapshots(dtype, state0, ref, u0, dt, snaps, modified_params=None, bet
     trace, out = [], {}
     for it in range(max(snaps) + 1):
         if it in snaps:
-            J = cost(model, s0, r, u, dt)
+            J = cost(model, s0, r, u, dt, weights)
             out[it] = dict(u=u.clone(), cost=J, trace=torch.stack(trace + [J]))
         if it == max(snaps):
             break
-        J, g = cost_and_grad(model, s0, r, u, dt)
+        J, g = cost_and_grad(model, s0, r, u, dt, weights)
         trace.append(J)
         m = beta * m + alpha * g
         u = (u - m).clamp(0.0, 1.0)
@@ -225,7 +233,13 @@ def _options(iters, beta=BETA, alpha_thrust=ALPHA_THRUST, alpha_rate=ALPHA_RATE)
     return _capi.ApgQuadMpcOptions(int(iters), beta, alpha_thrust, alpha_rate)
 
 
-def twin_solve(tw, state0, ref, u0, dt, iters, modified_params=None):
+def _weights(weights=None):
+    from apg_trajectory_tracking_amd import functional as F
+    names = ("pos", "vel", "av", "rates", "thrust")
+    return F.quad_loss_weights(**dict(zip(names, WEIGHTS if weights is None else weights)))
+
+
+def twin_solve(tw, state0, ref, u0, dt, iters, modified_params=None, weights=None):
     """apg_quad_mpc_solve_cpu on [B,12] / [B,H,C] / [B,H,4] float32 tensors ->
     dict(u, cost, trace) as `solve` returns them."""
     from apg_trajectory_tracking_amd import functional as F
@@ -236,7 +250,7 @@ def twin_solve(tw, state0, ref, u0, dt, iters, modified_params=None):
     cost_out, trace = torch.zeros(B), torch.zeros(iters + 1, B)
     rc = tw.apg_quad_mpc_solve_cpu(
         s.data_ptr(), r.data_ptr(), C, dt, ctypes.byref(_params(modified_params)),
-        ctypes.byref(F.quad_loss_weights()), ctypes.byref(_options(iters)), B, Hh,
+        ctypes.byref(_weights(weights)), ctypes.byref(_options(iters)), B, Hh,
         u.data_ptr(), cost_out.data_ptr(), trace.data_ptr())
     assert rc == 0, tw.apg_cpu_last_error_string()
     return dict(u=u.permute(2, 0, 1).contiguous(), cost=cost_out, trace=trace)
