@@ -241,6 +241,10 @@ SIGNATURES = {
         _P, _P, _P, _I, _F, ctypes.POINTER(ApgQuadParams),
         ctypes.POINTER(ApgQuadLossWeights), _I, _I, _I, _P, _P, _P, _P, _P,
         ctypes.POINTER(ApgDeferredLoss), _P],
+    "apg_quad_rollout_fwd_bwd_chained": [
+        _P, _P, _P, _I, _F, ctypes.POINTER(ApgQuadParams),
+        ctypes.POINTER(ApgQuadLossWeights), _I, _I, _I, _P, _P, _P, _P, _P,
+        ctypes.POINTER(ApgDeferredLoss), _P],
     "apg_quad_rollout_fwd": [_P, _P, _F, ctypes.POINTER(ApgQuadParams), _I,
                              _I, _I, _P, _P],
     "apg_quad_learnt_rollout_fwd_bwd": [
@@ -365,6 +369,10 @@ SIGNATURES = {
         _P, _P, _P, _F, ctypes.POINTER(ApgWingParams),
         ctypes.POINTER(ApgWingLossWeights), _I, _I, _I, _P, _P, _P, _P, _P,
         ctypes.POINTER(ApgDeferredLoss), _P],
+    "apg_wing_rollout_fwd_bwd_chained": [
+        _P, _P, _P, _F, ctypes.POINTER(ApgWingParams),
+        ctypes.POINTER(ApgWingLossWeights), _I, _I, _I, _P, _P, _P, _P, _P,
+        ctypes.POINTER(ApgDeferredLoss), _P],
     "apg_wing_rollout_fwd": [_P, _P, _F, ctypes.POINTER(ApgWingParams), _I,
                              _I, _I, _P, _P],
     "apg_wing_set_two_per_lane": [_I],
@@ -414,6 +422,9 @@ SIGNATURES = {
         _P, _F, ctypes.POINTER(ApgCartpoleParams), ctypes.POINTER(ApgCartpoleLearnt),
         ctypes.POINTER(ApgCartpoleParams), ctypes.POINTER(ApgCartpoleMpcOptions),
         _I, _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "apg_launch_chain_prepare": [_P],
+    "apg_launch_chain_flush": [_P],
+    "apg_launch_chain_set_lane_priority": [_I],
     "apg_reduce_loss_partials": [_P, _I, _P, _P],
     "apg_loss_partials_count": [_I],
     "apg_stream_copy": [_P, _P, ctypes.c_longlong, _P],

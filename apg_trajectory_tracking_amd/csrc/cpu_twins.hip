@@ -14,6 +14,7 @@
 
 #include "apg_cpu.h"
 #include "apg_cpu_cartpole_fit.h"
+#include "apg_cpu_launch_chain.h"
 #include "apg_cpu_quad_fit.h"
 #include "apg_cpu_wing_fit.h"
 #include "apg_cpu_wing_learnt.h"
@@ -22,6 +23,7 @@
 #include "cartpole_math.h"
 #include "cartpole_mpc_math.h"
 #include "cartpole_rollout_math.h"
+#include "launch_chain.h"
 #include "quad_fit_math.h"
 #include "quad_math.h"
 #include "quad_mpc_math.h"
@@ -1036,6 +1038,43 @@ int apg_cartpole_mpc_closed_loop_cpu(const float *state0, float dt,
     cart_mpc_loop_batch<10>(state0, cp, r, cm, *opt, rule, B, steps, upright, vel_sum, vel_sq,
                             states, actions, cost);
   return APG_OK;
+}
+
+}  // extern "C"
+
+// ---- the launch chain's bookkeeping (apg_cpu_launch_chain.h) ---------------
+extern "C" {
+
+void *apg_cpu_chain_new(void) { return new LaunchChain; }
+void apg_cpu_chain_free(void *chain) { delete static_cast<LaunchChain *>(chain); }
+int apg_cpu_chain_empty(const void *chain) {
+  return static_cast<const LaunchChain *>(chain)->empty();
+}
+
+void apg_cpu_chain_launch(void *chain, const float *partials, int count, float *loss,
+                          const float *after_partials, int after_count,
+                          float *after_loss, ApgCpuChainStep *step) {
+  ChainLaunch L{partials, count, loss, {}};
+  if (after_loss) L.after = ChainReduce{after_partials, after_count, after_loss};
+  const ChainStep s = static_cast<LaunchChain *>(chain)->launch(L);
+  step->lane = s.lane, step->fork = s.fork;
+  step->pre_lane = s.pre_lane, step->edge_from = s.edge_from;
+  step->pre = ApgCpuChainReduce{s.pre.partials, s.pre.count, s.pre.loss};
+  step->fold = ApgCpuChainReduce{s.fold.partials, s.fold.count, s.fold.loss};
+}
+
+void apg_cpu_chain_flush(void *chain, ApgCpuChainReduce *lane0, int *n0,
+                         ApgCpuChainReduce *lane1, int *n1, int cap, int *join) {
+  const ChainFlush f = static_cast<LaunchChain *>(chain)->flush();
+  ApgCpuChainReduce *out[2] = {lane0, lane1};
+  int *n[2] = {n0, n1};
+  for (int m = 0; m < 2; ++m) {
+    *n[m] = (int)f.reduce[m].size();
+    for (int i = 0; i < *n[m] && i < cap; ++i)
+      out[m][i] = ApgCpuChainReduce{f.reduce[m][i].partials, f.reduce[m][i].count,
+                                    f.reduce[m][i].loss};
+  }
+  *join = f.join;
 }
 
 }  // extern "C"

@@ -871,10 +871,25 @@ class RolloutPlan:
     loss_mode:
       "eager"    the launch is followed by the small fixed-order reduction
                  kernel; `out["loss"]` is valid after this launch.
-      "deferred" the launch only leaves per-wave partials; the NEXT launch
-                 given `after=<this plan>` folds their reduction into its own
-                 kernel (ApgDeferredLoss), `flush()` reduces the last one.
+      "deferred" the launch only leaves per-wave partials; a LATER launch
+                 folds their reduction into its own kernel (ApgDeferredLoss).
+                 Launches given `after=<the plan launched before>` form a
+                 launch chain (include/apg.h): the library runs them as two
+                 overlapping lanes - the caller's stream and a stream of its
+                 own on another hardware queue - and kernel i+2 reduces kernel
+                 i.  While the chain is open, losses and outputs are ordered
+                 on no stream the caller sees, and the plans' inputs must not
+                 be refilled: `flush()` (of any plan of the chain) enqueues
+                 the reductions still owed and joins the second lane, after
+                 which everything the chain wrote is ordered on the caller's
+                 stream.  Every chain ends with flush(); under
+                 torch.cuda.graph a chain is flushed before the capture ends,
+                 and an eager chain before a capture begins.  An even number
+                 of plans in rotation keeps the lanes independent; an odd
+                 number, or relaunching a plan, costs a cross-lane event edge.
       "none"     partials only.
+    Eager and none launches, and the un-chained C entry points, stay serial on
+    the caller's stream.
     """
 
     def __init__(self, system, state0, actions, ref, dt, params, weights=None,
@@ -911,13 +926,19 @@ class RolloutPlan:
         head = [ptr(state0), ptr(actions), ptr(ref)]
         if system == "quad":
             head.append(_seq_shape(ref, lay)[2])
+        self._stream = stream_of(state0)
+        if loss_mode == "deferred":
+            # the chained entry points: lane, in-kernel reduction and
+            # cross-lane waits are decided in the library (csrc/launch_chain.h)
+            fn = getattr(lib(), f"apg_{system}_rollout_fwd_bwd_chained")
+            check(lib().apg_launch_chain_prepare(self._stream),
+                  "apg_launch_chain_prepare")
         self._fn = fn
         self._head = head + [
             float(dt), ctypes.byref(params), ctypes.byref(weights), B, H, lay,
             ptr(o["loss_partials"]),
-            ptr(o["loss"]) if loss_mode == "eager" else None,
+            ptr(o["loss"]) if loss_mode != "none" else None,
             ptr(o["grad_actions"]), ptr(o["grad_state0"]), ptr(o["states"])]
-        self._stream = stream_of(state0)
         self._args = tuple(self._head + [None, self._stream])
         self._args_after = {}
 
@@ -934,8 +955,11 @@ class RolloutPlan:
         return args
 
     def launch(self, after=None):
-        """Enqueue the rollout.  `after`: an earlier-launched *deferred* plan
-        (not this one) whose loss this launch should reduce on the side."""
+        """Enqueue the rollout.  `after`: the *deferred* plan launched before
+        this one (not this one): its loss becomes due, and this launch joins
+        its chain on the other lane."""
+        if after is not None and self.loss_mode != "deferred":
+            raise ValueError("after= needs loss_mode='deferred'")
         args = self._args if after is None else self._deferred_args(after)
         code = self._fn(*args)
         if code != 0:
@@ -943,8 +967,11 @@ class RolloutPlan:
         return self.out
 
     def flush(self):
-        """Reduce this plan's partials now (end of a deferred chain)."""
-        reduce_loss_partials(self.out["loss_partials"], self.out["loss"])
+        """End the deferred chain on this plan's stream: every loss of the
+        chain is reduced, and its outputs are ordered on that stream."""
+        if self.loss_mode != "deferred":
+            return reduce_loss_partials(self.out["loss_partials"], self.out["loss"])
+        check(lib().apg_launch_chain_flush(self._stream), "apg_launch_chain_flush")
         return self.out["loss"]
 
 

@@ -10,7 +10,8 @@
  * Conventions
  *  - All buffers are DEVICE pointers owned by the caller (e.g. the PyTorch
  *    caching allocator); the library allocates nothing and keeps no state
- *    except a thread-local error string.
+ *    except a thread-local error string and, per stream that asked for one,
+ *    the second lane of a launch chain (apg_launch_chain_prepare).
  *  - All arithmetic is IEEE fp32, as in the reference
  *    (neural_control/dynamics/quad_dynamics_flightmare.py:216).
  *  - Every call only ENQUEUES work on `stream` (a hipStream_t, may be NULL
@@ -88,7 +89,9 @@ enum {
  * That takes the second kernel of the `loss != NULL` mode off the per-step
  * critical path: step i's scalar loss is materialised by step i+1's launch,
  * the last one by apg_reduce_loss_partials().  `prev_partials` must not alias
- * the `loss_partials` of the launch it is passed to (ping-pong two buffers). */
+ * the `loss_partials` of the launch it is passed to (ping-pong two buffers).
+ * Such a chain is serial; the `..._chained` entry points ("launch chain"
+ * below) run the same launches as two overlapping lanes. */
 typedef struct ApgDeferredLoss {
   const float *prev_partials; /* [prev_count] written by an earlier launch */
   int prev_count;
@@ -1296,6 +1299,67 @@ int apg_cartpole_mpc_closed_loop(const float *state0, float dt, const ApgCartpol
                                  int mode, float thresh_div, int burn_in, int *steps,
                                  int *upright, double *vel_sum, double *vel_sq, float *states,
                                  float *actions, float *cost, apg_stream_t stream);
+
+/* ------------------------------------------------------- launch chain --- */
+/* A chain of deferred-loss rollout launches run as TWO overlapping lanes.
+ * Launched one `after` the other through the entry points above, kernel i+1
+ * reads kernel i's partials in its first instructions: the launches are
+ * serial, and each pays its ramp, its write-drain tail and the kernel boundary
+ * with the memory system partly idle.  The chained forms below take the same
+ * arguments and compute the same numbers, but place the launches alternately
+ * on lane 0 (`stream`) and lane 1 (a stream the library owns, on another
+ * hardware queue), and let a kernel reduce the oldest launch of its OWN lane
+ * that a later launch named as `deferred` - kernel i+2 reduces kernel i - so
+ * the lanes share no dependency and consecutive launches overlap
+ * (csrc/launch_chain.h has the rules, DESIGN.md 3.1 the measurements).
+ *   loss      [1], required: receives this launch's loss once it is reduced
+ *   deferred  NULL, or the partials / count / loss of the plan launched before
+ *             (any earlier launch; not this launch's own buffers)
+ * A plan is identified by its `loss` pointer; its inputs must not be written
+ * while the chain is open.  A launch whose buffers were last written on the
+ * other lane is ordered behind it by an event edge (an odd number of rotating
+ * plans, a relaunched plan); an even number of plans in rotation never needs
+ * one.
+ * Contract: between the first chained launch and apg_launch_chain_flush the
+ * outputs and losses are ordered on NO stream the caller sees.  The flush
+ * enqueues the reductions still owed (each plan's loss is written exactly once
+ * per launch, the same fixed-order sum as apg_reduce_loss_partials), joins
+ * lane 1 into `stream` and empties the chain: after it, everything the chain
+ * wrote is ordered on `stream`.  Work enqueued on `stream` before the first
+ * launch of a chain precedes both lanes.  The calls are capturable
+ * (hipEventRecord / hipStreamWaitEvent only: lane 1 joins a capture of
+ * `stream` at the fork and leaves it at the flush); a chain must be flushed
+ * before a capture of `stream` ends and before one begins.
+ * apg_launch_chain_prepare(stream) creates lane 1 and its events for `stream`
+ * on the current device - once, outside any capture, before the first chained
+ * launch (again is a no-op); they live as long as the process.  This is the
+ * one piece of state the library keeps besides the error string. */
+int apg_launch_chain_prepare(apg_stream_t stream);
+int apg_launch_chain_flush(apg_stream_t stream);
+int apg_quad_rollout_fwd_bwd_chained(const float *state0, const float *actions,
+                                     const float *ref, int ref_cols, float dt,
+                                     const ApgQuadParams *params,
+                                     const ApgQuadLossWeights *weights, int B, int H,
+                                     int layout, float *loss_partials, float *loss,
+                                     float *grad_actions, float *grad_state0,
+                                     float *states_out,
+                                     const ApgDeferredLoss *deferred,
+                                     apg_stream_t stream);
+int apg_wing_rollout_fwd_bwd_chained(const float *state0, const float *actions,
+                                     const float *ref, float dt,
+                                     const ApgWingParams *params,
+                                     const ApgWingLossWeights *weights, int B, int H,
+                                     int layout, float *loss_partials, float *loss,
+                                     float *grad_actions, float *grad_state0,
+                                     float *states_out,
+                                     const ApgDeferredLoss *deferred,
+                                     apg_stream_t stream);
+/* Measurement hook, process-wide, for streams prepared AFTER the call: the
+ * stream priority of lane 1.  0 (default) a priority other than the caller's
+ * (the runtime keeps its hardware-queue pools per priority, so the lanes never
+ * share a queue); 1 the caller's own (placement left to the runtime's pool);
+ * 2 the lowest.  Nothing in the environment influences the choice. */
+int apg_launch_chain_set_lane_priority(int mode);
 
 /* --------------------------------------------------------------- misc --- */
 /* loss[0] = fixed-order sum of partials[0..n) (one small kernel). */
