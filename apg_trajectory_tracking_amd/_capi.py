@@ -170,6 +170,36 @@ class ApgCartpolePolicy(ctypes.Structure):
         "w0", "b0", "w1", "b1", "w2", "b2", "w3", "b3", "w_out", "b_out")]
 
 
+class ApgCartpolePolicyGrads(ctypes.Structure):
+    """Where apg_cartpole_mlp_train_step puts each parameter's gradient."""
+    _fields_ = ApgCartpolePolicy._fields_
+
+
+class ApgCartpoleSgdUpdate(ctypes.Structure):
+    """apg_cartpole_mlp_train_step's optimizer part: momentum SGD on the
+    policy's tensors and the optimizer's momentum buffers."""
+    _fields_ = [("lr", ctypes.c_double), ("momentum", ctypes.c_double),
+                ("param", ApgCartpolePolicyGrads),
+                ("momentum_buf", ApgCartpolePolicyGrads)]
+
+
+# include/apg.h, APG_CARTPOLE_POLICY_G_*: where each tensor's gradient starts in
+# the flat gradient of the cart-pole controller step (simple_model.Net's
+# named_parameters() order); fc_out.bias follows fc_out.weight [H][32]
+CARTPOLE_POLICY_PARAMS = ("fc0.weight", "fc0.bias", "fc1.weight", "fc1.bias",
+                          "fc2.weight", "fc2.bias", "fc3.weight", "fc3.bias",
+                          "fc_out.weight", "fc_out.bias")
+CARTPOLE_POLICY_G = (0, 128, 160, 2208, 2272, 6368, 6432, 8480, 8512)
+
+
+def cartpole_policy_offsets(H):
+    """{parameter name: (start, shape)} in the flat gradient, and its length."""
+    shapes = ((32, 4), (32,), (64, 32), (64,), (64, 64), (64,), (32, 64), (32,),
+              (H, 32), (H,))
+    starts = CARTPOLE_POLICY_G + (8512 + 32 * H,)
+    return (dict(zip(CARTPOLE_POLICY_PARAMS, zip(starts, shapes))), 8512 + 33 * H)
+
+
 CARTPOLE_LEARNT_FIELDS = ("max_force_mag", "masspole", "length", "friction",
                           "total_mass", "polemass_length")
 
@@ -389,6 +419,11 @@ SIGNATURES = {
     "apg_cartpole_mlp_closed_loop": [
         _P, _F, ctypes.POINTER(ApgCartpoleParams), ctypes.POINTER(ApgCartpolePolicy),
         _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "apg_cartpole_mlp_train_step_workspace_floats": [_I, _I],
+    "apg_cartpole_mlp_train_step": [
+        _P, _P, _F, ctypes.POINTER(ApgCartpoleParams), ctypes.POINTER(ApgCartpolePolicy),
+        _I, _I, _P, _P, ctypes.POINTER(ApgCartpolePolicyGrads), _P, _P,
+        ctypes.POINTER(ApgCartpoleSgdUpdate), _P],
     "apg_cartpole_learnt_param_count": [],
     "apg_cartpole_learnt_workspace_floats": [_I],
     "apg_cartpole_learnt_step_fwd": [_P, _P, _F, ctypes.POINTER(ApgCartpoleLearnt), _I,

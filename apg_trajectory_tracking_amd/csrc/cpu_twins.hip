@@ -14,6 +14,7 @@
 
 #include "apg_cpu.h"
 #include "apg_cpu_cartpole_fit.h"
+#include "apg_cpu_cartpole_train.h"
 #include "apg_cpu_launch_chain.h"
 #include "apg_cpu_quad_fit.h"
 #include "apg_cpu_wing_fit.h"
@@ -23,6 +24,7 @@
 #include "cartpole_math.h"
 #include "cartpole_mpc_math.h"
 #include "cartpole_rollout_math.h"
+#include "cartpole_train_math.h"
 #include "launch_chain.h"
 #include "quad_fit_math.h"
 #include "quad_math.h"
@@ -657,6 +659,112 @@ int apg_cartpole_learnt_fit_fwd_bwd_cpu(const float *state, const float *action,
   for (int e = 0; e < kCartFitRow; ++e) {
     const int dest = cart_fit_dest(e);
     if (dest >= 0) grad[dest] = acc[e];
+  }
+  return APG_OK;
+}
+
+// apg_cpu_cartpole_train.h: cart_train_kernel (cartpole_train.hip) sample for
+// sample - the layers of cartpole_train_math.h one unit at a time, the rollout
+// of cartpole_rollout_math.h, every gradient element summed in sample order -
+// then the last stage (gradient out, momentum SGD) element by element
+int apg_cartpole_mlp_train_step_cpu(const float *in_state, const float *state0, float dt,
+                                    const ApgCartpoleParams *params,
+                                    const ApgCartpolePolicy *policy, int B, int H,
+                                    float *loss_partials, float *loss,
+                                    const ApgCartpolePolicyGrads *grads, float *actions_out,
+                                    float *workspace, const ApgCartpoleSgdUpdate *update) {
+  (void)workspace;
+  if (B < 1) return fail("B must be >= 1 (got %d)", B);
+  if (int e = check_h(H)) return e;
+  if (!params || !policy || !grads) return fail("params / policy / grads is NULL");
+  const ApgCartpolePolicy &P = *policy;
+  if (!P.w0 || !P.b0 || !P.w1 || !P.b1 || !P.w2 || !P.b2 || !P.w3 || !P.b3 || !P.w_out ||
+      !P.b_out)
+    return fail("policy weight pointer is NULL");
+  auto tensors = [](const ApgCartpolePolicyGrads &g, float *(&t)[10]) {
+    float *v[10] = {g.w0, g.b0, g.w1, g.b1, g.w2, g.b2, g.w3, g.b3, g.w_out, g.b_out};
+    bool all = true;
+    for (int q = 0; q < 10; ++q) t[q] = v[q], all = all && v[q];
+    return all;
+  };
+  float *tg[10], *tp[10], *tm[10];
+  if (!tensors(*grads, tg)) return fail("grads: pointer is NULL");
+  if (update && (!tensors(update->param, tp) || !tensors(update->momentum_buf, tm)))
+    return fail("update: parameter / momentum pointer is NULL");
+  if (update && !(update->lr == update->lr && update->momentum == update->momentum))
+    return fail("update: lr / momentum is NaN");
+  if (!in_state || !state0 || !loss_partials)
+    return fail("in_state / state0 / loss_partials must not be NULL");
+  const CartConst c = make_const(*params, dt);
+  std::vector<float> G((size_t)cpt_grads(H), 0.f), pre((size_t)H * 4), out((size_t)H);
+  // y = tanh(W x + b), one unit at a time
+  auto fwd = [](const float *W, const float *b, int N, int K, const float *x, float *y) {
+    for (int u = 0; u < N; ++u) {
+      float z[1] = {b[u]};
+      cpt_dense<1>(
+          z, K, [&](int, int j) { return W[u * K + j]; }, [&](int j) { return x[j]; });
+      y[u] = tanhf(z[0]);
+    }
+  };
+  // a layer's reverse: its weights' and bias' cotangents from dz [N] and its
+  // input x [K]; then (x_is_tanh) the cotangent of the input's pre-activation
+  // over x
+  auto bwd = [&](const float *W, int N, int K, const float *dz, float *x, int gw, int gb,
+                 bool x_is_tanh) {
+    float acc[kCptH1];
+    for (int j = 0; x_is_tanh && j < K; ++j) {
+      float z[1] = {0.f};
+      cpt_dense<1>(
+          z, N, [&](int, int m) { return W[m * K + j]; }, [&](int m) { return dz[m]; });
+      acc[j] = z[0];
+    }
+    for (int m = 0; m < N; ++m) {
+      float once = G[gb + m], again = 0.f;   // (the bias takes dz once per sample)
+      for (int j = 0; j < K; ++j) {
+        float g1[1] = {G[gw + m * K + j]};
+        cpt_wgrad<1>(g1, j == 0 ? once : again, dz[m], [&](int) { return x[j]; });
+        G[gw + m * K + j] = g1[0];
+      }
+      G[gb + m] = once;
+    }
+    for (int j = 0; x_is_tanh && j < K; ++j) x[j] = cpt_dtanh(acc[j], x[j]);
+  };
+  LossOut lo{loss_partials, loss};
+  auto ST = [&](int k, int i) -> float & { return pre[k * 4 + i]; };
+  for (int b = 0; b < B; ++b) {
+    float x[kCptIn], h0[kCptH0], h1[kCptH1], h2[kCptH2], h3[kCptH3];
+    x[0] = 0.f;                            // Net.forward zeroes column 0
+    for (int i = 1; i < kCptIn; ++i) x[i] = in_state[(size_t)b * kCptIn + i];
+    fwd(P.w0, P.b0, kCptH0, kCptIn, x, h0);
+    fwd(P.w1, P.b1, kCptH1, kCptH0, h0, h1);
+    fwd(P.w2, P.b2, kCptH2, kCptH1, h1, h2);
+    fwd(P.w3, P.b3, kCptH3, kCptH2, h2, h3);
+    fwd(P.w_out, P.b_out, H, kCptH3, h3, out.data());
+    for (int k = 0; actions_out && k < H; ++k) actions_out[(size_t)b * H + k] = out[k];
+    auto action = [&](int k) { return out[k]; };
+    float s0[4], s[4], lam[4];
+    for (int i = 0; i < 4; ++i) s0[i] = state0[(size_t)b * 4 + i];
+    lo.add(b, B, cart_rollout_forward(
+                     H, s0, s, action, ST, [&](float (&v)[4], float a) { cart_step(v, a, c); },
+                     [](int, const float (&)[4]) {}));
+    cart_rollout_reverse(
+        H, s0, s, lam, action, ST,
+        [&](float (&l)[4], const float (&p)[4], float a) {
+          return cart_step_adjoint(l, p[1], p[3], cart_step_aux(p, a, c), c);
+        },
+        [&](int k, float g) { out[k] = cpt_dtanh(g, out[k]); });
+    bwd(P.w_out, H, kCptH3, out.data(), h3, kCptGWout, kCptGWout + kCptH3 * H, true);
+    bwd(P.w3, kCptH3, kCptH2, h3, h2, kCptGW3, kCptGB3, true);
+    bwd(P.w2, kCptH2, kCptH1, h2, h1, kCptGW2, kCptGB2, true);
+    bwd(P.w1, kCptH1, kCptH0, h1, h0, kCptGW1, kCptGB1, true);
+    bwd(P.w0, kCptH0, kCptIn, h0, x, kCptGW0, kCptGB0, false);
+  }
+  lo.finish(B);
+  for (int e = 0; e < cpt_grads(H); ++e) {
+    int q, off;
+    cpt_locate(e, H, q, off);
+    tg[q][off] = G[e];
+    if (update) cpt_sgd(G[e], update->lr, update->momentum, tp[q][off], tm[q][off]);
   }
   return APG_OK;
 }

@@ -7,6 +7,7 @@ reference's row-major ones (`layout="aos"`) unless stated; the fused rollouts
 also accept the device-native SoA layout (`layout="soa"`, batch fastest).
 """
 import ctypes
+import math
 
 import torch
 
@@ -2425,6 +2426,101 @@ def cartpole_policy_optimality_gap(net, state0, dt, params, iters=50):
     warm = cartpole_mpc_solve(state0, dt, params, u0=acts, iters=iters, **kw)["cost"]
     cold = cartpole_mpc_solve(state0, dt, params, iters=iters, **kw)["cost"]
     return dict(policy=policy, mpc_from_policy=warm, mpc=cold, actions=acts)
+
+
+# ------------------------------------- the controller step with the policy inside
+def _cartpole_policy_tensors(net):
+    """The ten parameters of simple_model.Net in named_parameters() order
+    (= _capi.CARTPOLE_POLICY_PARAMS = the fields of ApgCartpolePolicy)."""
+    return [p for l in (net.fc0, net.fc1, net.fc2, net.fc3, net.fc_out)
+            for p in (l.weight, l.bias)]
+
+
+def cartpole_policy_fusable(net, H):
+    """Whether `net` is what the fused cart-pole controller step serves: the
+    stock simple_model.Net with shapes 4-32-64-64-32-H, H within the rollout's
+    range, every parameter a contiguous float32 tensor that requires grad, all
+    on one CUDA device."""
+    from .models.simple_model import Net
+    if type(net) is not Net or not 1 <= int(H) <= _capi.MAX_HORIZON:
+        return False
+    try:
+        tensors = _cartpole_policy_tensors(net)
+    except AttributeError:
+        return False
+    named = list(net.named_parameters())
+    shapes = [sh for _, sh in _capi.cartpole_policy_offsets(int(H))[0].values()]
+    return (tuple(n for n, _ in named) == _capi.CARTPOLE_POLICY_PARAMS
+            and all(a is b for a, (_, b) in zip(tensors, named))
+            and all(isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_cuda
+                    and t.is_contiguous() and t.requires_grad and tuple(t.shape) == sh
+                    for t, sh in zip(tensors, shapes))
+            and len({t.device for t in tensors}) == 1)
+
+
+def cartpole_policy_train_step(net, in_state, state0, dt, params, update=None,
+                               want_actions=False):
+    """The controller step of TrainCartpole.run_epoch (scripts/train_cartpole.py:
+    127-155) in one fused call (apg_cartpole_mlp_train_step): actions =
+    net(in_state) - column 0 read as 0, `in_state` itself is not written, no
+    clone needed -, the rollout from `state0` with make_reference and
+    cartpole_loss_mpc, the reverse sweep, the cotangent chain through the five
+    tanh layers and every parameter's gradient summed over the batch.  Returns
+    dict(loss [1], flat, grads): `flat` holds the gradients in
+    named_parameters() order (8 512 + 33 H floats) plus one trailing slot for the
+    loss - the all-reduce message of TrainBase._step_direct -, `grads` is {name:
+    view of flat}; with `want_actions` also actions [B,H,1].
+    `update` = (lr, momentum, {parameter name: momentum buffer}): the step also
+    APPLIES torch.optim.SGD's update (buf = momentum buf + grad, p -= lr buf) to
+    the network's parameters and these buffers, in its last stage.
+    The parameters are read on the device when the launches run: no host read,
+    no synchronisation, one stream - capturable in a graph, update included."""
+    H = net.fc_out.weight.shape[0] if hasattr(net, "fc_out") else 0
+    if not cartpole_policy_fusable(net, H):
+        raise ValueError("fused controller step expects simple_model.Net(4, H), H in "
+                         f"[1, {_capi.MAX_HORIZON}], as contiguous fp32 parameters that "
+                         "require grad on one CUDA device")
+    tensors = [t.detach() for t in _cartpole_policy_tensors(net)]
+    in_state, state0 = _f32c(in_state), _f32c(state0)
+    require_device(in_state, state0, *tensors)
+    if (in_state.dim() != 2 or in_state.shape[1] != 4 or state0.shape != in_state.shape
+            or in_state.shape[0] < 1):
+        raise ValueError("in_state / state0 [B,4] with B >= 1 expected, got "
+                         f"{tuple(in_state.shape)} / {tuple(state0.shape)}")
+    B, dev = in_state.shape[0], in_state.device
+    at, n = _capi.cartpole_policy_offsets(H)
+    flat = torch.empty(n + 1, dtype=torch.float32, device=dev)
+    grads = {name: flat[o:o + math.prod(sh)].view(sh) for name, (o, sh) in at.items()}
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    parts = torch.empty(_capi.loss_partials_count(B), dtype=torch.float32, device=dev)
+    ws = torch.empty(max(lib().apg_cartpole_mlp_train_step_workspace_floats(B, H), 1),
+                     dtype=torch.float32, device=dev)
+    actions = (torch.empty(B, H, 1, dtype=torch.float32, device=dev)
+               if want_actions else None)
+    names = _capi.CARTPOLE_POLICY_PARAMS
+    pol = _capi.ApgCartpolePolicy(*[ptr(t) for t in tensors])
+    gs = _capi.ApgCartpolePolicyGrads(*[ptr(grads[k]) for k in names])
+    upd, held = None, []
+    if update is not None:
+        lr, momentum, bufs = update
+        held = [bufs[k] for k in names]
+        require_device(*held)
+        if any(b.shape != t.shape for b, t in zip(held, tensors)):
+            raise ValueError("update: a momentum buffer has another shape than its parameter")
+        upd = ctypes.byref(_capi.ApgCartpoleSgdUpdate(
+            float(lr), float(momentum),
+            _capi.ApgCartpolePolicyGrads(*[ptr(t) for t in tensors]),
+            _capi.ApgCartpolePolicyGrads(*[ptr(b) for b in held])))
+    check(lib().apg_cartpole_mlp_train_step(
+        ptr(in_state), ptr(state0), float(dt), ctypes.byref(params), ctypes.byref(pol), B, H,
+        ptr(parts), ptr(loss), ctypes.byref(gs), ptr(actions), ptr(ws), upd,
+        stream_of(in_state)), "apg_cartpole_mlp_train_step")
+    if update is not None and not torch.cuda.is_current_stream_capturing():
+        note_in_kernel_update(tensors + held)
+    out = dict(loss=loss, flat=flat, grads=grads)
+    if want_actions:
+        out["actions"] = actions
+    return out
 
 
 # --------------------------- concurrent mode with the policy inside (config 2)

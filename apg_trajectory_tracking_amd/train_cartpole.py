@@ -1,8 +1,10 @@
 """Drop-in for scripts/train_cartpole.py:30-165 (`TrainCartpole`) restricted
 to the APG hot path: `run_epoch` (:118-165) with `make_reference` (:103-110).
 The controller branch is one fused HIP launch (make_reference + H x cartpole
-dynamics + cartpole_loss_mpc + adjoint).  Quirks kept: the policy ends in
-tanh with NO sigmoid (:127-130), `simple_model.Net` zeroes column 0 of its
+dynamics + cartpole_loss_mpc + adjoint); with the stock policy (`fused_policy`)
+the policy's forward, its reverse pass, the weight gradients and momentum SGD
+run inside the same call (apg_cartpole_mlp_train_step).  Quirks kept: the
+policy ends in tanh with NO sigmoid (:127-130), `simple_model.Net` zeroes column 0 of its
 input in place, run_epoch divides by the last batch index (:163).
 
 With a LearntCartpoleDynamics as train dynamics (`train_norm_dynamics`, the
@@ -163,6 +165,45 @@ class TrainCartpole(TrainBase):
         return self._finish_fused_fit(
             res["loss"], F.cartpole_learnt_fit_grad_views(d, res["grad"]))
 
+    fused_policy = True   # controller step with the stock policy inside the call
+
+    def _fusable_policy(self, in_state, current_state):
+        """The fused controller step (functional.cartpole_policy_train_step)
+        serves the stock simple_model.Net(4, horizon) - contiguous float32
+        parameters that require grad - rolled out through the plain analytic
+        CartpoleDynamics, with policy and batch on one CUDA device.  Anything
+        else - a learnt simulator, another policy, `fused_policy` False - takes
+        the tape: net(in_state.clone()), the fused rollout, loss.backward().
+        On by default for every batch size, under the rule of `_fusable_fit`:
+        measured against the tape at (B, H) = (8, 10), (64, 10), (64, 5) and
+        (65 536, 10) it is ahead by more than both ways' chunk spreads at every
+        size (profiles/cartpole_train_timing.jsonl)."""
+        from .dynamics.cartpole_dynamics import CartpoleDynamics
+        if not (self.fused_policy and self.action_dim == 1 and self.state_size == 4
+                and type(self.train_dynamics) is CartpoleDynamics
+                and F.cartpole_policy_fusable(self.net, self.horizon)):
+            return False
+        dev = self.net.fc0.weight.device
+        return all(t.device == dev and t.dtype == torch.float32 and t.is_contiguous()
+                   and t.dim() == 2 and t.shape[1] == 4 and t.shape[0] >= 1
+                   and not t.requires_grad
+                   for t in (in_state, current_state))
+
+    def _fused_policy_step(self, in_state, current_state):
+        """One controller step in one fused call: loss and every `.grad`, and -
+        where `_in_kernel_update` allows it (one process, plain momentum SGD, no
+        step hooks) - the optimizer's update inside the call; otherwise
+        (all-reduce,) optimizer.step() as `_step` does.  `in_state` is read, not
+        written: no clone."""
+        names = _capi.CARTPOLE_POLICY_PARAMS
+        upd = self._in_kernel_update(
+            names=names, tensors=F._cartpole_policy_tensors(self.net))
+        res = F.cartpole_policy_train_step(
+            self.net, in_state, current_state, self.delta_t,
+            self.train_dynamics.params, update=upd)
+        return self._step_direct(res["loss"].reshape(()), res["grads"], res["flat"],
+                                 stepped=upd is not None)
+
     def run_epoch(self, train="controller", epoch=0):
         """scripts/train_cartpole.py:118-165.  train "dynamics" fits a
         learnable simulator (TrainBase.train_dynamics_model) on the policy's
@@ -186,6 +227,10 @@ class TrainCartpole(TrainBase):
                     actions, (-1, self.horizon, self.action_dim))
                 loss = self.train_dynamics_model(current_state, action_seq).detach()
                 self.count_finetune_data += len(current_state)
+                running_loss = loss if running_loss is None else running_loss + loss
+                continue
+            if self._fusable_policy(in_state, current_state):
+                loss = self._fused_policy_step(in_state, current_state).detach()
                 running_loss = loss if running_loss is None else running_loss + loss
                 continue
             # the policy zeroes column 0 of its input in place: hand it a

@@ -1114,8 +1114,8 @@ typedef struct ApgCartpolePolicy {
   const float *b2;     /* [64] */
   const float *w3;     /* [32][64] fc3.weight */
   const float *b3;     /* [32] */
-  const float *w_out;  /* [H][32]  fc_out.weight (row 0 read) */
-  const float *b_out;  /* [H]      (entry 0 read) */
+  const float *w_out;  /* [H][32]  fc_out.weight (the closed loops read row 0, */
+  const float *b_out;  /* [H]      entry 0; the train step reads all H rows) */
 } ApgCartpolePolicy;
 
 enum { APG_CARTPOLE_BALANCE = 0, APG_CARTPOLE_SWINGUP = 1 };
@@ -1147,6 +1147,62 @@ int apg_cartpole_mlp_closed_loop(const float *state0, float dt,
                                  int *upright, double *vel_sum, double *vel_sq,
                                  float *states, float *actions, float *workspace,
                                  apg_stream_t stream);
+
+/* The controller step of the cart-pole in one call: the controller branch of
+ * TrainCartpole.run_epoch (scripts/train_cartpole.py:127-155) with
+ * simple_model.Net(4, H) as policy, up to and optionally including the
+ * optimizer step.
+ *   actions = tanh(fc_out(tanh(fc3(tanh(fc2(tanh(fc1(tanh(fc0(x)))))))))), x =
+ *             in_state [B,4] with column 0 read as 0 (Net.forward zeroes it;
+ *             in_state is never written), reshaped [B,H,1];
+ *   loss    = apg_cartpole_rollout_fwd_bwd's from state0 [B,4] (make_reference,
+ *             H steps, cartpole_loss_mpc; the gradient flows through the
+ *             reference as there);
+ *   grads   = the cotangent of every policy tensor, summed over the batch: ten
+ *             device pointers with the shapes of ApgCartpolePolicy's tensors -
+ *             typically views of one flat buffer in named_parameters() order,
+ *             whose offsets are APG_CARTPOLE_POLICY_G_* (fc_out.bias follows
+ *             fc_out.weight; APG_CARTPOLE_POLICY_GRADS(H) floats in all).
+ * loss_partials: apg_loss_partials_count(B) floats; loss [1] and actions_out
+ * [B,H] may be NULL.  update (or NULL: none): momentum SGD applied by the last
+ * stage where it holds an element's final sum - buf = momentum buf + grad,
+ * param -= lr buf, in double, rounded once each (as ApgMlpSgdUpdate); the
+ * gradients are written to `grads` all the same.  An update with a NULL pointer
+ * or a NaN rate is an argument error.
+ * Every policy tensor is read on the device when the launches run: no host
+ * read, no synchronisation, a linear chain of launches on `stream` (one launch
+ * when B <= 64, two otherwise) - the step, update included, can be captured in
+ * a graph.  No float atomics: a workgroup adds its samples in sample order,
+ * the workgroups' rows are added by a fixed tree; the same inputs give the same
+ * bits.  B >= 1, H in [1, APG_MAX_HORIZON].
+ * workspace: apg_cartpole_mlp_train_step_workspace_floats(B, H) device floats. */
+#define APG_CARTPOLE_POLICY_G_W0 0
+#define APG_CARTPOLE_POLICY_G_B0 128
+#define APG_CARTPOLE_POLICY_G_W1 160
+#define APG_CARTPOLE_POLICY_G_B1 2208
+#define APG_CARTPOLE_POLICY_G_W2 2272
+#define APG_CARTPOLE_POLICY_G_B2 6368
+#define APG_CARTPOLE_POLICY_G_W3 6432
+#define APG_CARTPOLE_POLICY_G_B3 8480
+#define APG_CARTPOLE_POLICY_G_WOUT 8512
+#define APG_CARTPOLE_POLICY_G_BOUT(H) (8512 + 32 * (H))
+#define APG_CARTPOLE_POLICY_GRADS(H) (8512 + 33 * (H))
+typedef struct ApgCartpolePolicyGrads {
+  float *w0, *b0, *w1, *b1, *w2, *b2, *w3, *b3, *w_out, *b_out;
+} ApgCartpolePolicyGrads;
+typedef struct ApgCartpoleSgdUpdate {
+  double lr, momentum;
+  ApgCartpolePolicyGrads param;
+  ApgCartpolePolicyGrads momentum_buf;
+} ApgCartpoleSgdUpdate;
+int apg_cartpole_mlp_train_step_workspace_floats(int B, int H);
+int apg_cartpole_mlp_train_step(const float *in_state, const float *state0, float dt,
+                                const ApgCartpoleParams *params,
+                                const ApgCartpolePolicy *policy, int B, int H,
+                                float *loss_partials, float *loss,
+                                const ApgCartpolePolicyGrads *grads, float *actions_out,
+                                float *workspace, const ApgCartpoleSgdUpdate *update,
+                                apg_stream_t stream);
 
 /* ---------------------------------------------------- cartpole, learnt --- */
 /* LearntCartpoleDynamics (neural_control/dynamics/cartpole_dynamics.py:
