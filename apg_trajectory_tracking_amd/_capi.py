@@ -437,6 +437,10 @@ SIGNATURES = {
     "apg_cartpole_learnt_rollout_fwd_bwd": [
         _P, _P, _F, ctypes.POINTER(ApgCartpoleLearnt), _I, _I, _I, _P, _P, _P, _P, _P,
         _P],
+    "apg_cartpole_learnt_mlp_train_step": [
+        _P, _P, _F, ctypes.POINTER(ApgCartpoleLearnt), ctypes.POINTER(ApgCartpolePolicy),
+        _I, _I, _P, _P, ctypes.POINTER(ApgCartpolePolicyGrads), _P, _P,
+        ctypes.POINTER(ApgCartpoleSgdUpdate), _P],
     "apg_cartpole_learnt_mlp_closed_loop": [
         _P, _F, ctypes.POINTER(ApgCartpoleLearnt), ctypes.POINTER(ApgCartpolePolicy),
         _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P],

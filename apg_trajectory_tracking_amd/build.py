@@ -140,6 +140,7 @@ def build_cpu(force=False, verbose=False):
             os.path.join(REPO, "include", "apg_cpu_quad_fit.h"),
             os.path.join(REPO, "include", "apg_cpu_cartpole_fit.h"),
             os.path.join(REPO, "include", "apg_cpu_cartpole_train.h"),
+            os.path.join(REPO, "include", "apg_cpu_cartpole_learnt_train.h"),
             os.path.join(REPO, "include", "apg_cpu_mpc.h"), __file__] + _headers()
     if (not force and os.path.exists(LIB_CPU)
             and os.path.getmtime(LIB_CPU) >= max(os.path.getmtime(d) for d in deps)):

@@ -26,6 +26,7 @@
 
 #include "apg_device.h"
 #include "cartpole_learnt_math.h"
+#include "cartpole_learnt_stage.h"
 #include "cartpole_rollout_math.h"
 
 namespace apg {
@@ -36,17 +37,7 @@ inline int grid_for(int B, int block) { return (B + block - 1) / block; }
 constexpr int kStepBlock = 256;
 constexpr int kStepWaves = kStepBlock / kWave;
 
-// the residual's unit rows into LDS (all threads of the workgroup; barrier)
-__device__ __forceinline__ void stage_residual(float *rows, const ApgCartpoleLearnt &m) {
-  for (int t = threadIdx.x; t < kCartResFloats; t += blockDim.x)
-    rows[t] = cart_residual_packed(t, m.w1, m.b1, m.w2);
-  __syncthreads();
-}
-
-__device__ __forceinline__ CartLearntParams load_params(const ApgCartpoleLearnt &m) {
-  return CartLearntParams{*m.max_force_mag, *m.masspole, *m.length,
-                          *m.friction,      *m.total_mass, *m.polemass_length};
-}
+// (stage_residual, load_params: cartpole_learnt_stage.h)
 
 __global__ __launch_bounds__(kStepBlock) void cart_learnt_step_fwd_kernel(
     const float *__restrict__ state, const float *__restrict__ action, ApgCartpoleLearnt m,

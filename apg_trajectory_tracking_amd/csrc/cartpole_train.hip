@@ -22,9 +22,12 @@
 // over the rows (cart_train_reduce_kernel), which also sums the loss partials
 // and applies the update; with one workgroup (B <= 64) the first kernel does
 // all of that itself and the second launch is not made.  No float atomics.
+// The same body serves the step through LearntCartpoleDynamics
+// (cartpole_learnt_policy_kernel): only the rollout's two step functions differ.
 #include <stddef.h>
 
 #include "apg_device.h"
+#include "cartpole_learnt_stage.h"
 #include "cartpole_math.h"
 #include "cartpole_train_math.h"
 
@@ -52,7 +55,7 @@ inline int train_grid(int B) {
   const int n = train_chunks(B);
   return n < kTrMaxGrid ? n : kTrMaxGrid;
 }
-inline size_t train_lds_floats(int H) {
+__host__ __device__ inline size_t train_lds_floats(int H) {
   return (size_t)(rOut + H) * kTrLd + (size_t)H * 4 * kTrChunk;
 }
 
@@ -155,14 +158,21 @@ __device__ __forceinline__ void layer_wgrad(float (&gw)[KP], float &gb, const fl
     cpt_wgrad<KP>(gw, gb, dz_m[s], [&](int jj) { return x_j0[jj * kTrLd + s]; });
 }
 
-__global__ __launch_bounds__(kTrBlock) void cart_train_kernel(CartTrainArgs A) {
+// The step, whatever simulates: `step(x, a)` advances a state in place,
+// `adjoint(lam, pre, a)` turns dL/dnext into dL/dstate over lam and returns
+// dL/daction (the two step functions of cart_rollout_forward / _reverse).
+// (The workgroup's LDS is named here, not handed in as a pointer: its address
+// is then a constant to the compiler - handed in, the analytic kernel took 255
+// VGPRs instead of 251 and the learnt one 256 + 2 AGPRs, one wave per SIMD.)
+template <class Step, class Adjoint>
+__device__ __forceinline__ void policy_step_body(const CartTrainArgs &A, Step &&step,
+                                                 Adjoint &&adjoint) {
   extern __shared__ float lds[];
   const int H = A.H, B = A.B;
   const int tid = threadIdx.x, lane = tid & (kWave - 1);
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   float *stash = lds + (rOut + H) * kTrLd;
   const ApgCartpolePolicy &P = A.p;
-  const CartConst c = A.c;
   // who owns what of the weight gradients: 32-unit layers (fc0, fc3) m32 / g32
   // (8 groups), 64-unit layers (fc1, fc2, the head padded to 64) m64 / g64 (4)
   const int m32 = tid & 31, g32 = tid >> 5, m64 = lane, g64 = wave;
@@ -218,18 +228,14 @@ __global__ __launch_bounds__(kTrBlock) void cart_train_kernel(CartTrainArgs A) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) s0[i] = live ? A.state0[(size_t)b * 4 + i] : 0.f;
       const float loss = cart_rollout_forward(
-          H, s0, s, action, ST, [&](float (&x)[4], float a) { cart_step(x, a, c); },
-          [](int, const float (&)[4]) {});
+          H, s0, s, action, ST, step, [](int, const float (&)[4]) {});
       const float sum = wave_sum(live ? loss : 0.f);
       if (lane == 0) {
         A.loss_partials[chunk] = sum;
         if (gridDim.x == 1 && A.out.loss) A.out.loss[0] = sum;
       }
       cart_rollout_reverse(
-          H, s0, s, lam, action, ST,
-          [&](float (&l)[4], const float (&pre)[4], float a) {
-            return cart_step_adjoint(l, pre[1], pre[3], cart_step_aux(pre, a, c), c);
-          },
+          H, s0, s, lam, action, ST, adjoint,
           [&](int k, float g) {
             float *at = lds + (rOut + k) * kTrLd + lane;
             *at = live ? cpt_dtanh(g, *at) : 0.f;
@@ -300,6 +306,41 @@ __global__ __launch_bounds__(kTrBlock) void cart_train_kernel(CartTrainArgs A) {
   }
 }
 
+__global__ __launch_bounds__(kTrBlock) void cart_train_kernel(CartTrainArgs A) {
+  const CartConst c = A.c;
+  policy_step_body(
+      A, [&](float (&x)[4], float a) { cart_step(x, a, c); },
+      [&](float (&l)[4], const float (&pre)[4], float a) {
+        return cart_step_adjoint(l, pre[1], pre[3], cart_step_aux(pre, a, c), c);
+      });
+}
+
+// The same step through LearntCartpoleDynamics (apg_cartpole_learnt_mlp_train_
+// step): the simulator is frozen in the controller phase, so only the two step
+// functions differ - cart_learnt_step / cart_learnt_step_adjoint of
+// cartpole_learnt_math.h, as cart_learnt_rollout_kernel (cartpole_learnt.hip)
+// calls them, all 64 residual units in ascending order on wave 0.  The step
+// constants are built here from the module's six live device parameters, the
+// residual's packed unit rows sit in LDS behind the rollout's stash.
+struct CartLearntTrainArgs {
+  CartTrainArgs t;        // (t.c is not read)
+  ApgCartpoleLearnt m;
+  float dt;
+};
+
+__global__ __launch_bounds__(kTrBlock) void cartpole_learnt_policy_kernel(
+    CartLearntTrainArgs A) {
+  extern __shared__ float lds[];
+  float *rows = lds + train_lds_floats(A.t.H);
+  stage_residual(rows, A.m);
+  const CartConst c = make_learnt_const(load_params(A.m), A.dt);
+  policy_step_body(
+      A.t, [&](float (&x)[4], float a) { cart_learnt_step(x, a, c, rows); },
+      [&](float (&l)[4], const float (&pre)[4], float a) {
+        return cart_learnt_step_adjoint(l, pre, a, cart_step_aux(pre, a, c), c, rows);
+      });
+}
+
 // Element c of the flat gradient = the sum over the workgroups' rows: the 8
 // threads of a column add rows r, r + 8, ... in order, then a fixed tree (the
 // scheme of fit_rows_sum, residual_fit.h, with a row length known at run time);
@@ -347,31 +388,19 @@ bool all_set(const ApgCartpolePolicyGrads &g) {
   return g.w0 && g.b0 && g.w1 && g.b1 && g.w2 && g.b2 && g.w3 && g.b3 && g.w_out && g.b_out;
 }
 
-}  // namespace
-}  // namespace apg
-
-using namespace apg;
-
-extern "C" {
-
-int apg_cartpole_mlp_train_step_workspace_floats(int B, int H) {
-  if (B <= 0 || H < 1 || H > APG_MAX_HORIZON) return 0;
-  return train_grid(B) * cpt_grads(H);
-}
-
-int apg_cartpole_mlp_train_step(const float *in_state, const float *state0, float dt,
-                                const ApgCartpoleParams *params,
-                                const ApgCartpolePolicy *policy, int B, int H,
-                                float *loss_partials, float *loss,
-                                const ApgCartpolePolicyGrads *grads, float *actions_out,
-                                float *workspace, const ApgCartpoleSgdUpdate *update,
-                                apg_stream_t stream) {
+// Everything the two entry points check and build alike: the arguments but for
+// the simulator (argument errors before any HIP call), the kernels' arguments
+// and the launches.
+int check_step_args(const float *in_state, const float *state0, const void *sim,
+                    const ApgCartpolePolicy *policy, int B, int H, const float *loss_partials,
+                    const ApgCartpolePolicyGrads *grads, const float *workspace,
+                    const ApgCartpoleSgdUpdate *update) {
   if (B < 1) { set_error("B must be >= 1 (got %d)", B); return APG_ERR_ARG; }
   if (H < 1 || H > APG_MAX_HORIZON) {
     set_error("H must be in [1, %d] (got %d)", APG_MAX_HORIZON, H);
     return APG_ERR_ARG;
   }
-  if (!params || !policy || !grads) {
+  if (!sim || !policy || !grads) {
     set_error("params / policy / grads is NULL");
     return APG_ERR_ARG;
   }
@@ -393,6 +422,13 @@ int apg_cartpole_mlp_train_step(const float *in_state, const float *state0, floa
     set_error("in_state / state0 / loss_partials / workspace must not be NULL");
     return APG_ERR_ARG;
   }
+  return APG_OK;
+}
+
+CartTrainArgs step_args(const float *in_state, const float *state0,
+                        const ApgCartpolePolicy *policy, int B, int H, float *loss_partials,
+                        float *loss, const ApgCartpolePolicyGrads *grads, float *actions_out,
+                        float *workspace, const ApgCartpoleSgdUpdate *update) {
   CartTrainArgs A;
   A.in_state = in_state, A.state0 = state0, A.p = *policy;
   A.loss_partials = loss_partials, A.actions_out = actions_out, A.rows = workspace;
@@ -401,24 +437,83 @@ int apg_cartpole_mlp_train_step(const float *in_state, const float *state0, floa
   A.out.mom = update ? update->momentum_buf : *grads;
   A.out.lr = update ? update->lr : 0.0, A.out.momentum = update ? update->momentum : 0.0;
   A.out.loss = loss, A.out.H = H, A.out.update = update != nullptr;
-  A.c = make_const(*params, dt);
+  A.c = CartConst{};
   A.B = B, A.H = H;
-  hipStream_t st = (hipStream_t)stream;
-  const int grid = train_grid(B);
-  const size_t lds = train_lds_floats(H) * sizeof(float);
+  return A;
+}
+
+// `kernel(args)` on min(ceil(B / 64), 256) workgroups with `lds` bytes, then -
+// more than one workgroup - the second stage over their rows
+template <class Args>
+int launch_step(void (*kernel)(Args), const Args &args, const CartTrainArgs &A, size_t lds,
+                hipStream_t st, const char *what) {
+  const int grid = train_grid(A.B);
   if (lds > 64 * 1024 &&
-      hipFuncSetAttribute((const void *)cart_train_kernel,
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return check_launch("hipFuncSetAttribute(cartpole_mlp_train_step)");
-  hipLaunchKernelGGL(cart_train_kernel, dim3(grid), dim3(kTrBlock), lds, st, A);
-  if (int e = check_launch("cartpole_mlp_train_step")) return e;
+      hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)lds) != hipSuccess)
+    return check_launch("hipFuncSetAttribute(cartpole train step)");
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kTrBlock), lds, st, args);
+  if (int e = check_launch(what)) return e;
   if (grid == 1) return APG_OK;
   CartTrainReduceArgs R;
-  R.rows = workspace, R.loss_partials = loss_partials, R.out = A.out;
-  R.nrows = grid, R.npartials = train_chunks(B);
-  const int columns = (cpt_grads(H) + kTrCols - 1) / kTrCols;
+  R.rows = A.rows, R.loss_partials = A.loss_partials, R.out = A.out;
+  R.nrows = grid, R.npartials = train_chunks(A.B);
+  const int columns = (cpt_grads(A.H) + kTrCols - 1) / kTrCols;
   hipLaunchKernelGGL(cart_train_reduce_kernel, dim3(columns + 1), dim3(kTrBlock), 0, st, R);
   return check_launch("cartpole_mlp_train_reduce");
+}
+
+}  // namespace
+}  // namespace apg
+
+using namespace apg;
+
+extern "C" {
+
+int apg_cartpole_mlp_train_step_workspace_floats(int B, int H) {
+  if (B <= 0 || H < 1 || H > APG_MAX_HORIZON) return 0;
+  return train_grid(B) * cpt_grads(H);
+}
+
+int apg_cartpole_mlp_train_step(const float *in_state, const float *state0, float dt,
+                                const ApgCartpoleParams *params,
+                                const ApgCartpolePolicy *policy, int B, int H,
+                                float *loss_partials, float *loss,
+                                const ApgCartpolePolicyGrads *grads, float *actions_out,
+                                float *workspace, const ApgCartpoleSgdUpdate *update,
+                                apg_stream_t stream) {
+  if (int e = check_step_args(in_state, state0, params, policy, B, H, loss_partials, grads,
+                              workspace, update))
+    return e;
+  CartTrainArgs A = step_args(in_state, state0, policy, B, H, loss_partials, loss, grads,
+                              actions_out, workspace, update);
+  A.c = make_const(*params, dt);
+  return launch_step(cart_train_kernel, A, A, train_lds_floats(H) * sizeof(float),
+                     (hipStream_t)stream, "cartpole_mlp_train_step");
+}
+
+int apg_cartpole_learnt_mlp_train_step(const float *in_state, const float *state0, float dt,
+                                       const ApgCartpoleLearnt *model,
+                                       const ApgCartpolePolicy *policy, int B, int H,
+                                       float *loss_partials, float *loss,
+                                       const ApgCartpolePolicyGrads *grads,
+                                       float *actions_out, float *workspace,
+                                       const ApgCartpoleSgdUpdate *update,
+                                       apg_stream_t stream) {
+  if (int e = check_step_args(in_state, state0, model, policy, B, H, loss_partials, grads,
+                              workspace, update))
+    return e;
+  if (const char *e = cart_learnt_check(model, /*need_residual=*/true)) {
+    set_error("%s", e);
+    return APG_ERR_ARG;
+  }
+  CartLearntTrainArgs A;
+  A.t = step_args(in_state, state0, policy, B, H, loss_partials, loss, grads, actions_out,
+                  workspace, update);
+  A.m = *model, A.dt = dt;
+  return launch_step(cartpole_learnt_policy_kernel, A, A.t,
+                     (train_lds_floats(H) + kCartResFloats) * sizeof(float),
+                     (hipStream_t)stream, "cartpole_learnt_mlp_train_step");
 }
 
 }  // extern "C"

@@ -14,6 +14,7 @@
 
 #include "apg_cpu.h"
 #include "apg_cpu_cartpole_fit.h"
+#include "apg_cpu_cartpole_learnt_train.h"
 #include "apg_cpu_cartpole_train.h"
 #include "apg_cpu_launch_chain.h"
 #include "apg_cpu_quad_fit.h"
@@ -663,20 +664,27 @@ int apg_cartpole_learnt_fit_fwd_bwd_cpu(const float *state, const float *action,
   return APG_OK;
 }
 
-// apg_cpu_cartpole_train.h: cart_train_kernel (cartpole_train.hip) sample for
-// sample - the layers of cartpole_train_math.h one unit at a time, the rollout
-// of cartpole_rollout_math.h, every gradient element summed in sample order -
-// then the last stage (gradient out, momentum SGD) element by element
-int apg_cartpole_mlp_train_step_cpu(const float *in_state, const float *state0, float dt,
-                                    const ApgCartpoleParams *params,
-                                    const ApgCartpolePolicy *policy, int B, int H,
-                                    float *loss_partials, float *loss,
-                                    const ApgCartpolePolicyGrads *grads, float *actions_out,
-                                    float *workspace, const ApgCartpoleSgdUpdate *update) {
-  (void)workspace;
+}  // extern "C"
+
+namespace {
+
+// apg_cpu_cartpole_train.h: the kernels' shared body (policy_step_body,
+// cartpole_train.hip) sample for sample - the layers of cartpole_train_math.h
+// one unit at a time, the rollout of cartpole_rollout_math.h through the two
+// step functions of `simulator` (AnalyticCart / LearntCart below; asked for
+// once the other arguments hold and its own check has passed), every gradient
+// element summed in sample order - then the last stage (gradient out, momentum
+// SGD) element by element.  `sim`: the entry point's simulator argument, for
+// the NULL check.
+template <class Simulator>
+int cart_policy_step_host(const float *in_state, const float *state0, const void *sim,
+                          const ApgCartpolePolicy *policy, int B, int H,
+                          float *loss_partials, float *loss,
+                          const ApgCartpolePolicyGrads *grads, float *actions_out,
+                          const ApgCartpoleSgdUpdate *update, Simulator &&simulator) {
   if (B < 1) return fail("B must be >= 1 (got %d)", B);
   if (int e = check_h(H)) return e;
-  if (!params || !policy || !grads) return fail("params / policy / grads is NULL");
+  if (!sim || !policy || !grads) return fail("params / policy / grads is NULL");
   const ApgCartpolePolicy &P = *policy;
   if (!P.w0 || !P.b0 || !P.w1 || !P.b1 || !P.w2 || !P.b2 || !P.w3 || !P.b3 || !P.w_out ||
       !P.b_out)
@@ -695,7 +703,9 @@ int apg_cartpole_mlp_train_step_cpu(const float *in_state, const float *state0, 
     return fail("update: lr / momentum is NaN");
   if (!in_state || !state0 || !loss_partials)
     return fail("in_state / state0 / loss_partials must not be NULL");
-  const CartConst c = make_const(*params, dt);
+  if (int e = simulator.check()) return e;
+  const auto step = simulator.step();
+  const auto adjoint = simulator.adjoint();
   std::vector<float> G((size_t)cpt_grads(H), 0.f), pre((size_t)H * 4), out((size_t)H);
   // y = tanh(W x + b), one unit at a time
   auto fwd = [](const float *W, const float *b, int N, int K, const float *x, float *y) {
@@ -744,15 +754,10 @@ int apg_cartpole_mlp_train_step_cpu(const float *in_state, const float *state0, 
     auto action = [&](int k) { return out[k]; };
     float s0[4], s[4], lam[4];
     for (int i = 0; i < 4; ++i) s0[i] = state0[(size_t)b * 4 + i];
-    lo.add(b, B, cart_rollout_forward(
-                     H, s0, s, action, ST, [&](float (&v)[4], float a) { cart_step(v, a, c); },
-                     [](int, const float (&)[4]) {}));
-    cart_rollout_reverse(
-        H, s0, s, lam, action, ST,
-        [&](float (&l)[4], const float (&p)[4], float a) {
-          return cart_step_adjoint(l, p[1], p[3], cart_step_aux(p, a, c), c);
-        },
-        [&](int k, float g) { out[k] = cpt_dtanh(g, out[k]); });
+    lo.add(b, B, cart_rollout_forward(H, s0, s, action, ST, step,
+                                      [](int, const float (&)[4]) {}));
+    cart_rollout_reverse(H, s0, s, lam, action, ST, adjoint,
+                         [&](int k, float g) { out[k] = cpt_dtanh(g, out[k]); });
     bwd(P.w_out, H, kCptH3, out.data(), h3, kCptGWout, kCptGWout + kCptH3 * H, true);
     bwd(P.w3, kCptH3, kCptH2, h3, h2, kCptGW3, kCptGB3, true);
     bwd(P.w2, kCptH2, kCptH1, h2, h1, kCptGW2, kCptGB2, true);
@@ -767,6 +772,70 @@ int apg_cartpole_mlp_train_step_cpu(const float *in_state, const float *state0, 
     if (update) cpt_sgd(G[e], update->lr, update->momentum, tp[q][off], tm[q][off]);
   }
   return APG_OK;
+}
+
+// what cart_policy_step_host rolls out through: the analytic step on host
+// parameters, or LearntCartpoleDynamics on the module's tensors
+struct AnalyticCart {
+  CartConst c;
+  int check() const { return APG_OK; }
+  auto step() const {
+    return [c = c](float (&v)[4], float a) { cart_step(v, a, c); };
+  }
+  auto adjoint() const {
+    return [c = c](float (&l)[4], const float (&p)[4], float a) {
+      return cart_step_adjoint(l, p[1], p[3], cart_step_aux(p, a, c), c);
+    };
+  }
+};
+
+struct LearntCart {
+  const ApgCartpoleLearnt *model;
+  float dt;
+  CartConst c;
+  std::vector<float> rows;
+  int check() {
+    if (const char *e = cart_learnt_check(model, /*need_residual=*/true)) return fail("%s", e);
+    CartLearntParams p;
+    learnt_setup(*model, dt, p, c, rows);
+    return APG_OK;
+  }
+  auto step() const {
+    return [this](float (&v)[4], float a) { cart_learnt_step(v, a, c, rows.data()); };
+  }
+  auto adjoint() const {
+    return [this](float (&l)[4], const float (&p)[4], float a) {
+      return cart_learnt_step_adjoint(l, p, a, cart_step_aux(p, a, c), c, rows.data());
+    };
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+int apg_cartpole_mlp_train_step_cpu(const float *in_state, const float *state0, float dt,
+                                    const ApgCartpoleParams *params,
+                                    const ApgCartpolePolicy *policy, int B, int H,
+                                    float *loss_partials, float *loss,
+                                    const ApgCartpolePolicyGrads *grads, float *actions_out,
+                                    float *workspace, const ApgCartpoleSgdUpdate *update) {
+  (void)workspace;
+  return cart_policy_step_host(in_state, state0, params, policy, B, H, loss_partials, loss,
+                               grads, actions_out, update,
+                               AnalyticCart{params ? make_const(*params, dt) : CartConst{}});
+}
+
+int apg_cartpole_learnt_mlp_train_step_cpu(const float *in_state, const float *state0,
+                                           float dt, const ApgCartpoleLearnt *model,
+                                           const ApgCartpolePolicy *policy, int B, int H,
+                                           float *loss_partials, float *loss,
+                                           const ApgCartpolePolicyGrads *grads,
+                                           float *actions_out, float *workspace,
+                                           const ApgCartpoleSgdUpdate *update) {
+  (void)workspace;
+  return cart_policy_step_host(in_state, state0, model, policy, B, H, loss_partials, loss,
+                               grads, actions_out, update, LearntCart{model, dt});
 }
 
 }  // extern "C"

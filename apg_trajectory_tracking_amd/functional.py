@@ -2475,6 +2475,47 @@ def cartpole_policy_train_step(net, in_state, state0, dt, params, update=None,
     the network's parameters and these buffers, in its last stage.
     The parameters are read on the device when the launches run: no host read,
     no synchronisation, one stream - capturable in a graph, update included."""
+    return _cartpole_policy_step(
+        net, in_state, state0, update, want_actions, (),
+        lambda *a: lib().apg_cartpole_mlp_train_step(
+            *a[:2], float(dt), ctypes.byref(params), *a[2:]),
+        "apg_cartpole_mlp_train_step")
+
+
+def cartpole_learnt_policy_train_step(net, dyn, in_state, state0, dt, update=None,
+                                      want_actions=False):
+    """cartpole_policy_train_step through the LearntCartpoleDynamics `dyn`: the
+    controller step of the adapt flow in one fused call
+    (apg_cartpole_learnt_mlp_train_step).  Same returns, same `update`.  The
+    simulator is frozen in this phase: its tensors are read on the device when
+    the launches run - a graph replay sees their values of that moment - never
+    written, and get no gradient."""
+    H = net.fc_out.weight.shape[0] if hasattr(net, "fc_out") else 0
+    if not (cartpole_policy_fusable(net, H) and cartpole_learnt_fusable(dyn)):
+        raise ValueError("fused controller step expects simple_model.Net(4, H), H in "
+                         f"[1, {_capi.MAX_HORIZON}], with parameters that require grad, and "
+                         "a LearntCartpoleDynamics with [1] parameters and the 5 -> 64 -> 4 "
+                         "residual network, each as contiguous fp32 tensors on one CUDA "
+                         "device")
+    sim = [t.detach() for t in _cartpole_learnt_tensors(dyn)]
+    devs = {t.device for t in (net.fc0.weight, sim[0], in_state, state0)}
+    if len(devs) != 1:
+        raise ValueError("policy, simulator, in_state and state0 must be on one CUDA "
+                         f"device, got {sorted(map(str, devs))}")
+    model = _cartpole_learnt_model(sim)
+    return _cartpole_policy_step(
+        net, in_state, state0, update, want_actions, sim,
+        lambda *a: lib().apg_cartpole_learnt_mlp_train_step(
+            *a[:2], float(dt), ctypes.byref(model), *a[2:]),
+        "apg_cartpole_learnt_mlp_train_step")
+
+
+def _cartpole_policy_step(net, in_state, state0, update, want_actions, sim_tensors, call,
+                          what):
+    """What the two fused controller steps share: the checks, the outputs and
+    the policy's structs.  `call(in_state, state0, policy, B, H, ...)` makes the
+    entry point's call with its simulator put in; `sim_tensors`: the
+    simulator's device tensors (on the policy's device)."""
     H = net.fc_out.weight.shape[0] if hasattr(net, "fc_out") else 0
     if not cartpole_policy_fusable(net, H):
         raise ValueError("fused controller step expects simple_model.Net(4, H), H in "
@@ -2482,7 +2523,7 @@ def cartpole_policy_train_step(net, in_state, state0, dt, params, update=None,
                          "require grad on one CUDA device")
     tensors = [t.detach() for t in _cartpole_policy_tensors(net)]
     in_state, state0 = _f32c(in_state), _f32c(state0)
-    require_device(in_state, state0, *tensors)
+    require_device(in_state, state0, *tensors, *sim_tensors)
     if (in_state.dim() != 2 or in_state.shape[1] != 4 or state0.shape != in_state.shape
             or in_state.shape[0] < 1):
         raise ValueError("in_state / state0 [B,4] with B >= 1 expected, got "
@@ -2511,10 +2552,8 @@ def cartpole_policy_train_step(net, in_state, state0, dt, params, update=None,
             float(lr), float(momentum),
             _capi.ApgCartpolePolicyGrads(*[ptr(t) for t in tensors]),
             _capi.ApgCartpolePolicyGrads(*[ptr(b) for b in held])))
-    check(lib().apg_cartpole_mlp_train_step(
-        ptr(in_state), ptr(state0), float(dt), ctypes.byref(params), ctypes.byref(pol), B, H,
-        ptr(parts), ptr(loss), ctypes.byref(gs), ptr(actions), ptr(ws), upd,
-        stream_of(in_state)), "apg_cartpole_mlp_train_step")
+    check(call(ptr(in_state), ptr(state0), ctypes.byref(pol), B, H, ptr(parts), ptr(loss),
+               ctypes.byref(gs), ptr(actions), ptr(ws), upd, stream_of(in_state)), what)
     if update is not None and not torch.cuda.is_current_stream_capturing():
         note_in_kernel_update(tensors + held)
     out = dict(loss=loss, flat=flat, grads=grads)

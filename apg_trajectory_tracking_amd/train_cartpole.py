@@ -11,7 +11,10 @@ With a LearntCartpoleDynamics as train dynamics (`train_norm_dynamics`, the
 reference's adapt mode :245-262) run_epoch also fits the simulator
 (train="dynamics") and the controller branch runs through it, fused into one
 launch (apg_cartpole_learnt_rollout_fwd_bwd); the fit step itself is one fused
-call as well (`fused_fit`, apg_cartpole_learnt_fit_fwd_bwd).  Two deliberate deviations make
+call as well (`fused_fit`, apg_cartpole_learnt_fit_fwd_bwd).  With
+`fused_learnt_policy` (off by default) the controller step through the learnt
+simulator is one fused call too, policy and momentum SGD inside
+(apg_cartpole_learnt_mlp_train_step).  Two deliberate deviations make
 that loop run at all: run_epoch accepts the `epoch` that TrainBase.run_dynamics
 passes (the reference's raises TypeError), and init_optimizer builds the
 simulator's optimizer for any nn.Module simulator (the reference's only for
@@ -204,6 +207,38 @@ class TrainCartpole(TrainBase):
         return self._step_direct(res["loss"].reshape(()), res["grads"], res["flat"],
                                  stepped=upd is not None)
 
+    fused_learnt_policy = False   # the same through a LearntCartpoleDynamics
+
+    def _fusable_learnt_policy(self, in_state, current_state):
+        """The fused controller step through the learnt simulator
+        (functional.cartpole_learnt_policy_train_step) serves the stock
+        simple_model.Net(4, horizon) rolled out through a stock
+        LearntCartpoleDynamics, with policy, simulator and batch on one CUDA
+        device - the tensor conditions of `_fusable_policy`.  Off unless
+        `fused_learnt_policy` is set: a trainer nobody configured takes the
+        tape, as before (timings: profiles/cartpole_learnt_train_timing.jsonl)."""
+        if not (self.fused_learnt_policy and self.action_dim == 1 and self.state_size == 4
+                and F.cartpole_learnt_fusable(self.train_dynamics)
+                and F.cartpole_policy_fusable(self.net, self.horizon)):
+            return False
+        dev = self.net.fc0.weight.device
+        return (self.train_dynamics.linear_state_1.weight.device == dev
+                and all(t.device == dev and t.dtype == torch.float32 and t.is_contiguous()
+                        and t.dim() == 2 and t.shape[1] == 4 and t.shape[0] >= 1
+                        and not t.requires_grad
+                        for t in (in_state, current_state)))
+
+    def _fused_learnt_policy_step(self, in_state, current_state):
+        """`_fused_policy_step` through the learnt simulator, which is read and
+        left as it is (no gradient; its `timestamp` stays, as in the fused
+        rollout of `_controller_loss`)."""
+        upd = self._in_kernel_update(
+            names=_capi.CARTPOLE_POLICY_PARAMS, tensors=F._cartpole_policy_tensors(self.net))
+        res = F.cartpole_learnt_policy_train_step(
+            self.net, self.train_dynamics, in_state, current_state, self.delta_t, update=upd)
+        return self._step_direct(res["loss"].reshape(()), res["grads"], res["flat"],
+                                 stepped=upd is not None)
+
     def run_epoch(self, train="controller", epoch=0):
         """scripts/train_cartpole.py:118-165.  train "dynamics" fits a
         learnable simulator (TrainBase.train_dynamics_model) on the policy's
@@ -231,6 +266,10 @@ class TrainCartpole(TrainBase):
                 continue
             if self._fusable_policy(in_state, current_state):
                 loss = self._fused_policy_step(in_state, current_state).detach()
+                running_loss = loss if running_loss is None else running_loss + loss
+                continue
+            if self._fusable_learnt_policy(in_state, current_state):
+                loss = self._fused_learnt_policy_step(in_state, current_state).detach()
                 running_loss = loss if running_loss is None else running_loss + loss
                 continue
             # the policy zeroes column 0 of its input in place: hand it a
@@ -309,14 +348,17 @@ def train_control(base_model, config, swingup=0, device=None):
     return trainer
 
 
-def train_norm_dynamics(base_model, config, not_trainable="all", device=None):
+def train_norm_dynamics(base_model, config, not_trainable="all", device=None,
+                        fused_learnt_policy=False):
     """scripts/train_cartpole.py:245-262 (`-t adapt`): fit a
     LearntCartpoleDynamics to CartpoleDynamics(modified_params) for the first
     epochs, then train the controller through it (TrainBase.run_dynamics),
     evaluating in the LEARNT environment (sample_in "train_env").
     base_model: a state_dict checkpoint file (checkpoint.load_policy) or None.
-    finalize saves the simulator's state_dict as `dynamics_model`.  Returns
-    the trainer."""
+    finalize saves the simulator's state_dict as `dynamics_model`.
+    fused_learnt_policy: the trainer's flag of that name - the controller
+    epochs take the fused step through the learnt simulator.  Returns the
+    trainer."""
     from .checkpoint import load_policy
     from .dynamics.cartpole_dynamics import CartpoleDynamics, LearntCartpoleDynamics
     modified_params = config["modified_params"]
@@ -327,6 +369,7 @@ def train_norm_dynamics(base_model, config, not_trainable="all", device=None):
     train_dyn = LearntCartpoleDynamics(not_trainable=not_trainable).to(dev)
     eval_dyn = CartpoleDynamics(modified_params=modified_params)
     trainer = TrainCartpole(train_dyn, eval_dyn, config)
+    trainer.fused_learnt_policy = bool(fused_learnt_policy)
     net = None if base_model is None else load_policy(base_model, system="cartpole")
     trainer.initialize_model(net, device=dev)
     trainer.run_dynamics(config)

@@ -1286,6 +1286,32 @@ int apg_cartpole_learnt_rollout_fwd_bwd(const float *state0, const float *action
                                         float *grad_actions, float *grad_state0,
                                         float *states_out, apg_stream_t stream);
 
+/* apg_cartpole_mlp_train_step through the learnt simulator: the controller
+ * step of the adapt flow (scripts/train_cartpole.py:127-155 with
+ * LearntCartpoleDynamics as train dynamics) in one call - policy forward,
+ * make_reference + H learnt steps + cartpole_loss_mpc, the reverse sweep, the
+ * cotangent chain through the five tanh layers, every POLICY tensor's gradient
+ * summed over the batch and, with `update`, momentum SGD on the policy.  The
+ * simulator is frozen in this phase: `model` is read, never written, and gets
+ * no gradient.  Its six physical parameters and the residual (which must be
+ * given) are read ON THE DEVICE when the launches run, as the policy's
+ * tensors are: no host read, no synchronisation, a linear chain on `stream`
+ * (one launch when B <= 64, two otherwise), capturable in a graph, and a replay
+ * sees the simulator's values of that moment.  Per sample the arithmetic is
+ * apg_cartpole_learnt_rollout_fwd_bwd's (all 64 residual units in ascending
+ * order).  Everything else - in_state / state0 [B,4], loss_partials, loss,
+ * grads (APG_CARTPOLE_POLICY_G_*), actions_out, update, the argument errors,
+ * no float atomics, B >= 1, H in [1, APG_MAX_HORIZON] - is as there, and so
+ * is the workspace: apg_cartpole_mlp_train_step_workspace_floats(B, H). */
+int apg_cartpole_learnt_mlp_train_step(const float *in_state, const float *state0, float dt,
+                                       const ApgCartpoleLearnt *model,
+                                       const ApgCartpolePolicy *policy, int B, int H,
+                                       float *loss_partials, float *loss,
+                                       const ApgCartpolePolicyGrads *grads,
+                                       float *actions_out, float *workspace,
+                                       const ApgCartpoleSgdUpdate *update,
+                                       apg_stream_t stream);
+
 /* apg_cartpole_mlp_closed_loop in the LEARNT environment - what
  * CartPoleEnv(train_dynamics) steps with in the adapt flow
  * (scripts/train_cartpole.py:50-55, 245-262): each env step is the module's
