@@ -14,6 +14,7 @@
 #include <math.h>
 
 #include "cartpole_math.h"
+#include "residual_fit.h"
 
 namespace apg {
 namespace {
@@ -135,23 +136,12 @@ __host__ __device__ __forceinline__ void cart_residual_adjoint(const float (&lam
 }
 
 // Weight cotangents of ONE unit row for one sample (added to gw[0..9] in the
-// row's own order: dW1[m][0..4], db1[m], dW2[0..3][m]).
+// row's own order: dW1[m][0..4], db1[m], dW2[0..3][m]): residual_fit.h
 __host__ __device__ __forceinline__ void cart_residual_unit_grads(const float *w,
                                                                   const float (&z)[5],
                                                                   const float (&lam)[4],
                                                                   float (&gw)[10]) {
-  float h = w[5];
-#pragma unroll
-  for (int j = 0; j < 5; ++j) h = fmaf(w[j], z[j], h);
-  float dh = 0.f;
-#pragma unroll
-  for (int o = 0; o < 4; ++o) dh = fmaf(w[6 + o], lam[o], dh);
-  const float dp = h > 0.f ? dh : 0.f, hr = fmaxf(h, 0.f);
-#pragma unroll
-  for (int j = 0; j < 5; ++j) gw[j] = fmaf(dp, z[j], gw[j]);
-  gw[5] += dp;
-#pragma unroll
-  for (int o = 0; o < 4; ++o) gw[6 + o] = fmaf(lam[o], hr, gw[6 + o]);
+  residual_unit_grads<5, 4, 6, 5, 6, 5>(w, z, lam, gw);
 }
 
 // One learnt step in place: physics on the live parameters, then the residual

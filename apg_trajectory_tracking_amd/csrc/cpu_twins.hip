@@ -103,6 +103,67 @@ struct LossOut {
   }
 };
 
+// The host twins of the fused simulator fits: fit_body and fit_reduce of
+// residual_fit.h on the traits T, lane for lane.  The common checks, then per
+// sample, in order: T::sample, the head and every hidden unit's cotangents
+// added into ONE partial row; then the norms and fit_scatter per element.
+// model_error: the outcome of the entry point's own model checks; make(): the
+// model (asked for once the arguments hold); t: the residual's tensors, for the
+// regulariser (T::REG).
+template <class T, class Make>
+int fit_host(const char *model_error, const float *state, const float *action,
+             const float *target, const typename T::Eval *eval, float l2_lambda, int B,
+             float *loss_partials, float *loss, float *grad, const typename T::Scale &scale,
+             const ResidualTensors &t, Make &&make) {
+  if (B < 0) return fail("B must be >= 0 (got %d)", B);
+  if (model_error) return fail("%s", model_error);
+  if ((target != nullptr) == (eval != nullptr))
+    return fail("exactly one of target / eval_params must be given");
+  if (!(l2_lambda >= 0.f)) return fail("l2_lambda must be >= 0");
+  if (!grad) return fail("grad is NULL");
+  for (int i = 0; i < T::GRADS; ++i) grad[i] = 0.f;
+  if (B == 0) {
+    if (loss) *loss = 0.f;
+    return APG_OK;
+  }
+  if (!state || !action || !loss_partials)
+    return fail("state / action / loss_partials must not be NULL");
+  const auto m = make();
+  std::vector<float> acc(T::ROW, 0.f);
+  LossOut out{loss_partials, loss};
+  for (int b = 0; b < B; ++b) {
+    float s[T::S], a[T::A], tgt[T::S], lam[T::OUT], z[T::IN], hd[T::USED];
+    for (int i = 0; i < T::S; ++i) s[i] = state[(size_t)b * T::S + i];
+    for (int i = 0; i < T::A; ++i) a[i] = action[(size_t)b * T::A + i];
+    if (!eval)
+      for (int i = 0; i < T::S; ++i) tgt[i] = target[(size_t)b * T::S + i];
+    const float l = T::sample(m, s, a, tgt, eval, lam, z, hd);
+    for (int i = 0; i < T::USED; ++i) acc[i] += hd[i];
+    for (int u = 0; u < kResHidden; ++u) {
+      float gw[T::UNIT] = {0.f};
+      residual_unit_grads<T::IN, T::OUT, T::RW2, T::RB1, T::UW2, T::UB1>(
+          m.rows + u * T::RES_ROW, z, lam, gw);
+      for (int j = 0; j < T::UNIT; ++j) acc[T::HEAD + j * kResHidden + u] += gw[j];
+    }
+    out.add(b, B, l);
+  }
+  out.finish(B);
+  float norms[4] = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (T::REG)
+    if (l2_lambda > 0.f) {
+      const float *tens[4] = {t.w2, t.b2, t.w1, t.b1};
+      const int count[4] = {T::OUT * kResHidden, T::OUT, kResHidden * T::IN, kResHidden};
+      for (int q = 0; q < 4; ++q) {
+        float ss = 0.f;
+        for (int i = 0; i < count[q]; ++i) ss = fmaf(tens[q][i], tens[q][i], ss);
+        norms[q] = sqrtf(ss);
+      }
+      if (loss) *loss += fit_penalty(l2_lambda, norms);
+    }
+  for (int c = 0; c < T::ROW; ++c) fit_scatter<T>(c, acc[c], scale, t, norms, l2_lambda, grad);
+  return APG_OK;
+}
+
 int run_deferred(const ApgDeferredLoss *d) {
   if (!d) return APG_OK;
   if (!d->prev_loss || d->prev_count < 0 || (d->prev_count > 0 && !d->prev_partials))
@@ -610,58 +671,24 @@ int apg_cartpole_learnt_rollout_fwd_bwd_cpu(const float *state0, const float *ac
   return APG_OK;
 }
 
-// apg_cpu_cartpole_fit.h: cartpole_fit_kernel (cartpole_fit.hip) lane for lane,
-// the batch summed in sample order into one partial row
+// apg_cpu_cartpole_fit.h: fit_host on CartFit (cartpole_fit_math.h)
 int apg_cartpole_learnt_fit_fwd_bwd_cpu(const float *state, const float *action, float dt,
                                         const ApgCartpoleLearnt *model, const float *target,
                                         const ApgCartpoleParams *eval_params, int B,
                                         float *loss_partials, float *loss, float *grad,
                                         float *workspace) {
   (void)workspace;
-  if (int e = check_learnt(model, B, true)) return e;
-  if ((target != nullptr) == (eval_params != nullptr))
-    return fail("exactly one of target / eval_params must be given");
-  if (!grad) return fail("grad is NULL");
-  for (int i = 0; i < kCartLearntGrads; ++i) grad[i] = 0.f;
-  if (B == 0) {
-    if (loss) *loss = 0.f;
-    return APG_OK;
-  }
-  if (!state || !action || !loss_partials)
-    return fail("state / action / loss_partials must not be NULL");
-  CartLearntParams p;
-  CartConst c;
-  std::vector<float> rows;
-  learnt_setup(*model, dt, p, c, rows);
   const CartConst ce = eval_params ? make_const(*eval_params, dt) : CartConst{};
-  std::vector<float> acc(kCartFitRow, 0.f);
-  LossOut out{loss_partials, loss};
-  for (int b = 0; b < B; ++b) {
-    float s[4], tgt[4], lam[4], g[kCartPhysGrads] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int i = 0; i < 4; ++i) s[i] = state[(size_t)b * 4 + i];
-    const float a = action[b];
-    if (eval_params) {
-      for (int i = 0; i < 4; ++i) tgt[i] = s[i];
-      cart_step(tgt, a, ce);
-    } else {
-      for (int i = 0; i < 4; ++i) tgt[i] = target[(size_t)b * 4 + i];
-    }
-    const float l = cart_fit_sample(s, a, tgt, p, c, dt, rows.data(), lam, g);
-    for (int i = 0; i < kCartPhysGrads; ++i) acc[i] += g[i];
-    const float z[5] = {s[0], s[1], s[2], s[3], a};
-    for (int m = 0; m < kCartResHidden; ++m) {
-      float gw[kCartResRow] = {0.f};
-      cart_residual_unit_grads(&rows[m * kCartResRow], z, lam, gw);
-      for (int j = 0; j < kCartResRow; ++j) acc[kCartFitHead + j * kCartResHidden + m] += gw[j];
-    }
-    out.add(b, B, l);
-  }
-  out.finish(B);
-  for (int e = 0; e < kCartFitRow; ++e) {
-    const int dest = cart_fit_dest(e);
-    if (dest >= 0) grad[dest] = acc[e];
-  }
-  return APG_OK;
+  std::vector<float> rows;
+  return fit_host<CartFit>(cart_learnt_check(model, true), state, action, target,
+                           eval_params ? &ce : nullptr, 0.f, B, loss_partials, loss, grad,
+                           FitNoScale{}, ResidualTensors{}, [&] {
+                             CartFitModel m;
+                             m.dt = dt;
+                             learnt_setup(*model, dt, m.p, m.c, rows);
+                             m.rows = rows.data();
+                             return m;
+                           });
 }
 
 }  // extern "C"
@@ -882,84 +909,33 @@ int apg_wing_learnt_rollout_fwd_bwd_cpu(const float *state0, const float *action
   return APG_OK;
 }
 
-// apg_cpu_wing_fit.h: wing_learnt_fit_kernel (wing_learnt.hip) lane for lane,
-// the batch summed in order; the regulariser as its reduction kernel adds it
+// apg_cpu_wing_fit.h: fit_host on WingFit (wing_learnt_math.h) - the table and
+// the packed unit rows built as the pack kernel does
 int apg_wing_learnt_fit_fwd_bwd_cpu(const float *state, const float *action, float dt,
                                     const ApgWingLearnt *model, const float *target,
                                     const ApgWingParams *eval_params, float l2_lambda, int B,
                                     float *loss_partials, float *loss, float *grad,
                                     float *workspace) {
   (void)workspace;
-  if (B < 0) return fail("B must be >= 0 (got %d)", B);
-  if (!model || !model->theta || !model->inertia || !model->w1 || !model->b1 || !model->w2 ||
-      !model->b2)
-    return fail("model or one of its pointers is NULL");
-  if ((target != nullptr) == (eval_params != nullptr))
-    return fail("exactly one of target / eval_params must be given");
-  if (!(l2_lambda >= 0.f)) return fail("l2_lambda must be >= 0");
-  if (!grad) return fail("grad is NULL");
-  for (int i = 0; i < kWingFitGrads; ++i) grad[i] = 0.f;
-  if (B == 0) {
-    if (loss) *loss = 0.f;
-    return APG_OK;
-  }
-  if (!state || !action || !loss_partials)
-    return fail("state / action / loss_partials must not be NULL");
-  const WingGeneralConst k = wing_learnt_table(model->theta, model->inertia, dt);
+  const bool ok = model && model->theta && model->inertia && model->w1 && model->b1 &&
+                  model->w2 && model->b2;
   const WingConst ke = eval_params ? make_const(*eval_params, dt) : WingConst{};
-  std::vector<float> rows(kWingResFloats), acc(kWingFitRow, 0.f);
-  for (int t = 0; t < kWingResFloats; ++t)
-    rows[t] = wing_residual_packed(t, model->w1, model->b1, model->w2, model->b2);
-  const float *rw = rows.data();
-  LossOut out{loss_partials, loss};
-  for (int b = 0; b < B; ++b) {
-    float s[12], a[4], tgt[12], lam[12], z[16];
-    for (int i = 0; i < 12; ++i) s[i] = z[i] = state[(size_t)b * 12 + i];
-    for (int i = 0; i < 4; ++i) a[i] = z[12 + i] = action[(size_t)b * 4 + i];
-    if (eval_params) {
-      for (int i = 0; i < 12; ++i) tgt[i] = s[i];
-      wing_step(tgt, a, ke);
-    } else {
-      for (int i = 0; i < 12; ++i) tgt[i] = target[(size_t)b * 12 + i];
-    }
-    WingParamGrads pg;
-    for (int i = 0; i < kWingParamGrads; ++i) pg.v[i] = 0.f;
-    const float l = wing_learnt_fit_sample(s, a, tgt, k, rw, lam, pg);
-    for (int i = 0; i < kWingParamGrads; ++i) acc[i] += pg.v[i];
-    for (int o = 0; o < 12; ++o) acc[kWingParamGrads + o] += lam[o];
-    for (int m = 0; m < kWingResHidden; ++m) {
-      float gw[kWingFitUnit] = {0.f};
-      wing_residual_unit_grads(rw + m * kWingResRow, z, lam, gw);
-      for (int j = 0; j < kWingFitUnit; ++j)
-        acc[kWingFitHead + j * kWingResHidden + m] += gw[j];
-    }
-    out.add(b, B, l);
-  }
-  out.finish(B);
-  float norms[4] = {0.f, 0.f, 0.f, 0.f};
-  if (l2_lambda > 0.f) {
-    const float *tens[4] = {model->w2, model->b2, model->w1, model->b1};
-    const int count[4] = {12 * kWingResHidden, 12, kWingResHidden * 16, kWingResHidden};
-    for (int q = 0; q < 4; ++q) {
-      float ss = 0.f;
-      for (int t = 0; t < count[q]; ++t) ss = fmaf(tens[q][t], tens[q][t], ss);
-      norms[q] = sqrtf(ss);
-    }
-    if (loss) *loss += l2_lambda * (((norms[0] + norms[1]) + norms[2]) + norms[3]);
-  }
-  for (int c = 0; c < kWingFitRow; ++c) {
-    const int dest = wing_fit_dest(c);
-    if (dest < 0) continue;
-    grad[dest] = acc[c] + (l2_lambda > 0.f
-                               ? wing_fit_l2_grad(dest, l2_lambda, model->w1, model->b1,
-                                                  model->w2, model->b2, norms)
-                               : 0.f);
-  }
-  return APG_OK;
+  WingGeneralConst k;
+  std::vector<float> rows(kWingResFloats);
+  return fit_host<WingFit>(
+      ok ? nullptr : "model or one of its pointers is NULL", state, action, target,
+      eval_params ? &ke : nullptr, l2_lambda, B, loss_partials, loss, grad, FitNoScale{},
+      ok ? ResidualTensors{model->w1, model->b1, model->w2, model->b2} : ResidualTensors{},
+      [&] {
+        k = wing_learnt_table(model->theta, model->inertia, dt);
+        for (int t = 0; t < kWingResFloats; ++t)
+          rows[t] = wing_residual_packed(t, model->w1, model->b1, model->w2, model->b2);
+        return WingFitModel<const WingGeneralConst, const float *>{&k, rows.data()};
+      });
 }
 
-// apg_cpu_quad_fit.h: quad_learnt_fit_kernel (quad_fit.hip) lane for lane, the
-// batch summed in order; the regulariser as its reduction kernel adds it
+// apg_cpu_quad_fit.h: fit_host on QuadFit (quad_fit_math.h) - the model packed
+// as the pack kernel does
 int apg_quad_learnt_fit_fwd_bwd_cpu(const float *state, const float *action, float dt,
                                     const ApgQuadParams *params,
                                     const ApgLearntResidual *model, const float *target,
@@ -967,70 +943,20 @@ int apg_quad_learnt_fit_fwd_bwd_cpu(const float *state, const float *action, flo
                                     float *loss_partials, float *loss, float *grad,
                                     float *workspace) {
   (void)workspace;
-  if (B < 0) return fail("B must be >= 0 (got %d)", B);
-  if (!params) return fail("params is NULL");
-  if (!model || !model->linear_at || !model->w1 || !model->b1 || !model->w2 || !model->b2)
-    return fail("model or one of its pointers is NULL");
-  if ((target != nullptr) == (eval_params != nullptr))
-    return fail("exactly one of target / eval_params must be given");
-  if (!(l2_lambda >= 0.f)) return fail("l2_lambda must be >= 0");
-  if (!grad) return fail("grad is NULL");
-  for (int i = 0; i < kQuadFitGrads; ++i) grad[i] = 0.f;
-  if (B == 0) {
-    if (loss) *loss = 0.f;
-    return APG_OK;
-  }
-  if (!state || !action || !loss_partials)
-    return fail("state / action / loss_partials must not be NULL");
-  const QuadConst c = make_const(*params, dt);
+  const bool ok = model && model->linear_at && model->w1 && model->b1 && model->w2 && model->b2;
   const QuadConst ce = eval_params ? make_const(*eval_params, dt) : QuadConst{};
-  const QuadFitInertia q = make_fit_inertia(*params, dt);
-  std::vector<float> pack(kQuadPackFloats), acc(kQuadFitRow, 0.f);
-  for (int t = 0; t < kQuadPackFloats; ++t) pack[t] = quad_fit_packed(t, *model);
-  const float *pk = pack.data();
-  LossOut out{loss_partials, loss};
-  for (int b = 0; b < B; ++b) {
-    float s[12], a[4], tgt[12], lam[12], x[16], hd[kQuadFitHUsed];
-    for (int i = 0; i < 12; ++i) s[i] = state[(size_t)b * 12 + i];
-    for (int i = 0; i < 4; ++i) a[i] = action[(size_t)b * 4 + i];
-    const Trig t = make_trig(&s[3]);
-    if (eval_params) {
-      for (int i = 0; i < 12; ++i) tgt[i] = s[i];
-      quad_step(tgt, a, ce, t);
-    } else {
-      for (int i = 0; i < 12; ++i) tgt[i] = target[(size_t)b * 12 + i];
-    }
-    const float l = quad_learnt_fit_sample(s, a, tgt, c, t, pk, lam, x, hd);
-    for (int i = 0; i < kQuadFitHUsed; ++i) acc[i] += hd[i];
-    for (int m = 0; m < kResHidden; ++m) {
-      float gw[kResFitUnit] = {0.f};
-      residual_unit_grads<kQuadResW2, kQuadResB1>(pk + m * kQuadResRow, x, lam, gw);
-      for (int j = 0; j < kResFitUnit; ++j) acc[kQuadFitHead + j * kResHidden + m] += gw[j];
-    }
-    out.add(b, B, l);
-  }
-  out.finish(B);
-  float norms[4] = {0.f, 0.f, 0.f, 0.f};
-  if (l2_lambda > 0.f) {
-    const float *tens[4] = {model->w2, model->b2, model->w1, model->b1};
-    const int count[4] = {12 * kResHidden, 12, kResHidden * 16, kResHidden};
-    for (int k = 0; k < 4; ++k) {
-      float ss = 0.f;
-      for (int t = 0; t < count[k]; ++t) ss = fmaf(tens[k][t], tens[k][t], ss);
-      norms[k] = sqrtf(ss);
-    }
-    if (loss) *loss += l2_lambda * (((norms[0] + norms[1]) + norms[2]) + norms[3]);
-  }
-  for (int e = 0; e < kQuadFitRow; ++e) {
-    const int dest = quad_fit_dest(e);
-    if (dest < 0) continue;
-    grad[dest] = quad_fit_value(e, acc[e], q) +
-                 (l2_lambda > 0.f
-                      ? residual_l2_grad<kQuadFitGW1, kQuadFitGB1, kQuadFitGW2, kQuadFitGB2>(
-                            dest, l2_lambda, model->w1, model->b1, model->w2, model->b2, norms)
-                      : 0.f);
-  }
-  return APG_OK;
+  QuadConst c;
+  std::vector<float> pack(kQuadPackFloats);
+  return fit_host<QuadFit>(
+      !params ? "params is NULL" : ok ? nullptr : "model or one of its pointers is NULL", state,
+      action, target, eval_params ? &ce : nullptr, l2_lambda, B, loss_partials, loss, grad,
+      params ? make_fit_inertia(*params, dt) : QuadFitInertia{},
+      ok ? ResidualTensors{model->w1, model->b1, model->w2, model->b2} : ResidualTensors{},
+      [&] {
+        c = make_const(*params, dt);
+        for (int t = 0; t < kQuadPackFloats; ++t) pack[t] = quad_fit_packed(t, *model);
+        return QuadFitModel<const float *>{c, pack.data()};
+      });
 }
 
 }  // extern "C"

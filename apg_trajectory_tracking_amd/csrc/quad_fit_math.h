@@ -7,9 +7,10 @@
 // and what one sample adds to the cotangent of every parameter.  The physics is
 // quad_step / quad_step_adjoint of quad_math.h on the constants of construction
 // time (the reference's torch.diag copies, :48-50); the residual's weights are
-// read from packed unit rows; a hidden unit's cotangents, the regulariser and
-// the reduction are residual_fit.h.  Called per lane by quad_fit.hip and per
-// sample by its host twin (csrc/cpu_twins.hip).
+// read from packed unit rows; the fit's skeleton, a hidden unit's cotangents,
+// the regulariser and the reduction are residual_fit.h, which reads this system
+// through QuadFit below.  Called per lane by quad_fit.hip and per sample by its
+// host twin (csrc/cpu_twins.hip).
 #pragma once
 #include "quad_math.h"
 #include "residual_fit.h"
@@ -157,6 +158,77 @@ __host__ __device__ __forceinline__ float quad_learnt_fit_sample(
   for (int o = 0; o < 12; ++o) head[kQuadFitHB2 + o] = lam[o];
   return loss;
 }
+
+// What residual_fit.h's shared fit reads of this system.  The model: the step's
+// constants and the packed model, which starts with the unit rows (device: the
+// pack in the workspace through the constant address space; host: plain).
+template <class P>
+struct QuadFitModel {
+  const QuadConst &c;
+  P rows;
+};
+
+#if defined(__HIPCC__)
+// the fit kernel's arguments (residual_fit.h fills the common ones)
+struct QuadFitArgs {
+  const float *state, *action, *target;   // target NULL: the analytic step on `eval`
+  const float *ws;                        // the pack
+  float *loss_partials, *rows;
+  QuadConst c, eval;
+  int B;
+};
+#endif
+
+struct QuadFit {
+  static constexpr int S = 12, A = 4, IN = 16, OUT = 12;
+  static constexpr int RES_ROW = kQuadResRow, RW2 = kQuadResW2, RB1 = kQuadResB1;
+  static constexpr int UNIT = kResFitUnit, UW2 = 16, UB1 = 28;
+  static constexpr int HEAD = kQuadFitHead, USED = kQuadFitHUsed, ROW = kQuadFitRow;
+  static constexpr int GRADS = kQuadFitGrads;
+  static constexpr bool REG = true;
+  static constexpr int G_W1 = kQuadFitGW1, G_B1 = kQuadFitGB1, G_W2 = kQuadFitGW2,
+                       G_B2 = kQuadFitGB2;
+  static constexpr int NORMS_AT = kQuadPackFloats, ROWS_AT = NORMS_AT + 16;
+  typedef QuadConst Eval;
+  typedef QuadFitInertia Scale;
+
+  static __host__ __device__ __forceinline__ int dest(int c) { return quad_fit_dest(c); }
+  static __host__ __device__ __forceinline__ float value(int c, float v, const Scale &q) {
+    return quad_fit_value(c, v, q);
+  }
+
+  // (the eval dynamics takes the RAW action; z = [s; a'], the transformed one)
+  template <class M>
+  static __host__ __device__ __forceinline__ float sample(const M &m, const float (&s)[12],
+                                                          const float (&a)[4], float (&tgt)[12],
+                                                          const QuadConst *eval,
+                                                          float (&lam)[12], float (&z)[16],
+                                                          float (&hd)[USED]) {
+    const Trig t = make_trig(&s[3]);
+    if (eval) {
+#pragma unroll
+      for (int i = 0; i < 12; ++i) tgt[i] = s[i];
+      quad_step(tgt, a, *eval, t);
+    }
+    return quad_learnt_fit_sample(s, a, tgt, m.c, t, m.rows, lam, z, hd);
+  }
+
+#if defined(__HIPCC__)
+  typedef QuadFitArgs Args;
+  static constexpr int UNROLL = 2;
+  typedef __attribute__((address_space(4))) const float *cfloat_ptr;
+  typedef QuadFitModel<cfloat_ptr> Model;
+
+  static __device__ __forceinline__ Model model(const Args &A) {
+    return Model{A.c, (cfloat_ptr)A.ws};
+  }
+  static __device__ __forceinline__ void unit_row(const Args &A, const Model &, int lane,
+                                                  float (&w)[RES_ROW]) {
+#pragma unroll
+    for (int j = 0; j < kQuadResRow; ++j) w[j] = A.ws[lane * kQuadResRow + j];
+  }
+#endif
+};
 
 }  // namespace
 }  // namespace apg

@@ -181,25 +181,14 @@ __global__ __launch_bounds__(kWave) void wing_learnt_rollout_kernel(WingLearntRo
 
 // ------------------------------------------------ the simulator fit's step --
 // TrainBase.train_dynamics_model (scripts/train_base.py:160-186) for this
-// module as three launches behind one entry point: pack (the table, the rows
-// and the four weight norms from the live tensors), the fit kernel (forward,
-// target, loss, reverse sweep, every parameter's cotangent summed over the
-// WORKGROUP), and a reduction over the workgroups' rows that also adds the
-// regulariser.  No float atomics: a wave sums its 64 samples (the physical
-// cotangents and db2 by a shuffle tree; the weights' by lane m = hidden unit m
-// looping over the wave's samples in LDS), the four waves of a workgroup are
-// added in wave order in LDS, the rows by a fixed tree.
+// module as three launches behind one entry point, the shared fit of
+// residual_fit.h on WingFit (wing_learnt_math.h): pack (the table, the rows and
+// the four weight norms from the live tensors), the fit kernel (the row's head:
+// the 50 physical cotangents of the reverse sweep, db2) and the reduction.
 static_assert(kWingFitGW1 == APG_WING_FIT_G_W1 && kWingFitGB1 == APG_WING_FIT_G_B1 &&
                   kWingFitGW2 == APG_WING_FIT_G_W2 && kWingFitGB2 == APG_WING_FIT_G_B2 &&
                   kWingFitGrads == APG_WING_FIT_GRADS && APG_WING_FIT_G_I == 41,
               "apg.h publishes these offsets");
-constexpr int kFitBlock = 256, kFitWaves = kFitBlock / kWave;
-constexpr int kFitSample = 28;                    // z (16), lam (12) per sample
-// a wave's LDS: its samples [28][64] first, its 29 weight planes [29][64] after
-constexpr int kFitWaveLds = kWingFitUnit * kWave;
-static_assert(kFitSample <= kWingFitUnit, "the weight planes re-use the sample planes");
-// workspace: [pack | norms (4), padded to 16 | rows]
-constexpr int kFitNorms = kWingLearntPackFloats, kFitRows = kFitNorms + 16;
 
 // wing_learnt_rollout_pack_kernel's content plus |W2|, |b2|, |W1|, |b1|
 // (2-norms; per-thread strided sums, then a fixed tree)
@@ -213,145 +202,21 @@ __global__ __launch_bounds__(256) void wing_learnt_fit_pack_kernel(ApgWingLearnt
   }
   for (int t = threadIdx.x; t < kWingResFloats; t += blockDim.x)
     ws[kWingLearntTableFloats + t] = wing_residual_packed(t, m.w1, m.b1, m.w2, m.b2);
-  residual_norms(m.w1, m.b1, m.w2, m.b2, part, ws + kFitNorms);
+  residual_norms(m.w1, m.b1, m.w2, m.b2, part, ws + WingFit::NORMS_AT);
 }
-
-struct WingFitArgs {
-  const float *state, *action, *target;   // target NULL: the analytic step on `eval`
-  const float *ws;                        // the pack
-  float *loss_partials, *rows;
-  WingConst eval;
-  int B;
-};
 
 template <bool EVAL>
 __global__ __launch_bounds__(kFitBlock) void wing_learnt_fit_kernel(WingFitArgs A) {
-  __shared__ float smp[kFitWaves][kFitWaveLds];
-  __shared__ float head[kFitWaves][kWingFitHead];
-  typedef __attribute__((address_space(4))) const float *cfloat_ptr;
-  WingGeneralConstK *kp = (WingGeneralConstK *)A.ws;
-  cfloat_ptr rows = (cfloat_ptr)(A.ws + kWingLearntTableFloats);
-  const int lane = threadIdx.x & (kWave - 1), wl = threadIdx.x >> 6;
-  const int b = blockIdx.x * kFitBlock + threadIdx.x;
-  const bool live = b < A.B;
-  const int bb = live ? b : A.B - 1;
-  WingParamGrads pg;
-#pragma unroll
-  for (int i = 0; i < kWingParamGrads; ++i) pg.v[i] = 0.f;
-  float s[12], a[4], tgt[12], lam[12];
-  load_state<APG_LAYOUT_AOS, 12>(A.state, A.B, bb, s);
-  load_state<APG_LAYOUT_AOS, 4>(A.action, A.B, bb, a);
-  if constexpr (EVAL) {
-#pragma unroll
-    for (int i = 0; i < 12; ++i) tgt[i] = s[i];
-    const WingConst &ke = A.eval;
-    wing_step(tgt, a, ke);
-  } else {
-    load_state<APG_LAYOUT_AOS, 12>(A.target, A.B, bb, tgt);
-  }
-  float loss = wing_learnt_fit_sample(s, a, tgt, *kp, rows, lam, pg);
-  // a dead lane adds nothing: zero seed, zero cotangents
-  if (!live) {
-    loss = 0.f;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) lam[i] = 0.f;
-#pragma unroll
-    for (int i = 0; i < kWingParamGrads; ++i) pg.v[i] = 0.f;
-  }
-  write_wave_partial(A.loss_partials, loss, (A.B + kWave - 1) / kWave);
-#pragma unroll
-  for (int i = 0; i < kWingParamGrads; ++i) {
-    const float v = wave_sum(pg.v[i]);
-    if (lane == 0) head[wl][i] = v;
-  }
-#pragma unroll
-  for (int o = 0; o < 12; ++o) {
-    const float v = wave_sum(lam[o]);   // db2
-    if (lane == 0) head[wl][kWingParamGrads + o] = v;
-  }
-  if (lane < 2) head[wl][kWingParamGrads + 12 + lane] = 0.f;
-  // the wave's samples into its LDS planes, then lane m = hidden unit m over
-  // all 64 (each wave reads and writes its own planes only)
-  float *mine = smp[wl];
-#pragma unroll
-  for (int j = 0; j < 12; ++j) mine[j * kWave + lane] = s[j];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) mine[(12 + j) * kWave + lane] = a[j];
-#pragma unroll
-  for (int o = 0; o < 12; ++o) mine[(16 + o) * kWave + lane] = lam[o];
-  __syncthreads();
-  float w[kWingResRow], gw[kWingFitUnit];
-  {
-    const float4 *src = reinterpret_cast<const float4 *>(A.ws + kWingLearntTableFloats +
-                                                         lane * kWingResRow);
-#pragma unroll
-    for (int q = 0; q < kWingResRow / 4; ++q) {
-      const float4 v = src[q];
-      w[4 * q] = v.x, w[4 * q + 1] = v.y, w[4 * q + 2] = v.z, w[4 * q + 3] = v.w;
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < kWingFitUnit; ++j) gw[j] = 0.f;
-#pragma unroll 2
-  for (int n = 0; n < kWave; ++n) {
-    float zn[16], ln[12];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) zn[j] = mine[j * kWave + n];
-#pragma unroll
-    for (int o = 0; o < 12; ++o) ln[o] = mine[(16 + o) * kWave + n];
-    wing_residual_unit_grads(w, zn, ln, gw);
-  }
-  __syncthreads();   // (uniform trip count above: every wave is done reading)
-#pragma unroll
-  for (int j = 0; j < kWingFitUnit; ++j) mine[j * kWave + lane] = gw[j];
-  __syncthreads();
-  // the four waves in wave order -> one row per workgroup
-  float *row = A.rows + (size_t)blockIdx.x * kWingFitRow;
-  for (int c = threadIdx.x; c < kWingFitRow; c += kFitBlock) {
-    float acc;
-    if (c < kWingFitHead) {
-      acc = head[0][c];
-#pragma unroll
-      for (int v = 1; v < kFitWaves; ++v) acc += head[v][c];
-    } else {
-      acc = smp[0][c - kWingFitHead];
-#pragma unroll
-      for (int v = 1; v < kFitWaves; ++v) acc += smp[v][c - kWingFitHead];
-    }
-    row[c] = acc;
-  }
+  fit_body<WingFit, EVAL>(A);
 }
 
-// grad[dest(c)] = sum over the workgroups' rows of element c (+ the
-// regulariser's gradient); kFitSplit threads per element: thread r adds rows
-// r, r + kFitSplit, ... in order, then a fixed tree over the kFitSplit sums.
-// Thread 0 of workgroup 0 adds the penalty to the loss, which the loss
-// reduction in front of this launch has written.
-constexpr int kFitCols = 32, kFitSplit = 8;
 __global__ __launch_bounds__(kFitCols * kFitSplit) void wing_learnt_fit_reduce_kernel(
     const float *__restrict__ ws, int nrows, ApgWingLearnt m, float l2_lambda,
     float *__restrict__ grad, float *__restrict__ loss) {
-  __shared__ float part[kFitSplit][kFitCols];
-  const int col = threadIdx.x % kFitCols, r = threadIdx.x / kFitCols;
-  const int c = blockIdx.x * kFitCols + col;          // kWingFitRow = 60 x 32
-  const float *rows = ws + kFitRows;
-  const float v = fit_rows_sum<kWingFitRow>(rows, nrows, c, col, r, part);
-  if (r == 0) {
-    const int dest = wing_fit_dest(c);
-    if (dest >= 0) {
-      float reg = 0.f;
-      if (l2_lambda > 0.f)
-        reg = wing_fit_l2_grad(dest, l2_lambda, m.w1, m.b1, m.w2, m.b2, ws + kFitNorms);
-      grad[dest] = v + reg;
-    }
-  }
-  if (l2_lambda > 0.f && loss && blockIdx.x == 0 && threadIdx.x == 0) {
-    const float *n = ws + kFitNorms;
-    loss[0] += l2_lambda * (((n[0] + n[1]) + n[2]) + n[3]);
-  }
+  fit_reduce<WingFit>(ws + WingFit::ROWS_AT, nrows, FitNoScale{},
+                      ResidualTensors{m.w1, m.b1, m.w2, m.b2}, ws + WingFit::NORMS_AT,
+                      l2_lambda, grad, loss);
 }
-static_assert(kWingFitRow % kFitCols == 0 && kFitSplit == 8,
-              "whole workgroups of columns; fit_rows_sum adds eight sums");
 
 int check_learnt(const void *state, const void *action, const void *params,
                  const float *inertia, int B) {
@@ -489,60 +354,34 @@ int apg_wing_learnt_rollout_fwd_bwd(const float *state0, const float *actions, c
 
 int apg_wing_learnt_fit_grad_count(void) { return kWingFitGrads; }
 
-int apg_wing_learnt_fit_workspace_floats(int B) {
-  return B <= 0 ? 0 : kFitRows + grid_for(B, kFitBlock) * kWingFitRow;
-}
+int apg_wing_learnt_fit_workspace_floats(int B) { return fit_workspace_floats<WingFit>(B); }
 
 int apg_wing_learnt_fit_fwd_bwd(const float *state, const float *action, float dt,
                                 const ApgWingLearnt *model, const float *target,
                                 const ApgWingParams *eval_params, float l2_lambda, int B,
                                 float *loss_partials, float *loss, float *grad,
                                 float *workspace, apg_stream_t stream) {
-  if (B < 0) { set_error("B must be >= 0 (got %d)", B); return APG_ERR_ARG; }
+  const char *bad = nullptr;
   if (!model || !model->theta || !model->inertia || !model->w1 || !model->b1 || !model->w2 ||
-      !model->b2) {
-    set_error("model or one of its pointers is NULL");
-    return APG_ERR_ARG;
-  }
-  if ((target != nullptr) == (eval_params != nullptr)) {
-    set_error("exactly one of target / eval_params must be given");
-    return APG_ERR_ARG;
-  }
-  if (!(l2_lambda >= 0.f)) { set_error("l2_lambda must be >= 0"); return APG_ERR_ARG; }
-  if (!grad) { set_error("grad is NULL"); return APG_ERR_ARG; }
+      !model->b2)
+    bad = "model or one of its pointers is NULL";
   hipStream_t st = (hipStream_t)stream;
-  if (B == 0) {
-    if (hipMemsetAsync(grad, 0, kWingFitGrads * sizeof(float), st) != hipSuccess ||
-        (loss && hipMemsetAsync(loss, 0, sizeof(float), st) != hipSuccess))
-      return check_launch("memset(grad, loss)");
-    return APG_OK;
-  }
-  if (!state || !action || !loss_partials || !workspace) {
-    set_error("state / action / loss_partials / workspace must not be NULL");
-    return APG_ERR_ARG;
-  }
-  hipLaunchKernelGGL(wing_learnt_fit_pack_kernel, dim3(1), dim3(256), 0, st, *model, dt,
-                     workspace);
-  WingFitArgs A;
-  A.state = state, A.action = action, A.target = target;
-  A.ws = workspace, A.loss_partials = loss_partials, A.rows = workspace + kFitRows;
-  A.B = B;
-  const int blocks = grid_for(B, kFitBlock);
-  if (eval_params) {
-    A.eval = make_const(*eval_params, dt);
-    hipLaunchKernelGGL(wing_learnt_fit_kernel<true>, dim3(blocks), dim3(kFitBlock), 0, st, A);
-  } else {
-    A.eval = WingConst{};
-    hipLaunchKernelGGL(wing_learnt_fit_kernel<false>, dim3(blocks), dim3(kFitBlock), 0, st, A);
-  }
-  if (int e = check_launch("wing_learnt_fit_fwd_bwd")) return e;
-  if (loss)
-    if (int e = launch_reduce_partials(loss_partials, apg_loss_partials_count(B), loss, st))
-      return e;
-  hipLaunchKernelGGL(wing_learnt_fit_reduce_kernel, dim3(kWingFitRow / kFitCols),
-                     dim3(kFitCols * kFitSplit), 0, st, workspace, blocks, *model, l2_lambda,
-                     grad, loss);
-  return check_launch("wing_learnt_fit_reduce");
+  const FitCall call{state, action, target, eval_params != nullptr, l2_lambda, B,
+                     loss_partials, loss, grad, workspace, st, bad};
+  return fit_run<WingFit>(
+      call, "wing_learnt_fit_fwd_bwd", "wing_learnt_fit_reduce", wing_learnt_fit_kernel<true>,
+      wing_learnt_fit_kernel<false>,
+      [&](WingFitArgs &A) {
+        hipLaunchKernelGGL(wing_learnt_fit_pack_kernel, dim3(1), dim3(256), 0, st, *model, dt,
+                           workspace);
+        A.ws = workspace;
+        A.eval = eval_params ? make_const(*eval_params, dt) : WingConst{};
+      },
+      [&](int blocks) {
+        hipLaunchKernelGGL(wing_learnt_fit_reduce_kernel, dim3(WingFit::ROW / kFitCols),
+                           dim3(kFitCols * kFitSplit), 0, st, workspace, blocks, *model,
+                           l2_lambda, grad, loss);
+      });
 }
 
 }  // extern "C"

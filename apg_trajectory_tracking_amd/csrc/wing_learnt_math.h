@@ -247,24 +247,93 @@ __host__ __device__ __forceinline__ float wing_learnt_fit_sample(const float (&s
   return loss;
 }
 
-// gw += hidden unit's 29 cotangents for one sample (residual_fit.h) on this
-// header's packed row
-__host__ __device__ __forceinline__ void wing_residual_unit_grads(const float *w,
-                                                                  const float (&z)[16],
-                                                                  const float (&lam)[12],
-                                                                  float (&gw)[kWingFitUnit]) {
-  residual_unit_grads<kWingResW2, kWingResB1>(w, z, lam, gw);
-}
+// What residual_fit.h's shared fit reads of this system.  The model: the step
+// table and the packed rows (device: both in the constant address space, from
+// the pack in the workspace; host: plain).
+template <class KT, class P>
+struct WingFitModel {
+  KT *k;
+  P rows;
+};
 
-// the regulariser's gradient for element `dest` of the flat gradient
-// (residual_fit.h)
-__host__ __device__ __forceinline__ float wing_fit_l2_grad(int dest, float l2_lambda,
-                                                           const float *w1, const float *b1,
-                                                           const float *w2, const float *b2,
-                                                           const float *norms) {
-  return residual_l2_grad<kWingFitGW1, kWingFitGB1, kWingFitGW2, kWingFitGB2>(
-      dest, l2_lambda, w1, b1, w2, b2, norms);
-}
+#if defined(__HIPCC__)
+// the fit kernel's arguments (residual_fit.h fills the common ones)
+struct WingFitArgs {
+  const float *state, *action, *target;   // target NULL: the analytic step on `eval`
+  const float *ws;                        // the pack
+  float *loss_partials, *rows;
+  WingConst eval;
+  int B;
+};
+#endif
+
+struct WingFit {
+  static constexpr int S = 12, A = 4, IN = 16, OUT = 12;
+  static constexpr int RES_ROW = kWingResRow, RW2 = kWingResW2, RB1 = kWingResB1;
+  static constexpr int UNIT = kWingFitUnit, UW2 = 16, UB1 = 28;
+  static constexpr int HEAD = kWingFitHead, USED = kWingParamGrads + 12, ROW = kWingFitRow;
+  static constexpr int GRADS = kWingFitGrads;
+  static constexpr bool REG = true;
+  static constexpr int G_W1 = kWingFitGW1, G_B1 = kWingFitGB1, G_W2 = kWingFitGW2,
+                       G_B2 = kWingFitGB2;
+  static constexpr int NORMS_AT = kWingLearntPackFloats, ROWS_AT = NORMS_AT + 16;
+  typedef WingConst Eval;
+  typedef FitNoScale Scale;
+
+  static __host__ __device__ __forceinline__ int dest(int c) { return wing_fit_dest(c); }
+  static __host__ __device__ __forceinline__ float value(int, float v, const Scale &) {
+    return v;
+  }
+
+  // the head: the 50 physical cotangents, then db2 = lam
+  template <class M>
+  static __host__ __device__ __forceinline__ float sample(const M &m, const float (&s)[12],
+                                                          const float (&a)[4], float (&tgt)[12],
+                                                          const WingConst *eval,
+                                                          float (&lam)[12], float (&z)[16],
+                                                          float (&hd)[USED]) {
+    if (eval) {
+#pragma unroll
+      for (int i = 0; i < 12; ++i) tgt[i] = s[i];
+      wing_step(tgt, a, *eval);
+    }
+    WingParamGrads pg;
+#pragma unroll
+    for (int i = 0; i < kWingParamGrads; ++i) pg.v[i] = 0.f;
+    const float loss = wing_learnt_fit_sample(s, a, tgt, *m.k, m.rows, lam, pg);
+#pragma unroll
+    for (int i = 0; i < 12; ++i) z[i] = s[i];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) z[12 + i] = a[i];
+#pragma unroll
+    for (int i = 0; i < kWingParamGrads; ++i) hd[i] = pg.v[i];
+#pragma unroll
+    for (int o = 0; o < 12; ++o) hd[kWingParamGrads + o] = lam[o];
+    return loss;
+  }
+
+#if defined(__HIPCC__)
+  typedef WingFitArgs Args;
+  static constexpr int UNROLL = 2;
+  typedef __attribute__((address_space(4))) const float *cfloat_ptr;
+  typedef WingFitModel<WingGeneralConstK, cfloat_ptr> Model;
+
+  static __device__ __forceinline__ Model model(const Args &A) {
+    return Model{(WingGeneralConstK *)A.ws, (cfloat_ptr)(A.ws + kWingLearntTableFloats)};
+  }
+  // (vector loads: one 128-byte line per lane)
+  static __device__ __forceinline__ void unit_row(const Args &A, const Model &, int lane,
+                                                  float (&w)[RES_ROW]) {
+    const float4 *src =
+        reinterpret_cast<const float4 *>(A.ws + kWingLearntTableFloats + lane * kWingResRow);
+#pragma unroll
+    for (int q = 0; q < kWingResRow / 4; ++q) {
+      const float4 v = src[q];
+      w[4 * q] = v.x, w[4 * q + 1] = v.y, w[4 * q + 2] = v.z, w[4 * q + 3] = v.w;
+    }
+  }
+#endif
+};
 
 }  // namespace
 }  // namespace apg

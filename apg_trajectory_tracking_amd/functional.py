@@ -6,6 +6,7 @@ backward enqueues its hand-derived adjoint kernel.  Tensors are the
 reference's row-major ones (`layout="aos"`) unless stated; the fused rollouts
 also accept the device-native SoA layout (`layout="soa"`, batch fastest).
 """
+import collections
 import ctypes
 import math
 
@@ -344,6 +345,79 @@ def _quad_learnt_tensors(dyn):
     return [t if t.is_contiguous() else t.contiguous() for t in tensors]
 
 
+# What differs between the three fused simulator fits (csrc/residual_fit.h) on
+# the way to the C entry point `apg_<name>_fwd_bwd`: `tensors(dyn)` - the
+# contiguous tensors its model struct points to (it raises where `dyn` is not
+# what the fit serves) - and `model(tensors)`, the struct; the state and action
+# widths; the gradient's size and `offsets`, {name of a parameter that enters the
+# fit: where it starts in the flat gradient}; whether `dyn.params`
+# (`sim_params`) and l2_lambda (`regulariser`) are arguments; whether target /
+# eval_params are checked here already (`target_check`), not only by the
+# library; whether a parameter with requires_grad False gets no view
+# (`skip_frozen`).
+_FitSpec = collections.namedtuple(
+    "_FitSpec", "name tensors model state action grads offsets sim_params regulariser "
+    "target_check skip_frozen")
+
+
+def _learnt_fit(spec, dyn, state, action, dt, target, eval_params, l2_lambda):
+    """The fused fit step of `spec` (the three public functions' body):
+    dict(loss [1], grad [spec.grads]), nothing read on the host."""
+    tensors = spec.tensors(dyn)
+    if spec.target_check and (target is None) == (eval_params is None):
+        raise ValueError("exactly one of target / eval_params must be given")
+    state, action = _f32c(state), _f32c(action)
+    if target is not None:
+        target = _f32c(target)
+    require_device(state, action, target, *tensors)
+    S, A = spec.state, spec.action
+    if state.dim() != 2 or state.shape[1] != S or action.shape != (state.shape[0], A):
+        raise ValueError(f"state [B,{S}] / action [B,{A}] expected")
+    if target is not None and target.shape != state.shape:
+        raise ValueError(f"target [B,{S}] expected")
+    B, dev = state.shape[0], state.device
+    grad = torch.empty(spec.grads, dtype=torch.float32, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    parts = torch.empty(_capi.loss_partials_count(B), dtype=torch.float32, device=dev)
+    ws = torch.empty(max(getattr(lib(), f"apg_{spec.name}_workspace_floats")(B), 1),
+                     dtype=torch.float32, device=dev)
+    model = spec.model(tensors)
+    args = [ptr(state), ptr(action), float(dt)]
+    if spec.sim_params:
+        args.append(ctypes.byref(dyn.params))
+    args += [ctypes.byref(model), ptr(target),
+             None if eval_params is None else ctypes.byref(eval_params)]
+    if spec.regulariser:
+        args.append(float(l2_lambda))
+    fn = f"apg_{spec.name}_fwd_bwd"
+    check(getattr(lib(), fn)(*args, B, ptr(parts), ptr(loss), ptr(grad), ptr(ws),
+                             stream_of(state)), fn)
+    return dict(loss=loss, grad=grad)
+
+
+def _fit_grad_views(spec, dyn, grad):
+    """The flat gradient of _learnt_fit as one entry per parameter, in the order
+    (and shapes) of dyn.named_parameters(): a view of `grad` (no copy:
+    `p.grad = view` costs no launch), None for a parameter that
+    `spec.offsets` leaves out or `spec.skip_frozen` excludes."""
+    at, every = spec.offsets, not spec.skip_frozen
+    return [grad[at[name]:at[name] + p.numel()].view_as(p)
+            if name in at and (every or p.requires_grad) else None
+            for name, p in dyn.named_parameters()]
+
+
+_QUAD_FIT = _FitSpec(
+    "quad_learnt_fit", _quad_learnt_tensors,
+    lambda tensors: _capi.ApgLearntResidual(*[t.data_ptr() for t in tensors]),
+    12, 4, _capi.QUAD_FIT_GRADS,
+    {"linear_at": _capi.QUAD_FIT_G_LINEAR_AT, "mass": _capi.QUAD_FIT_G_MASS,
+     "torch_inertia_vector": _capi.QUAD_FIT_G_INERTIA,
+     "torch_kinv_vector": _capi.QUAD_FIT_G_KINV,
+     "linear_state_1.weight": _capi.QUAD_FIT_G_W1, "linear_state_1.bias": _capi.QUAD_FIT_G_B1,
+     "linear_state_2.weight": _capi.QUAD_FIT_G_W2, "linear_state_2.bias": _capi.QUAD_FIT_G_B2},
+    sim_params=True, regulariser=True, target_check=False, skip_frozen=False)
+
+
 def quad_learnt_fit_fwd_bwd(dyn, state, action, dt, target=None, eval_params=None,
                             l2_lambda=0.0):
     """One step of the simulator fit (TrainBase.train_dynamics_model) on the
@@ -356,43 +430,14 @@ def quad_learnt_fit_fwd_bwd(dyn, state, action, dt, target=None, eval_params=Non
     The step runs on `dyn.params`, the constants of construction time, as the
     module's forward does; its tensors are read on the device when the launches
     run: no host read, no synchronisation, capturable in a graph."""
-    tensors = _quad_learnt_tensors(dyn)
-    state, action = _f32c(state), _f32c(action)
-    if target is not None:
-        target = _f32c(target)
-    require_device(state, action, target, *tensors)
-    if state.dim() != 2 or state.shape[1] != 12 or action.shape != (state.shape[0], 4):
-        raise ValueError("state [B,12] / action [B,4] expected")
-    if target is not None and target.shape != state.shape:
-        raise ValueError("target [B,12] expected")
-    B, dev = state.shape[0], state.device
-    grad = torch.empty(_capi.QUAD_FIT_GRADS, dtype=torch.float32, device=dev)
-    loss = torch.empty(1, dtype=torch.float32, device=dev)
-    parts = torch.empty(_capi.loss_partials_count(B), dtype=torch.float32, device=dev)
-    ws = torch.empty(max(lib().apg_quad_learnt_fit_workspace_floats(B), 1),
-                     dtype=torch.float32, device=dev)
-    model = _capi.ApgLearntResidual(*[t.data_ptr() for t in tensors])
-    check(lib().apg_quad_learnt_fit_fwd_bwd(
-        ptr(state), ptr(action), float(dt), ctypes.byref(dyn.params), ctypes.byref(model),
-        ptr(target), None if eval_params is None else ctypes.byref(eval_params),
-        float(l2_lambda), B, ptr(parts), ptr(loss), ptr(grad), ptr(ws), stream_of(state)),
-        "apg_quad_learnt_fit_fwd_bwd")
-    return dict(loss=loss, grad=grad)
+    return _learnt_fit(_QUAD_FIT, dyn, state, action, dt, target, eval_params, l2_lambda)
 
 
 def quad_learnt_fit_grad_views(dyn, grad):
     """The flat gradient of quad_learnt_fit_fwd_bwd as one view per parameter,
     in the order (and shapes) of dyn.named_parameters().  Views, not copies:
     `p.grad = view` costs no launch."""
-    at = {"linear_at": _capi.QUAD_FIT_G_LINEAR_AT, "mass": _capi.QUAD_FIT_G_MASS,
-          "torch_inertia_vector": _capi.QUAD_FIT_G_INERTIA,
-          "torch_kinv_vector": _capi.QUAD_FIT_G_KINV,
-          "linear_state_1.weight": _capi.QUAD_FIT_G_W1,
-          "linear_state_1.bias": _capi.QUAD_FIT_G_B1,
-          "linear_state_2.weight": _capi.QUAD_FIT_G_W2,
-          "linear_state_2.bias": _capi.QUAD_FIT_G_B2}
-    return [grad[at[name]:at[name] + p.numel()].view(p.shape)
-            for name, p in dyn.named_parameters()]
+    return _fit_grad_views(_QUAD_FIT, dyn, grad)
 
 
 class _QuadLoss(torch.autograd.Function):
@@ -559,6 +604,17 @@ def wing_learnt_rollout_loss(dyn, state0, action_seq, ref, dt, weights=None):
             dyn, s, a, _f32c(ref), dt, weights, want_grad_state0=want))
 
 
+_WING_FIT = _FitSpec(
+    "wing_learnt_fit", _wing_learnt_tensors,
+    lambda tensors: _capi.ApgWingLearnt(*[t.data_ptr() for t in tensors]),
+    12, 4, _capi.WING_FIT_GRADS,
+    {"I": _capi.WING_FIT_G_I, "linear_state_1.weight": _capi.WING_FIT_G_W1,
+     "linear_state_1.bias": _capi.WING_FIT_G_B1, "linear_state_2.weight": _capi.WING_FIT_G_W2,
+     "linear_state_2.bias": _capi.WING_FIT_G_B2,
+     **{"cfg." + k: i for i, k in enumerate(_capi.WING_PARAM_FIELDS)}},
+    sim_params=False, regulariser=True, target_check=False, skip_frozen=False)
+
+
 def wing_learnt_fit_fwd_bwd(dyn, state, action, dt, target=None, eval_params=None,
                             l2_lambda=0.0):
     """One step of the simulator fit (TrainBase.train_dynamics_model) on the
@@ -570,28 +626,7 @@ def wing_learnt_fit_fwd_bwd(dyn, state, action, dt, target=None, eval_params=Non
     (an ApgWingParams, e.g. FixedWingDynamics.params) - exactly one of the two.
     The module's tensors are read on the device when the launches run: no host
     read, no synchronisation, capturable in a graph."""
-    tensors = _wing_learnt_tensors(dyn)
-    state, action = _f32c(state), _f32c(action)
-    if target is not None:
-        target = _f32c(target)
-    require_device(state, action, target, *tensors)
-    if state.dim() != 2 or state.shape[1] != 12 or action.shape != (state.shape[0], 4):
-        raise ValueError("state [B,12] / action [B,4] expected")
-    if target is not None and target.shape != state.shape:
-        raise ValueError("target [B,12] expected")
-    B, dev = state.shape[0], state.device
-    grad = torch.empty(_capi.WING_FIT_GRADS, dtype=torch.float32, device=dev)
-    loss = torch.empty(1, dtype=torch.float32, device=dev)
-    parts = torch.empty(_capi.loss_partials_count(B), dtype=torch.float32, device=dev)
-    ws = torch.empty(max(lib().apg_wing_learnt_fit_workspace_floats(B), 1),
-                     dtype=torch.float32, device=dev)
-    model = _capi.ApgWingLearnt(*[t.data_ptr() for t in tensors])
-    check(lib().apg_wing_learnt_fit_fwd_bwd(
-        ptr(state), ptr(action), float(dt), ctypes.byref(model), ptr(target),
-        None if eval_params is None else ctypes.byref(eval_params), float(l2_lambda), B,
-        ptr(parts), ptr(loss), ptr(grad), ptr(ws), stream_of(state)),
-        "apg_wing_learnt_fit_fwd_bwd")
-    return dict(loss=loss, grad=grad)
+    return _learnt_fit(_WING_FIT, dyn, state, action, dt, target, eval_params, l2_lambda)
 
 
 def wing_learnt_fit_grad_views(dyn, grad):
@@ -599,19 +634,7 @@ def wing_learnt_fit_grad_views(dyn, grad):
     in the order (and shapes) of dyn.named_parameters(): `I` [3,3], each
     `cfg.<name>` [1], the residual's four tensors.  Views, not copies:
     `p.grad = view` costs no launch."""
-    at = {"I": (_capi.WING_FIT_G_I, (3, 3)),
-          "linear_state_1.weight": (_capi.WING_FIT_G_W1, (64, 16)),
-          "linear_state_1.bias": (_capi.WING_FIT_G_B1, (64,)),
-          "linear_state_2.weight": (_capi.WING_FIT_G_W2, (12, 64)),
-          "linear_state_2.bias": (_capi.WING_FIT_G_B2, (12,))}
-    views = []
-    for name, p in dyn.named_parameters():
-        if name.startswith("cfg."):
-            off, shape = _capi.WING_PARAM_FIELDS.index(name[4:]), (1,)
-        else:
-            off, shape = at[name]
-        views.append(grad[off:off + p.numel()].view(shape))
-    return views
+    return _fit_grad_views(_WING_FIT, dyn, grad)
 
 
 # -------------------------------------------------------------- cartpole
@@ -793,6 +816,25 @@ def cartpole_learnt_fusable(dyn):
             and len(list(dyn.parameters())) == 3 + len(dyn.cfg))
 
 
+def _cartpole_fit_tensors(dyn):
+    if not cartpole_learnt_fusable(dyn):
+        raise ValueError("fused fit expects a LearntCartpoleDynamics with [1] "
+                         "parameters and the 5 -> 64 -> 4 residual network as "
+                         "contiguous fp32 tensors on one CUDA device")
+    return [t.detach() for t in _cartpole_learnt_tensors(dyn)]
+
+
+# (the `cfg` keys outside the physics have no offset: no gradient, as autograd)
+_CARTPOLE_FIT = _FitSpec(
+    "cartpole_learnt_fit", _cartpole_fit_tensors, _cartpole_learnt_model,
+    4, 1, _capi.CARTPOLE_LEARNT_GRADS,
+    {"linear_state_1.weight": _capi.CARTPOLE_LEARNT_G_W1,
+     "linear_state_1.bias": _capi.CARTPOLE_LEARNT_G_B1,
+     "linear_state_2.weight": _capi.CARTPOLE_LEARNT_G_W2,
+     **{"cfg." + k: i for i, k in enumerate(_capi.CARTPOLE_LEARNT_FIELDS)}},
+    sim_params=False, regulariser=False, target_check=True, skip_frozen=True)
+
+
 def cartpole_learnt_fit_fwd_bwd(dyn, state, action, dt, target=None, eval_params=None):
     """One step of the simulator fit (TrainBase.train_dynamics_model) on the
     LearntCartpoleDynamics `dyn`, fused (apg_cartpole_learnt_fit_fwd_bwd):
@@ -803,34 +845,7 @@ def cartpole_learnt_fit_fwd_bwd(dyn, state, action, dt, target=None, eval_params
     ApgCartpoleParams, e.g. CartpoleDynamics.params) - exactly one of the two.
     The module's tensors are read on the device when the launches run: no host
     read, no synchronisation, capturable in a graph."""
-    if not cartpole_learnt_fusable(dyn):
-        raise ValueError("fused fit expects a LearntCartpoleDynamics with [1] "
-                         "parameters and the 5 -> 64 -> 4 residual network as "
-                         "contiguous fp32 tensors on one CUDA device")
-    if (target is None) == (eval_params is None):
-        raise ValueError("exactly one of target / eval_params must be given")
-    tensors = [t.detach() for t in _cartpole_learnt_tensors(dyn)]
-    state, action = _f32c(state), _f32c(action)
-    if target is not None:
-        target = _f32c(target)
-    require_device(state, action, target, *tensors)
-    if state.dim() != 2 or state.shape[1] != 4 or action.shape != (state.shape[0], 1):
-        raise ValueError("state [B,4] / action [B,1] expected")
-    if target is not None and target.shape != state.shape:
-        raise ValueError("target [B,4] expected")
-    B, dev = state.shape[0], state.device
-    grad = torch.empty(_capi.CARTPOLE_LEARNT_GRADS, dtype=torch.float32, device=dev)
-    loss = torch.empty(1, dtype=torch.float32, device=dev)
-    parts = torch.empty(_capi.loss_partials_count(B), dtype=torch.float32, device=dev)
-    ws = torch.empty(max(lib().apg_cartpole_learnt_fit_workspace_floats(B), 1),
-                     dtype=torch.float32, device=dev)
-    model = _cartpole_learnt_model(tensors)
-    check(lib().apg_cartpole_learnt_fit_fwd_bwd(
-        ptr(state), ptr(action), float(dt), ctypes.byref(model), ptr(target),
-        None if eval_params is None else ctypes.byref(eval_params), B, ptr(parts),
-        ptr(loss), ptr(grad), ptr(ws), stream_of(state)),
-        "apg_cartpole_learnt_fit_fwd_bwd")
-    return dict(loss=loss, grad=grad)
+    return _learnt_fit(_CARTPOLE_FIT, dyn, state, action, dt, target, eval_params, 0.0)
 
 
 def cartpole_learnt_fit_grad_views(dyn, grad):
@@ -839,13 +854,7 @@ def cartpole_learnt_fit_grad_views(dyn, grad):
     `p.grad = view` costs no launch) where autograd would leave a gradient,
     None where it would not - the `cfg` keys that do not enter the physics and
     every parameter with requires_grad False (`not_trainable`)."""
-    at = {"linear_state_1.weight": _capi.CARTPOLE_LEARNT_G_W1,
-          "linear_state_1.bias": _capi.CARTPOLE_LEARNT_G_B1,
-          "linear_state_2.weight": _capi.CARTPOLE_LEARNT_G_W2}
-    at.update(("cfg." + k, i) for i, k in enumerate(_capi.CARTPOLE_LEARNT_FIELDS))
-    return [grad[at[name]:at[name] + p.numel()].view(p.shape)
-            if name in at and p.requires_grad else None
-            for name, p in dyn.named_parameters()]
+    return _fit_grad_views(_CARTPOLE_FIT, dyn, grad)
 
 
 # ------------------------------------------------------ pre-bound launches

@@ -965,11 +965,73 @@ class TrainBase:
         self.results_dict["loss_dyn_per_step"].append(loss.detach())
         return loss
 
+    # ---- the fused simulator fit (csrc/residual_fit.h) ----------------------
+    # A trainer whose learnt simulator has one sets `fused_fit = True` and
+    # `_fit_system` (the <sys> of functional.<sys>_learnt_fusable /
+    # _learnt_fit_fwd_bwd / _learnt_fit_grad_views), overrides
+    # `_fit_eval_in_kernel` and makes `_fused_train_dynamics_model` its
+    # train_dynamics_model.
+    fused_fit = False
+    _fit_system = None
+
+    def _fit_functional(self, what):
+        """functional.<sys>_learnt_<what>, looked up when it is called."""
+        from . import functional as F
+        return getattr(F, f"{self._fit_system}_learnt_{what}")
+
+    def _fit_eval_in_kernel(self, eval_dynamics):
+        """Whether the fit kernel steps `eval_dynamics` itself, from its
+        `.params` (the plain analytic dynamics)."""
+        return False
+
+    def _fused_fit_prestep(self, in_kernel):
+        """What the two dynamics' forwards do besides computing (nothing)."""
+
+    def _fusable_fit(self, *tensors):
+        """The fused fit step serves the stock learnt simulator of the system
+        (functional.<sys>_learnt_fusable) with its tensors and the batch on one
+        device."""
+        d = self.train_dynamics
+        if not (self.fused_fit and self._fit_functional("fusable")(d)):
+            return False
+        devs = {p.device for p in d.parameters()} | {t.device for t in tensors}
+        return len(devs) == 1
+
+    def _fused_train_dynamics_model(self, current_state, action_seq):
+        """TrainBase.train_dynamics_model (scripts/train_base.py:160-186) with
+        prediction, target, loss, regulariser and the gradient of every
+        parameter of the learnt simulator in one fused call
+        (functional.<sys>_learnt_fit_fwd_bwd): no parameter is read on the host,
+        so the step - the optimizer's included - can be captured in a graph.
+        An analytic eval dynamics is stepped inside the kernel
+        (`_fit_eval_in_kernel`); any other one is called here and its output
+        handed over as the target.  Not `_fusable_fit`: the base method."""
+        if not self._fusable_fit(current_state, action_seq):
+            return TrainBase.train_dynamics_model(self, current_state, action_seq)
+        d, e = self.train_dynamics, self.eval_dynamics
+        first_action = action_seq[:, 0]
+        # (data parallel: every rank carries 1 / world of the penalty, as the
+        # base method; a fit without regulariser takes no l2_lambda)
+        kw = ({"l2_lambda": self.l2_lambda / parallel.world_size()}
+              if self.l2_lambda > 0 else {})
+        in_kernel = self._fit_eval_in_kernel(e)
+        self._fused_fit_prestep(in_kernel)
+        if in_kernel:
+            kw["eval_params"] = e.params
+        else:
+            with torch.no_grad():
+                kw["target"] = e(current_state, first_action, dt=self.delta_t)
+        res = self._fit_functional("fit_fwd_bwd")(
+            d, current_state, first_action, self.delta_t, **kw)
+        return self._finish_fused_fit(
+            res["loss"], self._fit_functional("fit_grad_views")(d, res["grad"]))
+
     def _finish_fused_fit(self, loss, grad_views):
-        """The tail of a fused simulator-fit step (the train_dynamics_model
-        overrides of TrainDrone / TrainFixedWing): `grad_views` - one view of
-        the kernel's flat gradient per parameter, in train_dynamics.parameters()
-        order - become the .grad fields, then what the base method does after
+        """The tail of a fused simulator-fit step
+        (`_fused_train_dynamics_model`: TrainDrone, TrainFixedWing,
+        TrainCartpole): `grad_views` - one view of the kernel's flat gradient
+        per parameter (None: no gradient), in train_dynamics.parameters() order
+        - become the .grad fields, then what the base method does after
         loss.backward()."""
         for p, g in zip(self.train_dynamics.parameters(), grad_views):
             p.grad = g

@@ -122,51 +122,35 @@ class TrainCartpole(TrainBase):
             states.append(s)
         return cartpole_loss_mpc(torch.stack(states, 1), ref_states, action_seq)
 
-    fused_fit = True      # simulator-fit phase of LearntCartpoleDynamics
+    # simulator-fit phase of the stock LearntCartpoleDynamics (six [1]
+    # parameters, 5 -> 64 -> 4 residual, one CUDA device): TrainBase's fused
+    # step.  On by default: measured against the base method at B = 8, 64 and
+    # 65 536 it is ahead by more than both ways' chunk spreads at every size
+    # (profiles/cartpole_learnt_timing.jsonl, `fit_step`).
+    fused_fit = True
+    _fit_system = "cartpole"
 
-    def _fusable_fit(self, *tensors):
-        """The fused fit step serves the stock LearntCartpoleDynamics (six [1]
-        parameters, 5 -> 64 -> 4 residual) with its tensors and the batch on
-        one CUDA device.  On by default: measured against the base method at
-        B = 8, 64 and 65 536 it is ahead by more than both ways' chunk spreads
-        at every size (profiles/cartpole_learnt_timing.jsonl, `fit_step`)."""
-        d = self.train_dynamics
-        if not (self.fused_fit and F.cartpole_learnt_fusable(d)):
-            return False
-        devs = {p.device for p in d.parameters()} | {t.device for t in tensors}
-        return len(devs) == 1
+    def _fit_eval_in_kernel(self, eval_dynamics):
+        """A plain CartpoleDynamics is stepped inside the kernel."""
+        from .dynamics.cartpole_dynamics import CartpoleDynamics
+        return type(eval_dynamics) is CartpoleDynamics
+
+    def _fused_fit_prestep(self, in_kernel):
+        """Both dynamics' `timestamp` side effects are kept."""
+        self.train_dynamics.timestamp += .05        # (the module's forward)
+        if in_kernel:
+            self.eval_dynamics.timestamp += .05     # (simulate_cartpole)
 
     def train_dynamics_model(self, current_state, action_seq):
         """scripts/train_base.py:160-186 for the cart-pole simulator.  The
         reference's regulariser reads linear_state_2.bias, which this network
-        does not have: l2_lambda > 0 is refused, as it fails there.
-        With `fused_fit` and the stock module: prediction, target, loss and the
-        gradient of every parameter in one fused call
-        (functional.cartpole_learnt_fit_fwd_bwd) - no parameter is read on the
-        host, so the step, the optimizer's included, can be captured in a
-        graph.  A plain CartpoleDynamics as eval dynamics is stepped inside the
-        kernel; any other one is called here and its output handed over as the
-        target.  Both dynamics' `timestamp` side effects are kept."""
+        does not have: l2_lambda > 0 is refused, as it fails there.  Then
+        TrainBase's fused step (functional.cartpole_learnt_fit_fwd_bwd) under
+        the rule of `_fusable_fit`, else the base method."""
         if self.l2_lambda > 0 and self.learnt_simulator():
             raise ValueError("l2_lambda > 0 needs linear_state_2.bias, which "
                              "LearntCartpoleDynamics does not have: set l2_lambda 0")
-        if not self._fusable_fit(current_state, action_seq):
-            return super().train_dynamics_model(current_state, action_seq)
-        from .dynamics.cartpole_dynamics import CartpoleDynamics
-        d, e = self.train_dynamics, self.eval_dynamics
-        first_action = action_seq[:, 0]
-        d.timestamp += .05             # (the module's forward)
-        if type(e) is CartpoleDynamics:
-            e.timestamp += .05         # (simulate_cartpole)
-            res = F.cartpole_learnt_fit_fwd_bwd(
-                d, current_state, first_action, self.delta_t, eval_params=e.params)
-        else:
-            with torch.no_grad():
-                target = e(current_state, first_action, dt=self.delta_t)
-            res = F.cartpole_learnt_fit_fwd_bwd(
-                d, current_state, first_action, self.delta_t, target=target)
-        return self._finish_fused_fit(
-            res["loss"], F.cartpole_learnt_fit_grad_views(d, res["grad"]))
+        return self._fused_train_dynamics_model(current_state, action_seq)
 
     fused_policy = True   # controller step with the stock policy inside the call
 

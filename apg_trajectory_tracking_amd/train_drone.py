@@ -551,48 +551,16 @@ class TrainDrone(TrainBase):
         return self._step(loss)
 
 
-    fused_fit = True      # simulator-fit phase of LearntDynamics
+    # simulator-fit phase of the stock LearntDynamics (4 x 4 action transform,
+    # 16 -> 64 -> 12 residual): TrainBase's fused step
+    fused_fit = True
+    _fit_system = "quad"
+    train_dynamics_model = TrainBase._fused_train_dynamics_model
 
-    def _fusable_fit(self, *tensors):
-        """The fused fit step serves the stock LearntDynamics (4 x 4 action
-        transform, 16 -> 64 -> 12 residual) with its tensors and the batch on
-        one device."""
-        d = self.train_dynamics
-        if not (self.fused_fit and F.quad_learnt_fusable(d)):
-            return False
-        devs = {p.device for p in d.parameters()} | {t.device for t in tensors}
-        return len(devs) == 1
-
-    def train_dynamics_model(self, current_state, action_seq):
-        """TrainBase.train_dynamics_model (scripts/train_base.py:160-186) with
-        prediction, target, loss, regulariser and the gradient of every
-        parameter of the learnt simulator in one fused call
-        (functional.quad_learnt_fit_fwd_bwd): no parameter is read on the host,
-        so the step - the optimizer's included - can be captured in a graph.
-        A plain FlightmareDynamics as eval dynamics is stepped inside the
-        kernel; any other one is called here and its output handed over as the
-        target."""
-        if not self._fusable_fit(current_state, action_seq):
-            return super().train_dynamics_model(current_state, action_seq)
-        from . import parallel
+    def _fit_eval_in_kernel(self, eval_dynamics):
+        """A plain FlightmareDynamics is stepped inside the kernel."""
         from .dynamics.quad_dynamics_flightmare import FlightmareDynamics
-        d, e = self.train_dynamics, self.eval_dynamics
-        first_action = action_seq[:, 0]
-        # (data parallel: every rank carries 1 / world of the penalty, as the
-        # base method)
-        lam = self.l2_lambda / parallel.world_size() if self.l2_lambda > 0 else 0.0
-        if type(e) is FlightmareDynamics:
-            res = F.quad_learnt_fit_fwd_bwd(
-                d, current_state, first_action, self.delta_t,
-                eval_params=e.params, l2_lambda=lam)
-        else:
-            with torch.no_grad():
-                target = e(current_state, first_action, dt=self.delta_t)
-            res = F.quad_learnt_fit_fwd_bwd(
-                d, current_state, first_action, self.delta_t, target=target,
-                l2_lambda=lam)
-        return self._finish_fused_fit(
-            res["loss"], F.quad_learnt_fit_grad_views(d, res["grad"]))
+        return type(eval_dynamics) is FlightmareDynamics
 
 
 def train_control(base_model, config, device=None):
