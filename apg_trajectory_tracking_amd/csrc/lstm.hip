@@ -445,7 +445,8 @@ __global__ __launch_bounds__(kThreads) void lstm_closed_loop_kernel(LoopArgs A) 
     float feat[kNF];
     quad_features(s, t, feat);
     // gates and conv on the 16-bit matrix pipe (policy_mfma16.h), as the
-    // forward training sweep, nothing saved
+    // forward training sweep, nothing saved; operands split without the
+    // assembly statement, as in mlp_closed_loop_kernel (split_pair<false>)
     f32x16 g0, g1;
 #pragma unroll
     for (int i = 0; i < 16; ++i) g0[i] = L.T(hTbg + i * 2), g1[i] = 0.f;
@@ -454,9 +455,9 @@ __global__ __launch_bounds__(kThreads) void lstm_closed_loop_kernel(LoopArgs A) 
 #pragma unroll
       for (int j = 0; j < 8; ++j)
         v[j] = hi ? (8 + j < kNF ? feat[8 + j < kNF ? 8 + j : 0] : 0.f) : feat[j];
-      g0 = mma3(L16.A(hA, nF), split8(v), g0);
+      g0 = mma3(L16.A(hA, nF), split8<false>(v), g0);
       const float vh[8] = {h[0], h[1], h[2], h[3], 0.f, 0.f, 0.f, 0.f};
-      g1 = mma3(L16.A(hA, nH), split8(vh), g1);
+      g1 = mma3(L16.A(hA, nH), split8<false>(vh), g1);
     }
     // lower: position columns relative to the drone; upper: the last three
     // columns are reference velocity minus drone velocity (prepare_data)
@@ -501,8 +502,8 @@ __global__ __launch_bounds__(kThreads) void lstm_closed_loop_kernel(LoopArgs A) 
         float v[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = rv[kb * 8 + j];
-        if (kb & 1) g1 = mma3(L16.A(hA, nG + pp * 3 + kb), split8(v), g1);
-        else g0 = mma3(L16.A(hA, nG + pp * 3 + kb), split8(v), g0);
+        if (kb & 1) g1 = mma3(L16.A(hA, nG + pp * 3 + kb), split8<false>(v), g1);
+        else g0 = mma3(L16.A(hA, nG + pp * 3 + kb), split8<false>(v), g0);
       }
     }
 #pragma unroll

@@ -296,7 +296,8 @@ __global__ __launch_bounds__(kThreads) void mlp_closed_loop_kernel(LoopArgs A) {
     float feat[kNF];
     quad_features(s, t, feat);
     // the policy on the 16-bit matrix pipe (policy_mfma16.h), as the forward
-    // training sweep, nothing saved
+    // training sweep, nothing saved; operands split without the assembly
+    // statement (split_pair<false>: run-to-run differences otherwise)
     f32x16 u[2], a[2];
     init_bias(u, L, hTbs);
     {
@@ -304,7 +305,7 @@ __global__ __launch_bounds__(kThreads) void mlp_closed_loop_kernel(LoopArgs A) {
 #pragma unroll
       for (int j = 0; j < 8; ++j)
         v[j] = hi ? (8 + j < kNF ? feat[8 + j < kNF ? 8 + j : 0] : 0.f) : feat[j];
-      const Op16 x = split8(v);
+      const Op16 x = split8<false>(v);
       u[0] = mma3(L16.A(hA, nS + 0), x, u[0]);
       u[1] = mma3(L16.A(hA, nS + 1), x, u[1]);
     }
@@ -352,17 +353,17 @@ __global__ __launch_bounds__(kThreads) void mlp_closed_loop_kernel(LoopArgs A) {
         float v[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = rv[kb * 8 + j];
-        const Op16 x = split8(v);
+        const Op16 x = split8<false>(v);
         a[0] = mma3(L16.A(hA, n1c + (0 * 4 + pp) * 3 + kb), x, a[0]);
         a[1] = mma3(L16.A(hA, n1c + (1 * 4 + pp) * 3 + kb), x, a[1]);
       }
     }
     const auto th = [](int, int, float v) { return tanh_fast(v); };
-    dense64_16(a, u, L16, hA, n1s, th);
+    dense64_16<false>(a, u, L16, hA, n1s, th);
     init_bias(u, L, hTb2);
-    dense64_16(u, a, L16, hA, n2, th);
+    dense64_16<false>(u, a, L16, hA, n2, th);
     init_bias(a, L, hTb3);
-    dense64_16(a, u, L16, hA, n3, th);
+    dense64_16<false>(a, u, L16, hA, n3, th);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float z0 = 0.f, z1 = 0.f;

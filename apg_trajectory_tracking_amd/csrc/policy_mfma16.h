@@ -37,18 +37,32 @@ __host__ __device__ constexpr int kin(int kb, int j, int hi) {
   return 32 * (kb >> 1) + rrow(8 * (kb & 1) + j) + 4 * hi;
 }
 
-// two fp32 values -> their packed fp16 high terms and packed fp16 low terms
+// two fp32 values -> their packed fp16 high terms and packed fp16 low terms.
+// MIX = false: the remainders in plain C++ (convert back, subtract: two
+// instructions each) - for the closed-loop evaluation kernels, see below.
+template <bool MIX = true>
 __device__ __forceinline__ void split_pair(float a, float b, unsigned &h, unsigned &l) {
   const h16x2 vh = {(_Float16)a, (_Float16)b};  // v_cvt_pk_f16_f32, round to nearest
   h = __builtin_bit_cast(unsigned, vh);
   // the remainders a - a_h, b - b_h (exact) as ONE mixed-precision fma each:
   // v_fma_mix_f32 reads the fp16 term out of the packed register (the compiler
   // does not form it: it converts back and subtracts, two instructions)
+  // The statement is invisible to the compiler's hazard recognizer (cf. relu1,
+  // policy_mfma.h).  In mlp_closed_loop_kernel its results are given the
+  // registers that the matrix instruction issued just before it reads as an
+  // operand, and the flights of waves 4..7 of a workgroup (the second wave of
+  // every SIMD) came out with actions up to 3.3e-6 off, other flights at every
+  // launch (tests/test_gpu_quad_flight.py; DESIGN.md, closed-loop section).
+  // With MIX = false the same kernel is bit-reproducible and exact to 2.5e-7.
   float ra, rb;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]"
-      : "=v"(ra) : "v"(h), "v"(a));
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-      : "=v"(rb) : "v"(h), "v"(b));
+  if (MIX) {
+    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]"
+        : "=v"(ra) : "v"(h), "v"(a));
+    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
+        : "=v"(rb) : "v"(h), "v"(b));
+  } else {
+    ra = a - (float)vh[0], rb = b - (float)vh[1];
+  }
   const h16x2 vl = {(_Float16)ra, (_Float16)rb};
   l = __builtin_bit_cast(unsigned, vl);
 }
@@ -58,12 +72,13 @@ struct Op16 {  // one operand of a k-block: 8 high terms, 8 low terms
 };
 
 // the 8 values v[0..7] of this lane's k-slots as a B operand
+template <bool MIX = true>
 __device__ __forceinline__ Op16 split8(const float (&v)[8]) {
   Op16 o;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     unsigned h, l;
-    split_pair(v[2 * q], v[2 * q + 1], h, l);
+    split_pair<MIX>(v[2 * q], v[2 * q + 1], h, l);
     o.h[q] = h, o.l[q] = l;
   }
   return o;
@@ -150,7 +165,7 @@ __device__ __forceinline__ void dense64T_16(f32x16 (&out)[2], const Op16 (&x)[4]
 // 64-wide layer on accumulator-layout inputs: out[rb] += W[rb] . in, blocks
 // [rb][kb] from block index `n0`; `f` is applied to every input first (tanh of
 // the previous layer, or the identity) and may store it.
-template <typename F>
+template <bool MIX = true, typename F>
 __device__ __forceinline__ void dense64_16(f32x16 (&out)[2], const f32x16 (&in)[2],
                                            const LdsView16 &L, int base, int n0, F f) {
 #pragma unroll
@@ -158,7 +173,7 @@ __device__ __forceinline__ void dense64_16(f32x16 (&out)[2], const f32x16 (&in)[
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = f(kb >> 1, 8 * (kb & 1) + j, in[kb >> 1][8 * (kb & 1) + j]);
-    const Op16 x = split8(v);
+    const Op16 x = split8<MIX>(v);
     out[0] = mma3(L.A(base, n0 + kb), x, out[0]);
     out[1] = mma3(L.A(base, n0 + 4 + kb), x, out[1]);
   }

@@ -470,9 +470,9 @@ def quad_closed_loop(net, dyn, traj, dt, horizon, max_steps, thresh_div,
     state[:, :3] = ref[:, 0, :3]
     cur = 0
     alive = torch.ones(B, dtype=torch.bool)
-    out = dict(drone=torch.zeros(B, T + 1, 12), ref=torch.zeros(B, T, 3),
-               div=torch.zeros(B, T), actions=torch.zeros(B, T, 4),
-               steps=torch.zeros(B, dtype=torch.long))
+    zeros = lambda *shape: torch.zeros(shape, dtype=traj.dtype)
+    out = dict(drone=zeros(B, T + 1, 12), ref=zeros(B, T, 3), div=zeros(B, T),
+               actions=zeros(B, T, 4), steps=torch.zeros(B, dtype=torch.long))
     out["drone"][:, 0] = state
     last = ref[:, -1, :3]
     with torch.no_grad():

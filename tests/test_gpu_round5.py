@@ -301,26 +301,7 @@ def test_split_graph_step_through_a_live_rccl_group_of_one(dev):
 
 
 # ---------------------------------------------------------------- item 5
-def _g17(dev):
-    """(golden G17, shipped controller, LSTM controller + its start state, the
-    package's LearntDynamics carrying the fixture's fitted simulator)."""
-    import ast
-    from apg_trajectory_tracking_amd.checkpoint import build_policy
-    from apg_trajectory_tracking_amd.dynamics.quad_dynamics_trained import LearntDynamics
-    from apg_trajectory_tracking_amd.models.rnn import LSTM_NEW
-    g, g11, ck = (load_golden("closed_loop_learnt.npz"), load_golden("closed_loop.npz"),
-                  load_golden("checkpoints.npz"))
-    net = build_policy("quad", {k[len("quad.w."):]: torch.from_numpy(ck[k])
-                                for k in ck.files if k.startswith("quad.w.")}).to(dev)
-    lstm = LSTM_NEW(15, 10, 9, 4, conv=1)
-    lstm.load_state_dict({k[len("lstm.w."):]: torch.from_numpy(g11[k])
-                          for k in g11.files if k.startswith("lstm.w.")})
-    init = {kv.split("=")[0]: ast.literal_eval(kv.split("=")[1]) for kv in g["init"]}
-    dyn = LearntDynamics(initial_params=init)
-    dyn.load_state_dict({k[len("dyn."):]: torch.from_numpy(g[k]) for k in g.files
-                         if k.startswith("dyn.")})
-    hidden = (torch.from_numpy(g11["lstm.h0"]).to(dev), torch.from_numpy(g11["lstm.c0"]).to(dev))
-    return g, net, lstm.to(dev), hidden, dyn.to(dev)
+from quad_flight_cases import g17 as _g17  # noqa: E402  (the G17 fixture's parts)
 
 
 @pytest.mark.parametrize("case", ["train", "test", "tight", "lstm_train", "lstm_test"])
@@ -374,37 +355,26 @@ def test_closed_loop_through_the_learnt_simulator_matches_reference_evaluator(de
 
 def test_closed_loop_learnt_simulator_large_batch_vs_oracle(dev):
     """The learnt-simulator closed loop over several workgroups with a ragged
-    tail, MLP and LSTM controller, against the batched oracle loop."""
+    tail, MLP and LSTM controller: every flight, step by step, on the branches
+    the kernel took (quad_flight_cases.check: float64 arbitrates, 2e-4 on the
+    divergences, every decision held against float64)."""
+    import quad_flight_cases as Q
     from apg_trajectory_tracking_amd import functional as F, synthetic
-    from oracle import torch_port as tp
-    g, net, lstm, _, dyn = _g17(dev)
-    weights = {k[len("dyn."):]: g[k] for k in g.files if k.startswith("dyn.")}
-    import ast
-    init = {kv.split("=")[0]: ast.literal_eval(kv.split("=")[1]) for kv in g["init"]}
+    _, net, lstm, _, dyn = _g17(dev)
     B, L, steps = 300, 40, 30
-    traj = synthetic.quad_eval_trajectories(B, L, 0.1, seed=9)
-    lifted = traj.clone()
+    lifted = synthetic.quad_eval_trajectories(B, L, 0.1, seed=9)
     lifted[:, :, 2] += 3
     gen = torch.Generator().manual_seed(4)
     h0, c0 = torch.randn(B, 8, generator=gen), torch.randn(B, 8, generator=gen)
-    for ctrl, name in ((net, "mlp"), (lstm, "lstm")):
-        cpu = __import__("copy").deepcopy(ctrl).cpu()
+    case = Q.Case("learnt-large-batch", lifted, steps, 0.4, 1.0, 0, h0, c0)
+    kw = dict(max_steps=steps, thresh_div=0.4, learnt=dyn, want_trajectory=True)
+    for name in ("mlp", "lstm"):
         if name == "lstm":
-            cpu.hidden_state, cpu.cell_state = h0.clone(), c0.clone()
-            out = F.quad_lstm_closed_loop(ctrl, lifted.to(dev), 0.1, dyn.params, h0.to(dev),
-                                          c0.to(dev), max_steps=steps, thresh_div=0.4,
-                                          learnt=dyn)
+            out = F.quad_lstm_closed_loop(lstm, lifted.to(dev), 0.1, dyn.params, h0.to(dev),
+                                          c0.to(dev), **kw)
         else:
-            out = F.quad_mlp_closed_loop(ctrl, lifted.to(dev), 0.1, dyn.params,
-                                         max_steps=steps, thresh_div=0.4, learnt=dyn)
-        ref = tp.quad_closed_loop(cpu, tp.LearntQuadOracle(weights, init), traj, 0.1, 10,
-                                  steps, 0.4, 1.0, 0)
-        same = [i for i in range(B) if int(out["steps"][i]) == int(ref["steps"][i])]
-        assert len(same) > 0.97 * B, name
-        bad = [i for i in same
-               if np.abs(N(out["div"][:int(ref["steps"][i]), i])
-                         - ref["div"][i, :int(ref["steps"][i])].numpy()).max() > 2e-3]
-        assert len(bad) <= 0.03 * B, (name, len(bad))
+            out = F.quad_mlp_closed_loop(net, lifted.to(dev), 0.1, dyn.params, **kw)
+        Q.check(case, name + "_learnt", Q.kernel_log(out), blank=0.0)
 
 
 def test_evaluate_model_flies_the_learnt_simulator_without_a_substitution(dev):
