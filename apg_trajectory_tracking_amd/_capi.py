@@ -339,6 +339,12 @@ SIGNATURES = {
         ctypes.POINTER(ApgQuadLossWeights), ctypes.POINTER(ApgMlpPolicy), _I, _I,
         _P, _P, _P, _P, _P, ctypes.POINTER(ApgMlpPolicyGrads), _P, _P, _P,
         ctypes.POINTER(ApgMlpSgdUpdate), ctypes.POINTER(ApgStepEvents), _P],
+    "apg_quad_learnt_mlp_step_workspace_floats": [],
+    "apg_quad_learnt_mlp_concurrent_train_step": [
+        _P, _P, _I, _F, ctypes.POINTER(ApgQuadParams), ctypes.POINTER(ApgLearntResidual),
+        ctypes.POINTER(ApgQuadLossWeights), ctypes.POINTER(ApgMlpPolicy), _I, _I,
+        _P, _P, _P, _P, _P, ctypes.POINTER(ApgMlpPolicyGrads), _P, _P, _P,
+        ctypes.POINTER(ApgMlpSgdUpdate), _P],
     "apg_quad_mlp_rollout_step_workspace_floats": [],
     "apg_quad_mlp_rollout_step_partials_floats": [_I],
     "apg_quad_mlp_rollout_train_step": [

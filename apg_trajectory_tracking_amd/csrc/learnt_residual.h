@@ -83,4 +83,81 @@ __device__ __forceinline__ void learnt_quad_step(float (&s)[12], const float (&a
   learnt_residual_add(s, x, lr, hi);
 }
 
+// The mirror of learnt_residual_add: gx = W1^T (relu' . W2^T lam) for the
+// cotangent lam of the step's result, in the same half-wave split.  Each half
+// recomputes its 32 hidden pre-activations from x = [state before the step,
+// transformed action], forms gh_m = sum_q W2^T[m][q] lam_q under the relu's
+// mask and accumulates gx_i += W1[m][i] gh_m; the halves exchange the 16 sums
+// (own + other: the same bits in both).  The packed rows serve as they are:
+// a unit's W1 row of 16 is read once for both products.
+__device__ __forceinline__ void learnt_residual_adjoint(float (&gx)[16], const float (&lam)[12],
+                                                        const float (&x)[16], const float *lr,
+                                                        int hi) {
+  typedef float f32x4_lr __attribute__((ext_vector_type(4)));
+#pragma unroll
+  for (int i = 0; i < 16; ++i) gx[i] = 0.f;
+  int u0 = 32 * hi;
+  asm volatile("" : "+v"(u0));
+  const float *w1 = lr + kLrW1 + u0 * 16, *b1 = lr + kLrB1 + u0, *w2 = lr + kLrW2 + u0 * 12;
+#pragma unroll 2
+  for (int m = 0; m < 32; ++m) {
+    float h = b1[m], wr[16];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const f32x4_lr w = *reinterpret_cast<const f32x4_lr *>(w1 + m * 16 + 4 * q);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        wr[4 * q + j] = w[j];
+        h = fmaf(w[j], x[4 * q + j], h);
+      }
+    }
+    float gh = 0.f;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      const f32x4_lr w = *reinterpret_cast<const f32x4_lr *>(w2 + m * 12 + 4 * q);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) gh = fmaf(w[j], lam[4 * q + j], gh);
+    }
+    gh = h > 0.f ? gh : 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) gx[i] = fmaf(wr[i], gh, gx[i]);
+  }
+#pragma unroll
+  for (int i = 0; i < 16; ++i) gx[i] += other_half(gx[i]);
+}
+
+// Adjoint of learnt_quad_step: lam = dL/d(next state) on entry, dL/d(state) on
+// exit; ga += dL/d(action) through linear_at^T; `pre` = the state the step
+// started from, `act` the policy's action (before the transform).  The
+// simulator's own parameters are frozen: nothing is produced for them.
+__device__ __forceinline__ void learnt_quad_step_adjoint(float (&lam)[12], float (&ga)[4],
+                                                         const float (&pre)[12],
+                                                         const float (&act)[4],
+                                                         const QuadConst &c, const float *lr,
+                                                         int hi) {
+  typedef float f32x4_lr __attribute__((ext_vector_type(4)));
+  float x[16], gx[16];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) x[i] = pre[i];
+  f32x4_lr a[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    a[i] = *reinterpret_cast<const f32x4_lr *>(lr + kLrA + 4 * i);
+    x[12 + i] =
+        fmaf(a[i][3], act[3], fmaf(a[i][2], act[2], fmaf(a[i][1], act[1], a[i][0] * act[0])));
+  }
+  learnt_residual_adjoint(gx, lam, x, lr, hi);   // (before lam is overwritten)
+  const Trig t = make_trig(&pre[3]);
+  float gap[4] = {0.f, 0.f, 0.f, 0.f};
+  const float w[3] = {pre[9], pre[10], pre[11]};
+  quad_step_adjoint(lam, gap, x[12], w, c, t);
+#pragma unroll
+  for (int i = 0; i < 12; ++i) lam[i] += gx[i];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) gap[r] += gx[12 + r];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)   // linear_at^T
+    ga[i] += fmaf(a[3][i], gap[3], fmaf(a[2][i], gap[2], fmaf(a[1][i], gap[1], a[0][i] * gap[0])));
+}
+
 }  // namespace apg

@@ -4,6 +4,8 @@
 // bias gradient (mlp_concurrent_bwd_tm_kernel), the second stage (mlp_common.h).
 // Replaces TrainBase.run_epoch's concurrent branch (scripts/train_base.py:198-204)
 // + TrainDrone.train_controller_model (scripts/train_drone.py:175-203).
+// The same step through the learnt simulator (apg_quad_learnt_mlp_concurrent_
+// train_step): mlp_concurrent_learnt_fwd_kernel in place of the forward kernel.
 #include "mlp_concurrent_fwd.h"
 
 namespace apg {
@@ -546,6 +548,108 @@ __global__ __launch_bounds__(kThreads) void mlp_concurrent_bwd_tm_kernel(WgArgs 
   }
 }
 
+// ------------------------------- concurrent mode through the learnt simulator
+// The controller phase of the adapt flow (TrainBase.run_dynamics,
+// scripts/train_base.py:334-375, with the concurrent policy of :198-204): the
+// forward kernel of the concurrent step with LearntDynamics
+// (neural_control/dynamics/quad_dynamics_trained.py:61-69) as the environment,
+//   a' = linear_at a;  s' = quad_step(s, a') + W2 relu(W1 [s; a'] + b1) + b2,
+// frozen: its packed weights (learnt_pack_kernel) sit in LDS behind the policy
+// tables, and nothing is produced for them.  Geometry and policy part are
+// mlp_concurrent_fwd_kernel<false>'s (conc_policy_forward); both half-waves of a
+// trajectory run the rollout, each with 32 of the 64 hidden units
+// (learnt_residual.h).  The residual's adjoint needs the whole pre-state of
+// every step: the ten of them go to LDS as [k][12][256] over the policy tables,
+// which are dead once every wave has its actions - so the reverse sweep holds
+// one state, one cotangent and the actions in registers, and rebuilds the
+// step's trigonometry from the pre-state it reads back.
+constexpr int kPreFloats = kH * 12 * kTrajPerBlock;
+static_assert(kPreFloats <= kCfLds, "the pre-states lie over the dead policy tables");
+static_assert((kCfLds + kLearntFloats) * 4 <= 160 * 1024, "LDS");
+
+__global__ __launch_bounds__(kThreads) void mlp_concurrent_learnt_fwd_kernel(
+    ConcArgs A, const float *learnt) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  // (the policy part's table fill waits for this one as well)
+  fill_lds_issue(lds + kCfLds, learnt, kLearntFloats);
+  ConcLane Z;
+  float act[kH][4];
+  conc_policy_forward<false>(A, lds, Z, act);
+  const int hi = Z.hi;
+  const unsigned pN = Z.pN, vb = Z.vb, vb_lo = Z.vb_lo, vr = Z.vr;
+  const QuadConst c = A.c;
+  const Planes Ps0(A.state0, 12, pN), Prf(A.ref, kH * A.ref_cols, pN);
+  const Planes Pdz(A.d_zout, kNA, pN);
+  const Planes Pst(A.states, A.states ? kH * 12 : 0, pN);
+  const float *lr = lds + kCfLds;
+  float *pre_at = lds + Z.tl;   // + (k * 12 + i) * 256: this trajectory's pre-states
+
+  float s[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) s[i] = Ps0.ld(vb, i * pN);
+  __syncthreads();   // every wave is done with the policy tables
+#pragma unroll
+  for (int k = 0; k < kH; ++k) {
+    if (hi == 0) {   // (both halves hold the same state)
+#pragma unroll
+      for (int i = 0; i < 12; ++i) pre_at[(k * 12 + i) * kTrajPerBlock] = s[i];
+    }
+    const Trig t = make_trig(&s[3]);
+    learnt_quad_step(s, act[k], c, t, lr, hi);
+#pragma unroll
+    for (int i = 0; i < 12; ++i) Pst.st(vb_lo, (k * 12 + i) * pN, s[i]);
+  }
+  // quad_mpc_loss and the adjoint, last step first; s: the state BEHIND step k
+  float loss = 0.f, lam[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) lam[i] = 0.f;
+#pragma unroll
+  for (int k = kH - 1; k >= 0; --k) {
+    float lp = 0.f, lv = 0.f, lw = 0.f, lr_ = 0.f;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const float rp = Prf.ld(vb, (k * A.ref_cols + i) * pN);
+      const float rv = Prf.ld(vb, (k * A.ref_cols + A.vel_col + i) * pN);
+      const float dp = s[i] - rp, dv = s[6 + i] - rv, wn = s[9 + i];
+      lp += dp * dp, lv += dv * dv, lw += wn * wn;
+      lam[i] += 2.f * A.w.pos * dp;
+      lam[6 + i] += 2.f * A.w.vel * dv;
+      lam[9 + i] += 2.f * A.w.av * wn;
+    }
+    const float da0 = act[k][0] - 0.5f;
+    float ga[4];
+    ga[0] = 2.f * A.w.thrust * da0;
+#pragma unroll
+    for (int i = 1; i < 4; ++i) {
+      const float d = act[k][i] - 0.5f;
+      lr_ += d * d;
+      ga[i] = 2.f * A.w.rates * d;
+    }
+    loss += A.w.pos * lp + A.w.vel * lv + A.w.av * lw + A.w.rates * lr_ +
+            A.w.thrust * da0 * da0;
+    // (summed HERE: the loss is read behind the last step only, and without this
+    // the compiler sinks all ten steps' sums there - with their ~90 operands
+    // alive across the sweep, which then spills)
+    asm volatile("" : "+v"(loss));
+#pragma unroll
+    for (int i = 0; i < 12; ++i) s[i] = pre_at[(k * 12 + i) * kTrajPerBlock];
+    learnt_quad_step_adjoint(lam, ga, s, act[k], c, lr, hi);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)  // dL/d(head pre-activation), in place
+      act[k][i] = ga[i] * act[k][i] * (1.f - act[k][i]);
+    // (likewise: one register per action, not its cotangent and the action)
+    asm volatile("" : "+v"(act[k][0]), "+v"(act[k][1]), "+v"(act[k][2]), "+v"(act[k][3]));
+  }
+  // own rows of dL/dz in accumulator layout: rows khead(c, hi)
+#pragma unroll
+  for (int cc = 0; cc < 20; ++cc) {
+    const int row = khead(cc, 0);
+    const float v = hi ? act[(row + 4) >> 2][(row + 4) & 3] : act[row >> 2][row & 3];
+    Pdz.st(vr, row * pN, v);
+  }
+  write_wave_partial(A.loss_partials, Z.st_lo ? loss : 0.f);
+}
+
 }  // namespace
 }  // namespace apg
 
@@ -575,7 +679,7 @@ int concurrent_train_step(
     const ApgMlpPolicy *policy, int B, int H, float *acts, unsigned *relu_mask,
     float *d_zout, float *loss_partials, float *loss, const ApgMlpPolicyGrads *grads,
     float *states, float *workspace, float *partials, const ApgMlpSgdUpdate *update,
-    const ApgStepEvents *events, apg_stream_t stream);
+    const ApgStepEvents *events, apg_stream_t stream, const ApgLearntResidual *learnt = nullptr);
 }  // namespace
 
 int apg_quad_mlp_concurrent_step(
@@ -632,6 +736,34 @@ int apg_quad_mlp_concurrent_train_step_rows(
                                workspace, partials, update, events, stream);
 }
 
+// [the analytic step's workspace | packed LearntDynamics weights]
+int apg_quad_learnt_mlp_step_workspace_floats(void) {
+  static_assert((kCfLds + kWgTabFloats + 4 + kMapInts) % 4 == 0, "16-byte rows for the DMA");
+  return kCfLds + kWgTabFloats + 4 + kMapInts + kLearntFloats;
+}
+
+int apg_quad_learnt_mlp_concurrent_train_step(
+    const float *state0, const float *ref, int ref_cols, float dt,
+    const ApgQuadParams *params, const ApgLearntResidual *learnt,
+    const ApgQuadLossWeights *weights, const ApgMlpPolicy *policy, int B, int H,
+    float *acts, unsigned *relu_mask, float *d_zout, float *loss_partials, float *loss,
+    const ApgMlpPolicyGrads *grads, float *states, float *workspace, float *partials,
+    const ApgMlpSgdUpdate *update, apg_stream_t stream) {
+  if (!learnt) { set_error("learnt is NULL"); return APG_ERR_ARG; }
+  if (!learnt->w1 || !learnt->b1 || !learnt->w2 || !learnt->b2) {
+    set_error("learnt: w1 / b1 / w2 / b2 pointer is NULL");
+    return APG_ERR_ARG;
+  }
+  if (update && update->resident != 0) {
+    set_error("update: the resident tables are not available through the learnt simulator "
+              "(resident must be 0)");
+    return APG_ERR_ARG;
+  }
+  return concurrent_train_step(nullptr, state0, ref, ref_cols, dt, params, weights, policy, B, H,
+                               acts, relu_mask, d_zout, loss_partials, loss, grads, states,
+                               workspace, partials, update, nullptr, stream, learnt);
+}
+
 }  // extern "C"
 
 namespace {
@@ -641,7 +773,7 @@ int concurrent_train_step(
     const ApgMlpPolicy *policy, int B, int H, float *acts, unsigned *relu_mask,
     float *d_zout, float *loss_partials, float *loss, const ApgMlpPolicyGrads *grads,
     float *states, float *workspace, float *partials, const ApgMlpSgdUpdate *update,
-    const ApgStepEvents *events, apg_stream_t stream) {
+    const ApgStepEvents *events, apg_stream_t stream, const ApgLearntResidual *learnt) {
   if (int e = check_mlp(params, policy, B, H)) return e;
   if (update && (!all_set(update->param) || !all_set(update->momentum_buf))) {
     set_error("update: parameter / momentum pointer is NULL");
@@ -696,6 +828,7 @@ int concurrent_train_step(
     if (int e = raise_lds(mlp_concurrent_fwd_kernel<true>, kCfRowsLds)) return e;
     if (int e = raise_lds(mlp_concurrent_bwd_tm_kernel<false>, kLdsAll / 4)) return e;
     if (int e = raise_lds(mlp_concurrent_bwd_tm_kernel<true>, kLdsAll / 4)) return e;
+    if (int e = raise_lds(mlp_concurrent_learnt_fwd_kernel, kCfLds + kLearntFloats)) return e;
     attr.set();
   }
   const size_t plane = (size_t)B;
@@ -774,7 +907,15 @@ int concurrent_train_step(
   if (events && events->inputs_ready &&
       hipStreamWaitEvent(st, (hipEvent_t)events->inputs_ready, 0) != hipSuccess)
     return check_launch("hipStreamWaitEvent(inputs_ready)");
-  if (rows)
+  if (learnt) {
+    // the simulator's weights as they are NOW (device pointers, read when the
+    // launch runs: a replayed graph follows the module's tensors), behind the map
+    float *packed = workspace + kCfLds + kWgTabFloats + 4 + kMapInts;
+    hipLaunchKernelGGL(learnt_pack_kernel, dim3((kLearntFloats + 255) / 256), dim3(256), 0, st,
+                       *learnt, packed);
+    hipLaunchKernelGGL(mlp_concurrent_learnt_fwd_kernel, dim3(blocks), dim3(kThreads),
+                       (kCfLds + kLearntFloats) * sizeof(float), st, A, packed);
+  } else if (rows)
     hipLaunchKernelGGL(mlp_concurrent_fwd_kernel<true>, dim3(blocks), dim3(kThreads),
                        kCfRowsLds * sizeof(float), st, A);
   else

@@ -105,9 +105,22 @@ __device__ __forceinline__ void gather_windows16_issue(float *dst, const int *ro
 #ifndef APG_CF_KNOCKOUT
 #define APG_CF_KNOCKOUT 0
 #endif
+// this lane's place in the launch, as the policy part leaves it to the rollout
+// behind it: half-wave, trajectory of the workgroup, plane offsets
+struct ConcLane {
+  int hi, tl;
+  bool live, st_lo;
+  unsigned pN, vb, vb_lo, vr;
+};
+
+// The policy part of a concurrent forward kernel: operand tables into LDS, the
+// network once per trajectory on the matrix pipe, its activations to the planes
+// the reverse kernel reads, the 40 sigmoid actions in every lane.  Shared by
+// mlp_concurrent_fwd_kernel and mlp_concurrent_learnt_fwd_kernel
+// (mlp_concurrent.hip), which differ in the rollout that follows.
 template <bool ROWS>
-__global__ __launch_bounds__(kThreads) void mlp_concurrent_fwd_kernel(ConcArgs A) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
+__device__ __forceinline__ void conc_policy_forward(const ConcArgs &A, float *lds, ConcLane &Z,
+                                                    float (&act)[kH][4]) {
   if (ROWS) {
     const int t = threadIdx.x, b_ = blockIdx.x * kTrajPerBlock + t;
     // (a dead trajectory reads the batch's last row: finite data, never stored;
@@ -146,12 +159,8 @@ __global__ __launch_bounds__(kThreads) void mlp_concurrent_fwd_kernel(ConcArgs A
   const bool live = b < B;
   const bool st_lo = live && hi == 0;
   const unsigned pN = (unsigned)B * 4u;  // every plane here is [..][B]
-  const QuadConst c = A.c;
   const Planes Pfe(A.feat, kNF, pN), Pin(A.in_ref, kH * kRD, pN);
-  const Planes Ps0(A.state0, 12, pN), Prf(A.ref, kH * A.ref_cols, pN);
   const Planes Px1(A.x1, kN1, pN), Ph(A.h, 3 * kW, pN), Pmk(A.mask, 5, pN);
-  const Planes Pdz(A.d_zout, kNA, pN);
-  const Planes Pst(A.states, A.states ? kH * 12 : 0, pN);
   const unsigned vb = live ? (unsigned)b * 4u : kDead;
   const unsigned vb_lo = st_lo ? vb : kDead;
   const unsigned vr = live ? vb + (hi ? 4u * pN : 0u) : kDead;   // + row 4 hi
@@ -332,7 +341,6 @@ __global__ __launch_bounds__(kThreads) void mlp_concurrent_fwd_kernel(ConcArgs A
     return tv;
   });
   // every lane needs all 40 actions (both halves run the same rollout)
-  float act[kH][4];
 #pragma unroll
   for (int cc = 0; cc < 20; ++cc) {
     const float own = cc < 16 ? u[0][cc] : u[1][cc - 16], oth = other_half(own);
@@ -340,6 +348,23 @@ __global__ __launch_bounds__(kThreads) void mlp_concurrent_fwd_kernel(ConcArgs A
     act[row >> 2][row & 3] = sigmoidf_(hi ? oth : own);
     act[(row + 4) >> 2][(row + 4) & 3] = sigmoidf_(hi ? own : oth);
   }
+  Z.hi = hi, Z.tl = tl, Z.live = live, Z.st_lo = st_lo;
+  Z.pN = pN, Z.vb = vb, Z.vb_lo = vb_lo, Z.vr = vr;
+}
+
+template <bool ROWS>
+__global__ __launch_bounds__(kThreads) void mlp_concurrent_fwd_kernel(ConcArgs A) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  ConcLane Z;
+  float act[kH][4];
+  conc_policy_forward<ROWS>(A, lds, Z, act);
+  const int hi = Z.hi, tl = Z.tl;
+  const bool st_lo = Z.st_lo;
+  const unsigned pN = Z.pN, vb = Z.vb, vb_lo = Z.vb_lo, vr = Z.vr;
+  const QuadConst c = A.c;
+  const Planes Ps0(A.state0, 12, pN), Prf(A.ref, kH * A.ref_cols, pN);
+  const Planes Pdz(A.d_zout, kNA, pN);
+  const Planes Pst(A.states, A.states ? kH * 12 : 0, pN);
 
   // ---- rollout + adjoint in registers (quad_rollout_reg_kernel's structure)
   float s[12];

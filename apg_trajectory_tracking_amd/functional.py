@@ -1888,6 +1888,13 @@ class _QuadMlpRolloutLoss(torch.autograd.Function):
 _MLP_PARAMS = ("states_in.weight", "states_in.bias", "conv_ref.weight",
                "conv_ref.bias", "fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias",
                "fc3.weight", "fc3.bias", "fc_out.weight", "fc_out.bias")
+# ... and their shapes in the concurrent policy Net(15, 10, 9, 40, conv=1)
+_QUAD_POLICY_SHAPES = {
+    "states_in.weight": (64, 15), "states_in.bias": (64,),
+    "conv_ref.weight": (20, 9, 3), "conv_ref.bias": (20,),
+    "fc1.weight": (64, 224), "fc1.bias": (64,), "fc2.weight": (64, 64),
+    "fc2.bias": (64,), "fc3.weight": (64, 64), "fc3.bias": (64,),
+    "fc_out.weight": (40, 64), "fc_out.bias": (40,)}
 
 
 def quad_recurrent_forward_inplace_ref(net, state0, in_ref, dt, params, h0=None, c0=None):
@@ -2641,12 +2648,7 @@ class _QuadConcurrentPolicyLoss(torch.autograd.Function):
             # round 4: the weight gradients are accumulated inside the reverse
             # pass (apg_quad_mlp_concurrent_step) - no cotangent planes, no
             # second pass of products; every gradient is a view of `flat`
-            flat, gr = _flat_grads(dev, {
-                "states_in.weight": (64, 15), "states_in.bias": (64,),
-                "conv_ref.weight": (20, 9, 3), "conv_ref.bias": (20,),
-                "fc1.weight": (64, 224), "fc1.bias": (64,), "fc2.weight": (64, 64),
-                "fc2.bias": (64,), "fc3.weight": (64, 64), "fc3.bias": (64,),
-                "fc_out.weight": (40, 64), "fc_out.bias": (40,)})
+            flat, gr = _flat_grads(dev, _QUAD_POLICY_SHAPES)
             gs = _capi.ApgMlpPolicyGrads(**{
                 k: ptr(gr[n]) for k, n in zip(names, _MLP_PARAMS)})
             d_zout = new(40, B)
@@ -2961,6 +2963,96 @@ def quad_concurrent_policy_grads(net, normed, state0, in_ref, ref, dt, params,
             params, weights or quad_loss_weights(), index)
         flat, gr = ctx.flat_grads
     return loss, gr, flat
+
+
+def quad_learnt_policy_fusable(net, dyn):
+    """Whether quad_learnt_concurrent_policy_grads serves this pair: the stock
+    `Net(15, 10, 9, 40, conv=1)` and a stock LearntDynamics (quad_learnt_fusable),
+    float32, every tensor of both on ONE CUDA device."""
+    from .models.hutter_model import Net
+    if not (isinstance(net, Net) and getattr(net, "conv", False)
+            and quad_learnt_fusable(dyn)):
+        return False
+    try:
+        tensors = _net_params(net, _MLP_PARAMS)
+    except AttributeError:
+        return False
+    dev = dyn.linear_at.device
+    return (dev.type == "cuda"
+            and all(t.dtype == torch.float32 and t.device == dev
+                    and tuple(t.shape) == _QUAD_POLICY_SHAPES[n]
+                    for n, t in zip(_MLP_PARAMS, tensors)))
+
+
+def quad_learnt_concurrent_policy_grads(net, dyn, normed, state0, in_ref, ref, dt,
+                                        weights=None, index=None, update=None,
+                                        out=None):
+    """quad_concurrent_policy_grads THROUGH THE LEARNT SIMULATOR `dyn` (a stock
+    LearntDynamics; the controller phase of the adapt flow): policy once per
+    trajectory, ten steps of `a' = linear_at a; s' = quad_step(s, a') + residual`,
+    quad_mpc_loss, the adjoint, the policy's reverse pass with every weight
+    gradient inside and the second stage - one library call, a linear chain of
+    launches on the current stream (apg_quad_learnt_mlp_concurrent_train_step;
+    capturable).  Returns (loss, {parameter name: gradient}, flat) as
+    quad_concurrent_policy_grads does: contiguous views of one flat buffer in
+    `_MLP_PARAMS` order, its last element a free slot for the loss.  `index`: the
+    four tensors are the whole data set, the batch is rows `index`.  `update` =
+    (lr, momentum, {parameter name: momentum buffer}): the second stage applies
+    momentum SGD to the policy.  The simulator is frozen: its tensors are read
+    on the device when the launches run (a replayed graph follows in-place
+    changes), never written, and get no gradient; its physics is `dyn.params`.
+    `out` (a dict, tests and tools): receives the step's planes - "acts"
+    [521][B], "states" [H][12][B], "d_zout" [40][B]."""
+    if not quad_learnt_policy_fusable(net, dyn):
+        raise ValueError("fused learnt-simulator step needs Net(15, 10, 9, 40, conv=1) and "
+                         "a LearntDynamics with the 4 x 4 action transform and the "
+                         "16 -> 64 -> 12 residual network, float32 on one CUDA device")
+    H = 10
+    names = ("w_s", "b_s", "conv_w", "conv_b", "w_1", "b_1", "w_2", "b_2",
+             "w_3", "b_3", "w_out", "b_out")
+    live = _net_params(net, _MLP_PARAMS)
+    with torch.no_grad():
+        acts, s0, rf = quad_concurrent_prepare(normed, state0, in_ref, ref, index, H=H)
+        B = s0.shape[-1]
+        dev = s0.device
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        pw = [t if t.is_contiguous() else t.contiguous() for t in live]
+        model = _learnt_model(dyn)            # (the module's own tensors, by address)
+        require_device(acts, s0, rf, *pw, dyn.linear_at)
+        pol = _capi.ApgMlpPolicy(**{k: ptr(v) for k, v in zip(names, pw)})
+        flat, gr = _flat_grads(dev, _QUAD_POLICY_SHAPES)
+        gs = _capi.ApgMlpPolicyGrads(**{k: ptr(gr[n]) for k, n in zip(names, _MLP_PARAMS)})
+        relu_mask = torch.empty(5, B, dtype=torch.int32, device=dev)
+        loss_partials = new(max(1, lib().apg_quad_mlp_loss_partials_count(B)))
+        loss, d_zout = new(1), new(40, B)
+        states = new(H, 12, B) if out is not None else None
+        ws = new(lib().apg_quad_learnt_mlp_step_workspace_floats())
+        part = new(max(1, lib().apg_quad_mlp_step_partials_floats(B)))
+        upd = None
+        if update is not None:
+            lr, momentum, bufs = update
+            if B == 0 or any(a is not b for a, b in zip(pw, live)):
+                raise ValueError("in-kernel update needs a non-empty batch and "
+                                 "contiguous float32 parameters")
+            require_device(*bufs.values())
+            upd = ctypes.byref(_capi.ApgMlpSgdUpdate(
+                lr=float(lr), momentum=float(momentum),
+                param=_capi.ApgMlpPolicyGrads(**{k: ptr(v) for k, v in zip(names, pw)}),
+                momentum_buf=_capi.ApgMlpPolicyGrads(**{
+                    k: ptr(bufs[n]) for k, n in zip(names, _MLP_PARAMS)})))
+        weights = weights or quad_loss_weights()
+        check(lib().apg_quad_learnt_mlp_concurrent_train_step(
+            ptr(s0), ptr(rf), rf.shape[1], float(dt), ctypes.byref(dyn.params),
+            ctypes.byref(model), ctypes.byref(weights), ctypes.byref(pol), B, H,
+            ptr(acts), relu_mask.data_ptr(), ptr(d_zout), ptr(loss_partials), ptr(loss),
+            ctypes.byref(gs), ptr(states) if states is not None else None, ptr(ws),
+            ptr(part), upd, stream_of(s0)),
+            "apg_quad_learnt_mlp_concurrent_train_step")
+        if update is not None:
+            note_in_kernel_update(list(live) + list(update[2].values()))
+    if out is not None:
+        out.update(acts=acts, states=states, d_zout=d_zout)
+    return loss.reshape(()), gr, flat
 
 
 # the sweeps address every plane tensor with unsigned 32-bit byte offsets: the

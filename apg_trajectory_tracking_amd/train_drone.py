@@ -301,6 +301,29 @@ class TrainDrone(TrainBase):
                 and n.conv_ref.weight.shape == (20, 9, 3)
                 and n.fc_out.weight.shape == (4, 8))
 
+    # True: the concurrent controller step through a LearntDynamics train
+    # simulator (the adapt flow's controller phase) runs as ONE fused call with
+    # the policy and the learnt simulator inside
+    # (functional.quad_learnt_concurrent_policy_grads).  Off by default: a
+    # trainer nobody configured takes the tape path, as before.
+    fused_learnt_policy = False
+
+    def _fusable_learnt_policy(self):
+        return bool(self.fused_learnt_policy and self.fused_policy
+                    and self.train_mode == "concurrent" and self.horizon == 10
+                    and F.quad_learnt_policy_fusable(self.net, self.train_dynamics))
+
+    def _fused_learnt_policy_step(self, in_state, current_state, in_ref_states,
+                                  ref_states, index=None):
+        """The concurrent step through the learnt simulator, which is read and
+        left alone; one process: the update happens inside the call, more ranks:
+        gradients only, then the all-reduce and optimizer.step()."""
+        update = self._in_kernel_update()
+        loss, grads, flat = F.quad_learnt_concurrent_policy_grads(
+            self.net, self.train_dynamics, in_state, current_state, in_ref_states,
+            ref_states, self.delta_t, index=index, update=update)
+        return self._step_direct(loss, grads, flat, stepped=update is not None)
+
     def train_concurrent_fused(
         self, in_state, current_state, in_ref_states, ref_states, index=None,
         probe=False, prepared=None, slot=0, events=None
@@ -308,8 +331,16 @@ class TrainDrone(TrainBase):
         """scripts/train_base.py:198-204 + scripts/train_drone.py:175-203 with
         the policy inside the kernels (apg_quad_mlp_concurrent_train_step).
         `prepared`: functional.quad_concurrent_prepare's result for this batch
-        (see train_recurrent_model)."""
+        (see train_recurrent_model).  With `fused_learnt_policy` and a stock
+        LearntDynamics as train dynamics a direct call (tensors, optional
+        `index`) runs the step through the learnt simulator
+        (apg_quad_learnt_mlp_concurrent_train_step); `probe` keeps answering
+        False for it - the loops that ask first are not built for it."""
         n = self.net
+        if (not probe and prepared is None and in_state is not None
+                and self._fusable_learnt_policy()):
+            return self._fused_learnt_policy_step(
+                in_state, current_state, in_ref_states, ref_states, index)
         ok = (self.fused_policy and isinstance(n, Net) and n.conv
                 and self.horizon == 10 and self.analytic_train_dynamics()
                 and n.states_in.weight.shape == (64, 15)

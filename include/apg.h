@@ -645,6 +645,46 @@ int apg_quad_mlp_concurrent_train_step_rows(
     const ApgMlpPolicyGrads *grads, float *states, float *workspace, float *partials,
     const ApgMlpSgdUpdate *update, const ApgStepEvents *events, apg_stream_t stream);
 
+/* The concurrent training step THROUGH THE LEARNT SIMULATOR in one call: the
+ * controller phase of the adapt flow (TrainBase.run_dynamics,
+ * scripts/train_base.py:334-375, after train_dynamics() has fitted a
+ * LearntDynamics to the changed plant) for Net(15, 10, 9, 40, conv=1), H = 10:
+ *   actions = sigmoid(policy), once per trajectory;
+ *   10 x (a' = linear_at a; s' = quad_step(s, a') + W2 relu(W1 [s; a'] + b1) + b2);
+ *   quad_mpc_loss with `weights`; the adjoint down to dL/d(head
+ *   pre-activations) - the residual's through W2^T, the relu and W1^T, the
+ *   action's through linear_at^T (csrc/learnt_residual.h);
+ * then the reverse kernel and the second stage of
+ * apg_quad_mlp_concurrent_train_step, unchanged.  One forward kernel
+ * (csrc/mlp_concurrent.hip, mlp_concurrent_learnt_fwd_kernel) does the first
+ * four; the call is a linear chain of launches on `stream` - no events, no side
+ * streams, no host reads - and can be captured into a graph.  Bit-reproducible
+ * run to run (no float atomics).
+ *   learnt: device pointers to the module's LIVE tensors, read when the launches
+ *     run (a replayed graph follows them); linear_at NULL: the identity.  The
+ *     simulator is frozen in this phase: no gradient is produced for its
+ *     parameters, none of its tensors is written.  `params`: the physics of the
+ *     module's construction time (its kinv / inertia copies).
+ *   buffers: as apg_quad_mlp_concurrent_train_step (plane inputs; states
+ *     [H][12][B] or NULL), workspace apg_quad_learnt_mlp_step_workspace_floats()
+ *     floats (policy tables | map | packed simulator weights), partials
+ *     apg_quad_mlp_step_partials_floats(B) floats;
+ *   update: NULL - gradients only; else momentum SGD inside the second stage,
+ *     with update->resident == 0 (the resident-table protocol is not available
+ *     here).
+ * APG_ERR_ARG before any device work (apg_last_error_string): learnt or one of
+ * its w1 / b1 / w2 / b2 NULL, H != 10, ref_cols not 6 or 9, a NULL gradient or
+ * update pointer, resident != 0, an update with B = 0.  B = 0 without update:
+ * zero gradients, zero loss, no launch of the step kernels. */
+int apg_quad_learnt_mlp_step_workspace_floats(void);
+int apg_quad_learnt_mlp_concurrent_train_step(
+    const float *state0, const float *ref, int ref_cols, float dt,
+    const ApgQuadParams *params, const ApgLearntResidual *learnt,
+    const ApgQuadLossWeights *weights, const ApgMlpPolicy *policy, int B, int H,
+    float *acts, unsigned *relu_mask, float *d_zout, float *loss_partials, float *loss,
+    const ApgMlpPolicyGrads *grads, float *states, float *workspace, float *partials,
+    const ApgMlpSgdUpdate *update, apg_stream_t stream);
+
 /* The AUTOREGRESSIVE training step in one call (round 5; configs[2] per rank):
  * TrainDrone.train_recurrent_model's unroll, loss and loss.backward()
  * (scripts/train_drone.py:113-173) for Net(15, 10, 9, 4, conv=1) - the forward
