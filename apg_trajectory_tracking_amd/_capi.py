@@ -216,6 +216,24 @@ class ApgWingLearnt(ctypes.Structure):
         "theta", "inertia", "w1", "b1", "w2", "b2")]
 
 
+class ApgWingPolicyGrads(ctypes.Structure):
+    """Where apg_wing_learnt_mlp_train_step puts each parameter's gradient."""
+    _fields_ = ApgWingPolicy._fields_
+
+
+class ApgWingSgdUpdate(ctypes.Structure):
+    """apg_wing_learnt_mlp_train_step's optimizer part: momentum SGD on the
+    policy's tensors and the optimizer's momentum buffers."""
+    _fields_ = [("lr", ctypes.c_double), ("momentum", ctypes.c_double),
+                ("param", ApgWingPolicyGrads), ("momentum_buf", ApgWingPolicyGrads)]
+
+
+# include/apg.h, APG_WING_POLICY_G_*: where each tensor's gradient starts in the
+# flat gradient of the fixed-wing controller step for H = 10 (ApgWingPolicy's
+# order), and its length
+WING_POLICY_G = (0, 576, 640, 832, 896, 9088, 9152, 13248, 13312, 17408, 17472, 20032)
+WING_POLICY_GRADS = 20072
+
 # include/apg.h, APG_WING_FIT_*: where each tensor's cotangent starts in the flat
 # gradient of apg_wing_learnt_fit_fwd_bwd (theta [41], I [9], dW1 [64][16], db1
 # [64], dW2 [12][64], db2 [12])
@@ -385,6 +403,12 @@ SIGNATURES = {
     "apg_wing_learnt_fit_fwd_bwd": [
         _P, _P, _F, ctypes.POINTER(ApgWingLearnt), _P, ctypes.POINTER(ApgWingParams),
         _F, _I, _P, _P, _P, _P, _P],
+    "apg_wing_learnt_mlp_step_workspace_floats": [_I],
+    "apg_wing_learnt_mlp_train_step": [
+        _P, _P, _P, _P, _F, ctypes.POINTER(ApgWingLearnt),
+        ctypes.POINTER(ApgWingLossWeights), ctypes.POINTER(ApgWingPolicy), _I, _I,
+        _P, _P, _P, _P, ctypes.POINTER(ApgWingPolicyGrads), _P, _P,
+        ctypes.POINTER(ApgWingSgdUpdate), _P],
     "apg_wing_mlp_closed_loop": [
         _P, _I, _P, _F, ctypes.POINTER(ApgWingParams), ctypes.POINTER(ctypes.c_float),
         ctypes.POINTER(ApgLearntResidual),

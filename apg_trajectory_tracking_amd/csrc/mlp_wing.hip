@@ -16,11 +16,16 @@
 // layers are v_mfma_f32_32x32x16_f16 products of fp16-split operands
 // (policy_mfma16.h: fp32 accuracy, cotangents scaled per trajectory).  Weight
 // gradients: cotangent planes x activation planes by apg_planes_gemm_grouped.
+// The same step through the learnt simulator (apg_wing_learnt_mlp_train_step):
+// wing_learnt_policy_fwd_kernel runs policy, rollout, loss and adjoint in one
+// kernel, in front of the unchanged reverse kernel.
 #include "apg_device.h"
 #include "policy_mfma.h"
 #include "policy_mfma16.h"
 #include "wing_math.h"
 #include "learnt_residual.h"
+#include "wing_learnt_math.h"
+#include "wing_rollout_math.h"
 
 namespace apg {
 namespace {
@@ -106,9 +111,22 @@ struct Args {
   int B, NA;   // NA = 4 H head rows in use (40 or 80)
 };
 
-__global__ __launch_bounds__(kThreads) void wing_policy_fwd_kernel(Args A) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  fill_lds(lds, A.tables, kFwd16Lds);
+// this lane's place in the launch, as the policy part leaves it to what follows
+// it in the same kernel: half-wave, plane offsets
+struct WingLane {
+  int hi;
+  bool live;
+  unsigned pN, vb, vr;
+};
+
+// The policy part of a forward kernel, tables already in LDS: the network once
+// per trajectory on the matrix pipe, x1 / h to the planes the reverse kernel
+// reads, the head's pre-activations z in accumulator layout (HB row blocks of
+// 32: 3 for the 80 rows of H = 20, 2 where at most 64 are in use).  Shared by
+// wing_policy_fwd_kernel and wing_learnt_policy_fwd_kernel.
+template <int HB>
+__device__ __forceinline__ void wing_policy_forward(const Args &A, const float *lds,
+                                                    WingLane &Z, f32x16 (&z)[HB]) {
   const int lane = threadIdx.x & 63, hi = lane >> 5;
   const LdsView L(lds, lane);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -117,7 +135,7 @@ __global__ __launch_bounds__(kThreads) void wing_policy_fwd_kernel(Args A) {
   const bool live = b < B;
   const unsigned pN = (unsigned)B * 4u;
   const Planes Pfe(A.feat, kNS, pN), Prf(A.ref_in, kNR, pN);
-  const Planes Pac(A.actions, A.NA, pN), Px1(A.x1, kW0, pN), Ph(A.h, 3 * kW, pN);
+  const Planes Px1(A.x1, kW0, pN), Ph(A.h, 3 * kW, pN);
   const unsigned vb = live ? (unsigned)b * 4u : kDead;
   const unsigned vr = live ? vb + (hi ? 4u * pN : 0u) : kDead;  // + row 4 hi
 
@@ -178,9 +196,8 @@ __global__ __launch_bounds__(kThreads) void wing_policy_fwd_kernel(Args A) {
     a[0] = u[0], a[1] = u[1];
   }
   // head: 80 outputs in three row blocks
-  f32x16 z[3];
 #pragma unroll
-  for (int rb = 0; rb < 3; ++rb)
+  for (int rb = 0; rb < HB; ++rb)
 #pragma unroll
     for (int i = 0; i < 16; ++i) z[rb][i] = L.T(hTo + (rb * 16 + i) * 2);
 #pragma unroll
@@ -194,8 +211,19 @@ __global__ __launch_bounds__(kThreads) void wing_policy_fwd_kernel(Args A) {
     }
     const Op16 xv = split8(v);
 #pragma unroll
-    for (int rb = 0; rb < 3; ++rb) z[rb] = mma3(L16.A(hA, nO + rb * 4 + kb), xv, z[rb]);
+    for (int rb = 0; rb < HB; ++rb) z[rb] = mma3(L16.A(hA, nO + rb * 4 + kb), xv, z[rb]);
   }
+  Z.hi = hi, Z.live = live, Z.pN = pN, Z.vb = vb, Z.vr = vr;
+}
+
+__global__ __launch_bounds__(kThreads) void wing_policy_fwd_kernel(Args A) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  fill_lds(lds, A.tables, kFwd16Lds);
+  WingLane Z;
+  f32x16 z[3];
+  wing_policy_forward<3>(A, lds, Z, z);
+  const unsigned pN = Z.pN, vr = Z.vr;
+  const Planes Pac(A.actions, A.NA, pN);
   // actions = sigmoid(z): accumulator rows ARE the action planes
 #pragma unroll
   for (int rb = 0; rb < 3; ++rb)
@@ -593,6 +621,258 @@ __global__ __launch_bounds__(kThreads) void wing_policy_bwd_kernel(Args A) {
   }
 }
 
+// ------------------------ the controller step through the learnt simulator --
+// The controller phase of the adapt flow (TrainFixedWing.train_controller_model,
+// scripts/train_fixed_wing.py:90-116, behind the concurrent policy of
+// scripts/train_base.py:198-209, with LearntFixedWingDynamics,
+// neural_control/dynamics/fixed_wing_dynamics.py:270-326, as train dynamics) in
+// ONE forward kernel: the policy (wing_policy_forward), H = 10 steps of
+//   s' = simulate_fixed_wing(s, a; live theta, full I) + W2 relu(W1 [s; a] + b1) + b2,
+// fixed_wing_mpc_loss and the reverse sweep down to dL/dactions, which leaves as
+// the planes wing_policy_bwd_kernel starts from.  Geometry of
+// wing_policy_fwd_kernel; both half-waves of a trajectory run the rollout
+// (wing_rollout_math.h), each with 32 of the residual's 64 hidden units
+// (learnt_residual.h).  The simulator is frozen: nothing is produced for it.
+//   LDS     [0, 100 352) the policy tables, dead once every wave has its head;
+//           [0, 122 880) over them the ten pre-step states [k][12][256];
+//           [122 880, 130 560) the packed residual, from the start.
+//   actions the head's accumulators, sigmoid applied, stay in 20 registers per
+//           lane: rows 4 k .. 4 k + 3 of step k = 2 q + h are registers 4 q ..
+//           4 q + 3 of half-wave h; the other half takes them by other_half.
+//           The step loops stay rolled (k is a scalar: the pick is a chain of
+//           selects), so one step's registers serve all ten.
+//   table   the step's constants (wing_learnt_table, built on the device by the
+//           pack launch) are read where they are used through the constant
+//           address space, as wing_learnt_rollout_kernel reads them.
+constexpr int kLpH = 10, kLpNA = 4 * kLpH;
+constexpr int kLpPre = kLpH * 12 * kTrajPerBlock;   // 30 720 floats
+constexpr int kLpLds = kLpPre + kLearntFloats;      // 32 640 floats = 130 560 B
+static_assert(kFwd16Lds <= kLpPre, "the pre-states lie over the dead policy tables");
+static_assert(kLpPre % 4 == 0 && kLpLds * 4 <= 160 * 1024, "LDS");
+
+struct WingLearntPolicyArgs {
+  Args P;                      // feat, ref_in, actions, x1, h, tables, B, NA = 40
+  const float *state0, *ref;   // [12][B], [H][3][B]
+  float *grad_actions;         // [40][B]
+  float *states;               // [H][12][B] or NULL
+  float *loss_partials;        // one per wave = 32 trajectories
+  const float *sim;            // the step table (WingGeneralConst)
+  const float *learnt;         // the packed residual (learnt_pack_kernel)
+  ApgWingLossWeights w;
+  int H;
+};
+
+__global__ __launch_bounds__(kThreads) void wing_learnt_policy_fwd_kernel(
+    WingLearntPolicyArgs A) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  fill_lds_issue(lds + kLpPre, A.learnt, kLearntFloats);
+  fill_lds(lds, A.P.tables, kFwd16Lds);   // (waits for both)
+  WingLane Z;
+  f32x16 z[2];
+  wing_policy_forward<2>(A.P, lds, Z, z);
+  const int hi = Z.hi;
+  const unsigned pN = Z.pN, vb = Z.vb, vr = Z.vr;
+  const unsigned vb_lo = Z.live && hi == 0 ? vb : kDead;
+  const Planes Pac(A.P.actions, kLpNA, pN), Pga(A.grad_actions, kLpNA, pN);
+  const Planes Ps0(A.state0, 12, pN), Prf(A.ref, kLpH * 3, pN);
+  const Planes Pst(A.states, A.states ? kLpH * 12 : 0, pN);
+  // own[4 q + j]: action j of step 2 q + hi (head row 8 q + 4 hi + j)
+  float own[20];
+#pragma unroll
+  for (int cc = 0; cc < 20; ++cc) {
+    own[cc] = sigmoidf_(cc < 16 ? z[0][cc] : z[1][cc - 16]);
+    Pac.st(vr, khead(cc, 0) * pN, own[cc]);
+  }
+  float s[12], lam[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) s[i] = Ps0.ld(vb, i * pN);
+  __syncthreads();   // every wave is done with the policy tables
+  const int tl = (threadIdx.x >> 6) * 32 + (threadIdx.x & 31);
+  float *pre_at = lds + tl;     // + (k * 12 + i) * 256: this trajectory's pre-states
+  const float *lr = lds + kLpPre;
+  WingGeneralConstK *kp = (WingGeneralConstK *)A.sim;
+  // (stops the compiler from hoisting the table's scalar loads out of the step
+  // loops, where they would not fit the SGPR file)
+#define APG_LAUNDER(p) asm volatile("" : "+s"(p))
+  const int H = A.H;
+  auto action = [&](int k, float (&a)[4]) {
+    const int q = k >> 1;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float v = own[16 + j];
+#pragma unroll
+      for (int c = 3; c >= 0; --c) {
+        // (opaque: left to itself the compiler folds the chain into ONE load at a
+        // computed index, which puts `own` into scratch)
+        float cand = own[4 * c + j];
+        asm volatile("" : "+v"(cand));
+        v = q == c ? cand : v;
+      }
+      const float oth = other_half(v);
+      a[j] = (k & 1) == hi ? v : oth;
+    }
+  };
+  auto ref = [&](int k, float (&rp)[3]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) rp[i] = Prf.ld(vb, (unsigned)(k * 3 + i) * pN);
+  };
+  auto ST = [&](int k, int i) -> float & { return pre_at[(k * 12 + i) * kTrajPerBlock]; };
+  const float loss = wing_rollout_forward(
+      H, s, A.w.pos, A.w.action, action, ref, ST,
+      [&](float (&x)[12], const float (&a)[4]) {
+        APG_LAUNDER(kp);
+        float xin[16];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) xin[i] = x[i];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) xin[12 + j] = a[j];
+        wing_step(x, a, *kp);
+        learnt_residual_add(x, xin, lr, hi);
+      },
+      [&](int k, const float (&x)[12]) {
+#pragma unroll
+        for (int i = 0; i < 12; ++i) Pst.st(vb_lo, (unsigned)(k * 12 + i) * pN, x[i]);
+      });
+  wing_rollout_reverse(
+      H, s, lam, A.w.pos, A.w.action, action, ref, ST,
+      [&](float (&l)[12], float (&ga)[4], const float (&pre)[12], const float (&a)[4]) {
+        APG_LAUNDER(kp);
+        float xin[16], gx[16], sd[12];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) xin[i] = pre[i];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) xin[12 + j] = a[j];
+        learnt_residual_adjoint(gx, l, xin, lr, hi);   // (before l is overwritten)
+        WingAux x;
+        wing_rates(pre, a, *kp, x, sd);
+        NoWingParamGrads none;
+        wing_step_adjoint(l, ga, pre, x, sd, *kp, none);
+#pragma unroll
+        for (int i = 0; i < 12; ++i) l[i] += gx[i];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ga[j] += gx[12 + j];
+      },
+      [&](int k, const float (&ga)[4]) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) Pga.st(vb_lo, (unsigned)(k * 4 + j) * pN, ga[j]);
+      });
+#undef APG_LAUNDER
+  write_wave_partial(A.loss_partials, vb_lo != kDead ? loss : 0.f, (A.P.B + 31) / 32);
+}
+
+// the flat gradient of the step (include/apg.h, APG_WING_POLICY_G_*): the twelve
+// tensors in ApgWingPolicy order for H = 10
+__host__ __device__ constexpr int pol_size(int t) {
+  return t == 0 ? kW * kNS : t == 2 ? kW * kNR : t == 4 ? kW * kW0
+         : (t == 6 || t == 8) ? kW * kW : t == 10 ? kLpNA * kW : t == 11 ? kLpNA : kW;
+}
+__host__ __device__ constexpr int pol_at(int t) {
+  int at = 0;
+  for (int i = 0; i < t; ++i) at += pol_size(i);
+  return at;
+}
+static_assert(pol_at(0) == APG_WING_POLICY_G_W_S && pol_at(1) == APG_WING_POLICY_G_B_S &&
+                  pol_at(2) == APG_WING_POLICY_G_W_R && pol_at(3) == APG_WING_POLICY_G_B_R &&
+                  pol_at(4) == APG_WING_POLICY_G_W_1 && pol_at(5) == APG_WING_POLICY_G_B_1 &&
+                  pol_at(6) == APG_WING_POLICY_G_W_2 && pol_at(7) == APG_WING_POLICY_G_B_2 &&
+                  pol_at(8) == APG_WING_POLICY_G_W_3 && pol_at(9) == APG_WING_POLICY_G_B_3 &&
+                  pol_at(10) == APG_WING_POLICY_G_W_OUT &&
+                  pol_at(11) == APG_WING_POLICY_G_B_OUT && pol_at(12) == APG_WING_POLICY_GRADS,
+              "apg.h publishes these offsets");
+
+// The step's workspace: [forward tables | packed residual | step table |
+// reverse tables | column descriptors of the weight products | products' scratch]
+constexpr int wsFwd = 0, wsLr = wsFwd + kFwd16Lds, wsSim = wsLr + kLearntFloats,
+              wsBwd = wsSim + kWingLearntTableFloats, wsDesc = wsBwd + kBwd16Lds,
+              kDescInts = 256, wsGemm = wsDesc + kDescInts;
+constexpr int dJ64 = 0, dJ9 = 192, dJ3 = 219;   // [3][J] each: plane, two strides (0)
+constexpr int kLpGroupWgs = 256;
+static_assert(wsLr % 4 == 0 && wsBwd % 4 == 0, "16-byte rows for the DMA");
+
+// the step table from the module's live tensors (wing_learnt_rollout_pack_kernel's)
+// and the descriptors: column j of a product is plane j behind its first one
+__global__ __launch_bounds__(256) void wing_learnt_policy_pack_kernel(ApgWingLearnt m, float dt,
+                                                                      float *__restrict__ sim,
+                                                                      int *__restrict__ desc) {
+  const int t = threadIdx.x;
+  if (t == 0) {
+    *reinterpret_cast<WingGeneralConst *>(sim) = wing_learnt_table(m.theta, m.inertia, dt);
+    for (int i = (int)(sizeof(WingGeneralConst) / sizeof(float)); i < kWingLearntTableFloats; ++i)
+      sim[i] = 0.f;
+  }
+  if (t < dJ9) desc[t] = t < 64 ? t : 0;
+  else if (t < dJ3) desc[t] = t - dJ9 < 9 ? t - dJ9 : 0;
+  else if (t < kDescInts) desc[t] = t - dJ3 < 3 ? t - dJ3 : 0;
+}
+
+// torch.optim.SGD on the twelve tensors: buf = momentum buf + grad, p -= lr buf,
+// in double, rounded once each (as the quadrotor's second stage, mlp_common.h)
+struct WingSgdArgs {
+  const float *g[12];
+  float *p[12], *m[12];
+  double lr, momentum;
+};
+
+__global__ __launch_bounds__(256) void wing_policy_sgd_kernel(WingSgdArgs A) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= pol_at(12)) return;
+  const float *g = nullptr;
+  float *p = nullptr, *m = nullptr;
+#pragma unroll
+  for (int t = 0; t < 12; ++t)
+    if (idx >= pol_at(t) && idx < pol_at(t + 1)) {
+      g = A.g[t] + (idx - pol_at(t));
+      p = A.p[t] + (idx - pol_at(t));
+      m = A.m[t] + (idx - pol_at(t));
+    }
+  const float buf = (float)(A.momentum * (double)*m + (double)*g);
+  *m = buf;
+  *p = (float)((double)*p - A.lr * (double)buf);
+}
+
+inline void pointers_of(const ApgWingPolicyGrads &g, float *(&out)[12]) {
+  float *v[12] = {g.w_s, g.b_s, g.w_r, g.b_r, g.w_1, g.b_1,
+                  g.w_2, g.b_2, g.w_3, g.b_3, g.w_out, g.b_out};
+  for (int t = 0; t < 12; ++t) out[t] = v[t];
+}
+
+inline bool all_set(const ApgWingPolicyGrads &g) {
+  float *v[12];
+  pointers_of(g, v);
+  for (int t = 0; t < 12; ++t)
+    if (!v[t]) return false;
+  return true;
+}
+
+// the seven weight-gradient products of the step (H = 10: the head is one):
+// cotangent planes x activation planes, as functional.wing_concurrent_policy_grads
+// states them.  acts: feat 0..8 | ref 9..11 | x1 12..139 | h1 140.. | h2 204.. |
+// h3 268..; cot: d_zout 0..39 | d_pre fc1, fc2, fc3 (64 each), first layer (128)
+constexpr int kLpProducts = 7;
+void wing_lp_products(const float *acts, const float *cot, float *const (&g)[12],
+                      const int *desc, long long B, ApgGemmProblem (&q)[kLpProducts]) {
+  // (acts / cot NULL: the shapes only, for the workspace size)
+  const auto set = [&](int p, int cot_plane, int M, int plane, int J, const int *d,
+                       float *C, int ldc, float *bias, bool ones) {
+    q[p].A = cot ? cot + cot_plane * B : nullptr;
+    q[p].B = acts ? acts + plane * B : nullptr;
+    q[p].bdesc = d, q[p].C = C, q[p].bias_out = bias;
+    q[p].N = B, q[p].M = M, q[p].S = 1, q[p].J = J, q[p].sdiv = 1;
+    q[p].with_ones = ones, q[p].b_planes = J, q[p].ldc = ldc;
+  };
+  const int dp = kLpNA;   // d_pre's first plane
+  set(0, 0, kLpNA, 268, kW, desc + dJ64, g[10], kW, g[11], true);
+  set(1, dp + 128, kW, 204, kW, desc + dJ64, g[8], kW, g[9], true);
+  set(2, dp + 64, kW, 140, kW, desc + dJ64, g[6], kW, g[7], true);
+  set(3, dp, kW, 12, kW, desc + dJ64, g[4], kW0, nullptr, false);
+  set(4, dp, kW, 76, kW, desc + dJ64, g[4] ? g[4] + kW : nullptr, kW0, g[5], true);
+  set(5, dp + 192, kW, 0, kNS, desc + dJ9, g[0], kNS, g[1], true);
+  set(6, dp + 256, kW, kNS, kNR, desc + dJ3, g[2], kNR, g[3], true);
+}
+
+// functional._run_products' rule: few columns - all products in one launch pair
+inline bool lp_grouped(long long B) { return kLpProducts * B <= 8 * 8192 && B <= 131072; }
+
 int check_wing_horizon(int H) {
   if (H != 10 && H != 20) {
     set_error("the fused fixed-wing policy is built for horizon 10 or 20 (got %d)", H);
@@ -769,6 +1049,145 @@ int apg_wing_mlp_closed_loop(const float *targets, int n_targets, const float *s
                        kFwd16Lds * sizeof(float), st, A);
   }
   return check_launch("wing_mlp_closed_loop");
+}
+
+int apg_wing_learnt_mlp_step_workspace_floats(int B) {
+  if (B <= 0) return 0;
+  long long scratch = (long long)kLpGroupWgs * 64 * 128;
+  if (!lp_grouped(B)) {
+    float *const none[12] = {};
+    ApgGemmProblem q[kLpProducts];
+    static const int no_desc[kDescInts] = {};
+    wing_lp_products(nullptr, nullptr, none, no_desc, B, q);
+    scratch = apg_planes_gemm_multi_workspace_floats(q, kLpProducts);
+  }
+  return (int)(wsGemm + scratch);
+}
+
+int apg_wing_learnt_mlp_train_step(
+    const float *feat, const float *ref_in, const float *state0, const float *ref,
+    float dt, const ApgWingLearnt *model, const ApgWingLossWeights *weights,
+    const ApgWingPolicy *policy, int B, int H,
+    float *acts, float *cot, float *loss_partials, float *loss,
+    const ApgWingPolicyGrads *grads, float *states, float *workspace,
+    const ApgWingSgdUpdate *update, apg_stream_t stream) {
+  if (!model || !model->theta || !model->inertia || !model->w1 || !model->b1 || !model->w2 ||
+      !model->b2) {
+    set_error("model or one of its pointers is NULL");
+    return APG_ERR_ARG;
+  }
+  if (int e = check_wing_policy(policy, B)) return e;
+  if (H != kLpH) {
+    set_error("the fused learnt-simulator step is built for horizon 10 (got %d)", H);
+    return APG_ERR_ARG;
+  }
+  if ((long long)B * 4 * (332 + 2 * kLpNA) >= (1ll << 32) - 64) {
+    set_error("B too large for 32-bit plane offsets; split the batch");
+    return APG_ERR_ARG;
+  }
+  if (!weights) { set_error("weights is NULL"); return APG_ERR_ARG; }
+  if (!grads || !all_set(*grads)) {
+    set_error("gradient pointer is NULL");
+    return APG_ERR_ARG;
+  }
+  if (update) {
+    if (!all_set(update->param) || !all_set(update->momentum_buf)) {
+      set_error("update: parameter / momentum pointer is NULL");
+      return APG_ERR_ARG;
+    }
+    // (NaN fails both comparisons)
+    if (!(update->lr >= 0.0 && update->lr < HUGE_VAL) ||
+        !(update->momentum >= 0.0 && update->momentum < HUGE_VAL)) {
+      set_error("update: lr and momentum must be finite and >= 0");
+      return APG_ERR_ARG;
+    }
+    // (an update with zero gradients would still move the parameters by the
+    // decaying momentum: not implemented)
+    if (B == 0) {
+      set_error("update with B = 0 is not supported");
+      return APG_ERR_ARG;
+    }
+  }
+  hipStream_t st = (hipStream_t)stream;
+  float *g[12];
+  pointers_of(*grads, g);
+  if (B == 0) {   // no trajectory: zero gradients, zero loss
+    for (int t = 0; t < 12; ++t)
+      if (hipMemsetAsync(g[t], 0, pol_size(t) * sizeof(float), st) != hipSuccess)
+        return check_launch("memset(grads)");
+    if (loss && hipMemsetAsync(loss, 0, sizeof(float), st) != hipSuccess)
+      return check_launch("memset(loss)");
+    return APG_OK;
+  }
+  if (!feat || !ref_in || !state0 || !ref || !acts || !cot || !loss_partials || !workspace) {
+    set_error("NULL buffer");
+    return APG_ERR_ARG;
+  }
+  static PerDeviceOnce attr;
+  if (!attr.test()) {
+    if (int e = raise_lds(wing_learnt_policy_fwd_kernel, kLpLds)) return e;
+    if (int e = raise_lds(wing_policy_bwd_kernel, kBwd16Lds)) return e;
+    attr.set();
+  }
+  const size_t plane = (size_t)B;
+  float *x1 = acts + 12 * plane, *h = acts + 140 * plane;
+  float *actions = acts + 332 * plane, *grad_actions = actions + kLpNA * plane;
+  int *desc = reinterpret_cast<int *>(workspace + wsDesc);
+  // 1. the tables, from the tensors as they are when the launches run
+  PackArgs P;
+  P.pol = *policy, P.head_rows = kLpNA;
+  P.dst = workspace + wsFwd;
+  hipLaunchKernelGGL(wing_pack_fwd16_kernel, dim3((kFwd16Lds + 255) / 256), dim3(256), 0,
+                     st, P);
+  const ApgLearntResidual res = {nullptr, model->w1, model->b1, model->w2, model->b2};
+  hipLaunchKernelGGL(learnt_pack_kernel, dim3((kLearntFloats + 255) / 256), dim3(256), 0, st,
+                     res, workspace + wsLr);
+  hipLaunchKernelGGL(wing_learnt_policy_pack_kernel, dim3(1), dim3(256), 0, st, *model, dt,
+                     workspace + wsSim, desc);
+  P.dst = workspace + wsBwd;
+  hipLaunchKernelGGL(wing_pack_bwd16_kernel, dim3((kBwd16Lds + 255) / 256), dim3(256), 0,
+                     st, P);
+  // 2. policy, rollout, loss, adjoint
+  const dim3 grid((B + kTrajPerBlock - 1) / kTrajPerBlock);
+  WingLearntPolicyArgs F = {};
+  F.P.feat = feat, F.P.ref_in = ref_in, F.P.actions = actions, F.P.x1 = x1, F.P.h = h;
+  F.P.tables = workspace + wsFwd, F.P.B = B, F.P.NA = kLpNA;
+  F.state0 = state0, F.ref = ref, F.grad_actions = grad_actions, F.states = states;
+  F.loss_partials = loss_partials, F.sim = workspace + wsSim, F.learnt = workspace + wsLr;
+  F.w = *weights, F.H = H;
+  hipLaunchKernelGGL(wing_learnt_policy_fwd_kernel, grid, dim3(kThreads),
+                     kLpLds * sizeof(float), st, F);
+  // 3. the policy's reverse pass
+  Args R = {};
+  R.actions = actions, R.grad_actions = grad_actions, R.x1 = x1, R.h = h;
+  R.d_zout = cot, R.d_pre = cot + kLpNA * plane, R.tables = workspace + wsBwd;
+  R.B = B, R.NA = kLpNA;
+  hipLaunchKernelGGL(wing_policy_bwd_kernel, grid, dim3(kThreads), kBwd16Lds * sizeof(float),
+                     st, R);
+  if (int e = check_launch("wing_learnt_mlp_train_step")) return e;
+  // 4. the weight gradients, straight into `grads`
+  ApgGemmProblem q[kLpProducts];
+  wing_lp_products(acts, cot, g, desc, B, q);
+  if (int e = lp_grouped(B)
+                  ? apg_planes_gemm_grouped(q, kLpProducts, workspace + wsGemm, kLpGroupWgs, stream)
+                  : apg_planes_gemm_multi(q, kLpProducts, workspace + wsGemm, stream))
+    return e;
+  // 5. the loss
+  if (loss)
+    if (int e = launch_reduce_partials(loss_partials, (B + 31) / 32, loss, st)) return e;
+  // 6. the optimizer
+  if (update) {
+    WingSgdArgs S;
+    float *p[12], *m[12];
+    pointers_of(update->param, p);
+    pointers_of(update->momentum_buf, m);
+    for (int t = 0; t < 12; ++t) S.g[t] = g[t], S.p[t] = p[t], S.m[t] = m[t];
+    S.lr = update->lr, S.momentum = update->momentum;
+    hipLaunchKernelGGL(wing_policy_sgd_kernel, dim3((pol_at(12) + 255) / 256), dim3(256), 0,
+                       st, S);
+    return check_launch("wing_policy_sgd");
+  }
+  return APG_OK;
 }
 
 

@@ -3224,3 +3224,114 @@ def wing_concurrent_policy_grads(net, normed, in_ref, state0, ref, dt, params,
             dict(A=d_pre[256:320], M=64, S=1, Bp=acts, bdesc=R(9, 12),
                  out=gr["ref_in.weight"], bias_out=gr["ref_in.bias"])])
     return res["loss"].reshape(()), gr, flat
+
+
+# ------------------- fixed wing: the same step through the learnt simulator
+# the policy's tensors for H = 10 (_WING_PARAMS order: the flat gradient's layout,
+# include/apg.h APG_WING_POLICY_G_*)
+_WING_POLICY_SHAPES = {
+    "states_in.weight": (64, 9), "states_in.bias": (64,),
+    "ref_in.weight": (64, 3), "ref_in.bias": (64,),
+    "fc1.weight": (64, 128), "fc1.bias": (64,), "fc2.weight": (64, 64),
+    "fc2.bias": (64,), "fc3.weight": (64, 64), "fc3.bias": (64,),
+    "fc_out.weight": (40, 64), "fc_out.bias": (40,)}
+_WING_POLICY_FIELDS = ("w_s", "b_s", "w_r", "b_r", "w_1", "b_1", "w_2", "b_2", "w_3",
+                       "b_3", "w_out", "b_out")
+
+
+def wing_learnt_policy_fusable(net, dyn):
+    """Whether wing_learnt_concurrent_policy_grads serves this pair: the stock
+    `Net(9, 1, 3, 40, conv=False)` and a stock LearntFixedWingDynamics
+    (wing_learnt_fusable), float32, every tensor of both on ONE CUDA device."""
+    from .models.hutter_model import Net
+    if not (isinstance(net, Net) and not getattr(net, "conv", True)
+            and wing_learnt_fusable(dyn)):
+        return False
+    try:
+        tensors = _net_params(net, _WING_PARAMS)
+    except AttributeError:
+        return False
+    dev = dyn.I.device
+    return (dev.type == "cuda"
+            and all(p.dtype == torch.float32 and p.device == dev for p in dyn.parameters())
+            and all(t.dtype == torch.float32 and t.device == dev
+                    and tuple(t.shape) == _WING_POLICY_SHAPES[n]
+                    for n, t in zip(_WING_PARAMS, tensors)))
+
+
+def wing_learnt_concurrent_policy_grads(net, dyn, normed, in_ref, state0, ref, dt,
+                                        weights=None, index=None, update=None,
+                                        out=None):
+    """wing_concurrent_policy_grads THROUGH THE LEARNT SIMULATOR `dyn` (a stock
+    LearntFixedWingDynamics; the controller phase of the adapt flow), H = 10:
+    policy once per trajectory, ten steps of `s' = simulate_fixed_wing(s, a) +
+    residual(s, a)` on the module's live parameters, fixed_wing_mpc_loss, the
+    adjoint, the policy's reverse pass, its weight gradients and the loss sum -
+    one library call, a linear chain of launches on the current stream
+    (apg_wing_learnt_mlp_train_step; capturable).  normed [B,9], in_ref [B,3],
+    state0 [B,12], ref [B,10,3].  Returns (loss, {parameter name: gradient},
+    flat) as wing_concurrent_policy_grads does: contiguous views of one flat
+    buffer in `_WING_PARAMS` order, its last element a free slot for the loss.
+    `index`: the four tensors are the whole data set, the batch is rows `index`.
+    `update` = (lr, momentum, {parameter name: momentum buffer}): the call applies
+    momentum SGD to the policy.  The simulator is frozen: its tensors are read on
+    the device when the launches run (a replayed graph follows in-place changes),
+    never written, and get no gradient.  `out` (a dict, tests and tools):
+    receives the step's planes - "acts" [412][B] (feat | ref | x1 | h1 h2 h3 |
+    actions | dL/dactions), "cot" [360][B] (d_zout | d_pre), "states" [H][12][B]."""
+    if not wing_learnt_policy_fusable(net, dyn):
+        raise ValueError("fused learnt-simulator step needs Net(9, 1, 3, 40, conv=False) "
+                         "and a LearntFixedWingDynamics with the 16 -> 64 -> 12 residual "
+                         "network, float32 on one CUDA device")
+    H = 10
+    if (normed.shape[1] != 9 or in_ref.reshape(in_ref.shape[0], -1).shape[1] != 3
+            or tuple(ref.shape[1:]) != (H, 3) or state0.shape[1] != 12):
+        raise ValueError("fused learnt-simulator step needs normed [B,9], in_ref [B,3], "
+                         "state0 [B,12] and ref [B,10,3]")
+    _guard_policy_inputs("fused fixed-wing step (learnt simulator)", normed=normed,
+                         in_ref=in_ref)
+    live = _net_params(net, _WING_PARAMS)
+    B = state0.shape[0] if index is None else index.numel()
+    dev = state0.device
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    with torch.no_grad():
+        acts, cot = new(332 + 8 * H, B), new(4 * H + 320, B)
+        _, _, s0, rf = to_soa_multi(
+            [(normed, acts[:9]), (in_ref.reshape(-1, 3), acts[9:12]), (state0, None),
+             (ref, None)], index=index)
+        pw = [t if t.is_contiguous() else t.contiguous() for t in live]
+        sim = _wing_learnt_tensors(dyn)       # (theta: gathered on the device)
+        require_device(acts, s0, rf, *pw, *sim)
+        pol = _capi.ApgWingPolicy(**{k: ptr(v) for k, v in zip(_WING_POLICY_FIELDS, pw)})
+        model = _capi.ApgWingLearnt(*[t.data_ptr() for t in sim])
+        flat, gr = _flat_grads(dev, _WING_POLICY_SHAPES)
+        gs = _capi.ApgWingPolicyGrads(**{
+            k: ptr(gr[n]) for k, n in zip(_WING_POLICY_FIELDS, _WING_PARAMS)})
+        loss_partials, loss = new(max(1, (B + 31) // 32)), new(1)
+        states = new(H, 12, B) if out is not None else None
+        ws = new(max(1, lib().apg_wing_learnt_mlp_step_workspace_floats(B)))
+        upd = None
+        if update is not None:
+            lr, momentum, bufs = update
+            if B == 0 or any(a is not b for a, b in zip(pw, live)):
+                raise ValueError("in-kernel update needs a non-empty batch and "
+                                 "contiguous float32 parameters")
+            require_device(*bufs.values())
+            upd = ctypes.byref(_capi.ApgWingSgdUpdate(
+                lr=float(lr), momentum=float(momentum),
+                param=_capi.ApgWingPolicyGrads(**{
+                    k: ptr(v) for k, v in zip(_WING_POLICY_FIELDS, pw)}),
+                momentum_buf=_capi.ApgWingPolicyGrads(**{
+                    k: ptr(bufs[n]) for k, n in zip(_WING_POLICY_FIELDS, _WING_PARAMS)})))
+        weights = weights or wing_loss_weights()
+        check(lib().apg_wing_learnt_mlp_train_step(
+            ptr(acts), ptr(acts[9:]), ptr(s0), ptr(rf), float(dt), ctypes.byref(model),
+            ctypes.byref(weights), ctypes.byref(pol), B, H, ptr(acts), ptr(cot),
+            ptr(loss_partials), ptr(loss), ctypes.byref(gs),
+            ptr(states) if states is not None else None, ptr(ws), upd, stream_of(s0)),
+            "apg_wing_learnt_mlp_train_step")
+        if update is not None:
+            note_in_kernel_update(list(live) + list(update[2].values()))
+    if out is not None:
+        out.update(acts=acts, cot=cot, states=states)
+    return loss.reshape(()), gr, flat

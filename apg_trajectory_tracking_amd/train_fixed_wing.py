@@ -142,8 +142,15 @@ class TrainFixedWing(TrainBase):
         probe=False
     ):
         """scripts/train_base.py:198-204 + scripts/train_fixed_wing.py:90-116
-        with the policy inside HIP kernels (functional.wing_concurrent_policy_grads)."""
+        with the policy inside HIP kernels (functional.wing_concurrent_policy_grads).
+        With `fused_learnt_policy` and a stock LearntFixedWingDynamics as train
+        dynamics a direct call (tensors, optional `index`) runs the step through
+        the learnt simulator (apg_wing_learnt_mlp_train_step); `probe` keeps
+        answering False for it - the loops that ask first are not built for it."""
         n = self.net
+        if not probe and in_state is not None and self._fusable_learnt_policy():
+            return self._fused_learnt_policy_step(
+                in_state, current_state, in_ref_states, ref_states, index)
         if not (self.fused_policy and isinstance(n, Net) and not n.conv
                 and self.horizon in (10, 20) and self.analytic_train_dynamics()
                 and n.states_in.weight.shape == (64, 9)
@@ -157,6 +164,31 @@ class TrainFixedWing(TrainBase):
             n, in_state, in_ref_states, current_state, ref_states,
             self.delta_t_train, self.train_dynamics.params, index=index)
         return self._step_direct(loss, grads, flat)
+
+    # True: the concurrent controller step through a LearntFixedWingDynamics train
+    # simulator (the adapt flow's controller phase) runs as ONE fused call with
+    # the policy and the learnt simulator inside
+    # (functional.wing_learnt_concurrent_policy_grads).  Off by default: a
+    # trainer nobody configured takes the tape path, as before.
+    fused_learnt_policy = False
+
+    def _fusable_learnt_policy(self):
+        return bool(self.fused_learnt_policy and self.fused_policy
+                    and self.horizon == 10
+                    and F.wing_learnt_policy_fusable(self.net, self.train_dynamics))
+
+    def _fused_learnt_policy_step(self, in_state, current_state, in_ref_states,
+                                  ref_states, index=None):
+        """The concurrent step through the learnt simulator, which is read and
+        left alone; one process: the update happens inside the call, more ranks:
+        gradients only, then the all-reduce and optimizer.step()."""
+        named = dict(self.net.named_parameters())
+        update = self._in_kernel_update(
+            names=F._WING_PARAMS, tensors=[named[n] for n in F._WING_PARAMS])
+        loss, grads, flat = F.wing_learnt_concurrent_policy_grads(
+            self.net, self.train_dynamics, in_state, in_ref_states, current_state,
+            ref_states, self.delta_t_train, index=index, update=update)
+        return self._step_direct(loss, grads, flat, stepped=update is not None)
 
     fused_learnt = True   # controller phase through LearntFixedWingDynamics
 
@@ -236,10 +268,12 @@ def train_control(base_model, config, device=None):
     return trainer
 
 
-def train_dynamics(base_model, config, device=None):
+def train_dynamics(base_model, config, device=None, fused_learnt_policy=False):
     """scripts/train_fixed_wing.py:218-241: fit LearntFixedWingDynamics to the
     (modified) evaluation simulator, then train the controller through the
-    learnt one; thresholds high so that the tracking error is reliable."""
+    learnt one; thresholds high so that the tracking error is reliable.
+    fused_learnt_policy: the trainer's flag of that name - the controller phase
+    as one fused call per batch (H = 10, the stock policy and simulator)."""
     from .dynamics.fixed_wing_dynamics import (
         FixedWingDynamics, LearntFixedWingDynamics)
     modified_params = config["modified_params"]
@@ -251,6 +285,7 @@ def train_dynamics(base_model, config, device=None):
         learnt = learnt.to(torch.device(device or "cuda"))
     trainer = TrainFixedWing(
         learnt, FixedWingDynamics(modified_params=modified_params), config)
+    trainer.fused_learnt_policy = bool(fused_learnt_policy)
     trainer.initialize_model(base_model, modified_params=modified_params,
                              device=device)
     trainer.run_dynamics(config)

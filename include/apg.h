@@ -1084,6 +1084,73 @@ int apg_wing_learnt_fit_fwd_bwd(const float *state, const float *action, float d
     float l2_lambda, int B, float *loss_partials, float *loss, float *grad,
     float *workspace, apg_stream_t stream);
 
+/* The controller step THROUGH THE LEARNT SIMULATOR in one call: the controller
+ * phase of the fixed-wing adapt flow (TrainFixedWing.train_controller_model,
+ * scripts/train_fixed_wing.py:90-116, behind the concurrent policy of
+ * scripts/train_base.py:198-209, with LearntFixedWingDynamics,
+ * neural_control/dynamics/fixed_wing_dynamics.py:270-326, as train dynamics) for
+ * Net(9, 1, 3, 40, conv=False), H = 10:
+ *   actions = sigmoid(policy), once per trajectory;
+ *   10 x s' = simulate_fixed_wing(s, a; live theta, full I) + W2 relu(W1 [s; a] + b1) + b2;
+ *   fixed_wing_mpc_loss with `weights`; the adjoint down to dL/dactions;
+ *   the policy's reverse pass, its weight gradients, the loss sum and - with
+ *   `update` - momentum SGD on the policy (buf = momentum buf + grad,
+ *   p -= lr buf, in double, rounded once each, as ApgMlpSgdUpdate).
+ * One forward kernel does the first four lines (csrc/mlp_wing.hip,
+ * wing_learnt_policy_fwd_kernel); then wing_policy_bwd_kernel, the products of
+ * apg_planes_gemm_grouped / _multi, the loss reduction and the update.  The call
+ * is a linear chain of launches on `stream` - no events, no side streams, no host
+ * reads - and can be captured into a graph.  Bit-reproducible (no float atomics).
+ *   model: device pointers to the module's LIVE tensors, read when the launches
+ *     run (a pack launch builds the step table - the double-precision 3x3 inverse
+ *     among it - and the packed residual into `workspace`): a replayed graph
+ *     follows in-place changes.  The simulator is frozen: nothing is produced for
+ *     its parameters, none of its tensors is written.
+ *   plane inputs: feat [9][B], ref_in [3][B], state0 [12][B], ref [10][3][B].
+ *   acts [332 + 80][B]: feat | ref_in | x1 [128] | h1 h2 h3 [64 each] - the B
+ *     operands of the weight products, so planes 0..11 must HOLD feat / ref_in (the
+ *     caller may pass acts and acts + 9 B as `feat` / `ref_in`) - then actions [40]
+ *     and dL/dactions [40], written here.
+ *   cot [40 + 320][B]: d_zout | d_pre (fc1, fc2, fc3, first layer), written here.
+ *   loss_partials: one float per 32 trajectories, ceil(B / 32); loss [1] or NULL;
+ *   states [10][12][B] or NULL; workspace:
+ *     apg_wing_learnt_mlp_step_workspace_floats(B) floats.
+ *   grads: where each tensor's gradient goes; in one flat buffer, in this order,
+ *     they start at APG_WING_POLICY_G_*.
+ * APG_ERR_ARG before any device work (apg_last_error_string): a NULL model,
+ * policy, weights or gradient pointer or a NULL pointer inside them, H != 10,
+ * B < 0, an update with B = 0, with a NULL pointer, or with a negative or
+ * non-finite lr / momentum.  B = 0 without update: zero gradients, zero loss, no
+ * launch of the step kernels. */
+typedef struct ApgWingPolicyGrads {   /* shapes of ApgWingPolicy's tensors, H = 10 */
+  float *w_s, *b_s, *w_r, *b_r, *w_1, *b_1, *w_2, *b_2, *w_3, *b_3, *w_out, *b_out;
+} ApgWingPolicyGrads;
+typedef struct ApgWingSgdUpdate {
+  double lr, momentum;
+  ApgWingPolicyGrads param, momentum_buf;
+} ApgWingSgdUpdate;
+#define APG_WING_POLICY_G_W_S 0
+#define APG_WING_POLICY_G_B_S 576
+#define APG_WING_POLICY_G_W_R 640
+#define APG_WING_POLICY_G_B_R 832
+#define APG_WING_POLICY_G_W_1 896
+#define APG_WING_POLICY_G_B_1 9088
+#define APG_WING_POLICY_G_W_2 9152
+#define APG_WING_POLICY_G_B_2 13248
+#define APG_WING_POLICY_G_W_3 13312
+#define APG_WING_POLICY_G_B_3 17408
+#define APG_WING_POLICY_G_W_OUT 17472
+#define APG_WING_POLICY_G_B_OUT 20032
+#define APG_WING_POLICY_GRADS 20072
+int apg_wing_learnt_mlp_step_workspace_floats(int B);
+int apg_wing_learnt_mlp_train_step(
+    const float *feat, const float *ref_in, const float *state0, const float *ref,
+    float dt, const ApgWingLearnt *model, const ApgWingLossWeights *weights,
+    const ApgWingPolicy *policy, int B, int H,
+    float *acts, float *cot, float *loss_partials, float *loss,
+    const ApgWingPolicyGrads *grads, float *states, float *workspace,
+    const ApgWingSgdUpdate *update, apg_stream_t stream);
+
 /* Fused rollout of TrainFixedWing.train_controller_model
  * (scripts/train_fixed_wing.py:90-110) with fixed_wing_mpc_loss.
  *   ref [B,H,3] linear reference (WingDataset._compute_target_pos,
