@@ -402,17 +402,18 @@ __global__ __launch_bounds__(kThreads) void wing_closed_loop_kernel(WingLoopArgs
       act[j] = sigmoidf_(hi ? oth : z[j]);
     }
 
-    // SimpleWingEnv.step
+    // SimpleWingEnv.step (sin / cos of the attitude in software: relative accuracy
+    // at small angles, wing_math.h sincos_att)
     if (LEARNT) {
       float x[16];
 #pragma unroll
       for (int i = 0; i < 12; ++i) x[i] = s[i];
 #pragma unroll
       for (int j = 0; j < 4; ++j) x[12 + j] = act[j];
-      wing_step(s, act, A.k);
+      wing_step<true>(s, act, A.k);
       learnt_residual_add(s, x, lds + kFwd16Lds, hi);
     } else {
-      wing_step(s, act, static_cast<const WingConst &>(A.k));
+      wing_step<true>(s, act, static_cast<const WingConst &>(A.k));
     }
 #pragma unroll
     for (int i = 0; i < 12; ++i) obs[i] = s[i];

@@ -228,18 +228,29 @@ __host__ __device__ __forceinline__ void sincos_small(T x, T *sn, T *cs) {
 }
 
 // attitude angles: the hardware pair on the device (apg_device.h), the
-// branch-free software pair on the host (tests/host_math)
+// branch-free software pair on the host (tests/host_math).
+// SW = true: the software pair on the device as well - for the closed-loop
+// evaluation.  The hardware pair is exact to 1.5e-7 ABSOLUTELY, the software
+// pair to 1.6 ulp: at a heading of a few hundredths of a radian that is 3e-6
+// against 1e-7 of sin(psi), and through pos_dot = R^T vel at 11.5 m/s the lateral
+// position of one step came out 3 x as far from float64 as float32 arithmetic
+// puts it (rms 4.6e-8 m against 1.4e-8 m).  A rollout of ten steps does not
+// notice; a flight that steers by the direction to a target half a metre away
+// does (closed-loop section).
+template <bool SW = false>
 __host__ __device__ __forceinline__ void sincos_att(float x, float *sn, float *cs) {
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(APG_SW_TRIG)
-  sincos_hw(x, sn, cs);
+  if (SW) sincos_fast(x, sn, cs);
+  else sincos_hw(x, sn, cs);
 #else
   sincos_fast(x, sn, cs);
 #endif
 }
+template <bool SW = false>
 __host__ __device__ __forceinline__ void sincos_att(fx2 x, fx2 *sn, fx2 *cs) {
   float s0, c0, s1, c1;
-  sincos_att(x.x, &s0, &c0);
-  sincos_att(x.y, &s1, &c1);
+  sincos_att<SW>(x.x, &s0, &c0);
+  sincos_att<SW>(x.y, &s1, &c1);
   *sn = (fx2){s0, s1}, *cs = (fx2){c0, c1};
 }
 
@@ -262,8 +273,8 @@ typedef WingAuxT<float> WingAux;
 
 // Evaluates state_dot (12) and fills aux.
 // (KT = const WingConst, possibly qualified with the constant address space,
-// or WingDefaultK)
-template <typename T, typename KT>
+// or WingDefaultK; SW_TRIG: see sincos_att)
+template <bool SW_TRIG = false, typename T, typename KT>
 __host__ __device__ __forceinline__ void wing_rates(const T (&s)[12], const T (&a)[4],
                                            KT &k, WingAuxT<T> &x, T (&sd)[12]) {
   const T u = s[3], v = s[4], w = s[5];
@@ -300,9 +311,9 @@ __host__ __device__ __forceinline__ void wing_rates(const T (&s)[12], const T (&
   // :185-204 body forces
   sincos_small(x.alpha, &x.sa, &x.ca);
   sincos_small(x.beta, &x.sb, &x.cb);
-  sincos_att(s[6], &x.sph, &x.cph);
-  sincos_att(s[7], &x.sth, &x.cth);
-  sincos_att(s[8], &x.sps, &x.cps);
+  sincos_att<SW_TRIG>(s[6], &x.sph, &x.cph);
+  sincos_att<SW_TRIG>(s[7], &x.sth, &x.cth);
+  sincos_att<SW_TRIG>(s[8], &x.sps, &x.cps);
   x.icth = rcp_nr(x.cth);
   const T f0 = -x.ca * x.cb * x.D - x.ca * x.sb * x.Y + x.sa * x.L -
                k.g_m * x.sth + x.Tt * k.cos_eps;
@@ -351,11 +362,11 @@ __host__ __device__ __forceinline__ void wing_rates(const T (&s)[12], const T (&
   }
 }
 
-template <typename T, typename KT>
+template <bool SW_TRIG = false, typename T, typename KT>
 __host__ __device__ __forceinline__ void wing_step(T (&s)[12], const T (&a)[4], KT &k) {
   WingAuxT<T> x;
   T sd[12];
-  wing_rates(s, a, k, x, sd);
+  wing_rates<SW_TRIG>(s, a, k, x, sd);
 #pragma unroll
   for (int i = 0; i < 12; ++i) s[i] = s[i] + k.dt * sd[i];
 }

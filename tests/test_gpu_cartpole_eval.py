@@ -209,3 +209,154 @@ def test_resample_data_vs_cpu_loop(dev, num, thresh):
     data.resample_data(num, thresh)
     assert data.states is rows and data.num_sampled_states == num
     assert torch.equal(data.states, data.labels)
+
+
+# ------------------------------------------------ what needs no tolerance
+# cart_closed_loop_kernel<false|true> (apg_cartpole_mlp_closed_loop,
+# apg_cartpole_learnt_mlp_closed_loop) in both modes: the same bits from launch
+# to launch, for an episode whatever batch it runs in, nothing written outside
+# the outputs or after an episode's end, optional outputs that change nothing,
+# and steps / upright / written rows that agree with each other.  (A per-episode
+# float64 comparison is another matter: theta goes through atan2, a rounding
+# at +-pi moves a value by 2 pi.)
+BIT_T, BALANCE_THRESH = 40, 0.07
+BIT_OUTPUTS = ("states", "actions", "steps", "upright", "vel_sum", "vel_sq")
+BIT_CASES = [(env, mode, B) for env in ("analytic", "learnt") for mode in ("balance", "swingup")
+             for B in (33, 129, 300)]
+
+
+def _bit_start(mode, B):
+    """Balance: near upright with the pole moving at up to 1.2 rad/s, so that with
+    thresh_div = 0.07 the episodes end at different steps (about a fifth after
+    one step, as many over the eight after it, the rest never); swing-up:
+    hanging."""
+    gen = torch.Generator().manual_seed(17 + B)
+    u = lambda: 2 * torch.rand(B, generator=gen) - 1
+    s0 = torch.stack((0.5 * u(), 1.0 * u(), 0.06 * u(), 1.2 * u()), 1)
+    if mode == "swingup":
+        s0[:, 2] = torch.where(u() > 0, 1.0, -1.0) * (2.8 + 0.3 * torch.rand(B, generator=gen))
+    return s0
+
+
+def _bit_fixtures(env, dev):
+    from apg_trajectory_tracking_amd.dynamics.cartpole_dynamics import CartpoleDynamics
+    from test_cartpole_learnt_cpu import fitted, g20
+    net = golden_net(load_golden("cartpole_closed_loop.npz"), "shipped").to(dev)
+    return net, CartpoleDynamics().params, (fitted(g20()).to(dev) if env == "learnt" else None)
+
+
+def _bit_run(env, mode, s0, dev):
+    from apg_trajectory_tracking_amd import functional as F
+    net, params, learnt = _bit_fixtures(env, dev)
+    return F.cartpole_mlp_closed_loop(net, s0.to(dev), DT, params, max_steps=BIT_T, mode=mode,
+                                      thresh_div=BALANCE_THRESH, burn_in=10,
+                                      want_trajectory=True, learnt=learnt)
+
+
+def _differing(a, b):
+    if a.shape != b.shape:
+        return -1
+    as_int = {torch.float32: torch.int32, torch.float64: torch.int64}.get(a.dtype)
+    if as_int is not None:
+        a, b = a.contiguous().view(as_int), b.contiguous().view(as_int)
+    return int((a != b).sum())
+
+
+@pytest.mark.parametrize("env,mode,B", BIT_CASES)
+def test_closed_loop_bits_across_launches_and_batches(dev, env, mode, B):
+    """Three launches give the same bits; a permuted batch gives every episode
+    the same bits; in balance mode steps, upright and the rows written agree."""
+    s0 = _bit_start(mode, B)
+    first = _bit_run(env, mode, s0, dev)
+    for again in range(2):
+        out = _bit_run(env, mode, s0, dev)
+        for k in BIT_OUTPUTS:
+            assert _differing(out[k], first[k]) == 0, (k, again)
+    order = torch.randperm(B, generator=torch.Generator().manual_seed(3))
+    moved, o = _bit_run(env, mode, s0[order], dev), order.to(dev)
+    for k in BIT_OUTPUTS:
+        assert _differing(moved[k], first[k][..., o]) == 0, k
+    steps, upright = first["steps"].cpu().numpy(), first["upright"].cpu().numpy()
+    if mode == "swingup":
+        assert (steps == BIT_T).all()
+        return
+    assert len(set(steps.tolist())) > 3 and (steps == BIT_T).any() and (steps < BIT_T).any()
+    states = first["states"].cpu().numpy()                      # [T,4,B]
+    last = states[steps - 1, 2, np.arange(B)]                   # theta of the last written row
+    outside = ~((-np.float32(BALANCE_THRESH) < last) & (last < np.float32(BALANCE_THRESH)))
+    assert ((upright == 0) == outside).all()
+    assert (upright[steps < BIT_T] == 0).all()
+
+
+CART_GUARD, CART_EXTRA = 2, 2
+
+
+def _cart_abi(env, mode, s0, dev, skip=()):
+    """The C entry point on NaN-filled states / actions with guard planes around
+    them and rows beyond T; `skip`: handed over as NULL."""
+    import ctypes
+    from apg_trajectory_tracking_amd import _capi, functional as F
+    net, params, learnt = _bit_fixtures(env, dev)
+    B, T = s0.shape[0], BIT_T
+    pw = []
+    for l in (net.fc0, net.fc1, net.fc2, net.fc3, net.fc_out):
+        pw += [l.weight.detach().float().contiguous(), l.bias.detach().float().contiguous()]
+    pol = _capi.ApgCartpolePolicy(*[t.data_ptr() for t in pw])
+    soa = s0.float().t().contiguous().to(dev)
+    cols = dict(states=4, actions=1)
+    full = {k: torch.full((CART_GUARD + (T + CART_EXTRA) * c + CART_GUARD, B), float("nan"),
+                          device=dev) for k, c in cols.items() if k not in skip}
+    ints = {k: torch.full((CART_GUARD + 1 + CART_GUARD, B), -7, dtype=torch.int32, device=dev)
+            for k in ("steps", "upright")}
+    sums = {k: torch.full((CART_GUARD + 1 + CART_GUARD, B), float("nan"), dtype=torch.float64,
+                          device=dev) for k in ("vel_sum", "vel_sq")}
+    at = lambda k: full[k][CART_GUARD:].data_ptr() if k in full else None
+    lib = _capi.lib()
+    ws = torch.empty(lib.apg_cartpole_policy_workspace_floats(), device=dev)
+    if learnt is None:
+        name, model = "apg_cartpole_mlp_closed_loop", params
+    else:
+        name = "apg_cartpole_learnt_mlp_closed_loop"
+        model = F._cartpole_learnt_model(F._cartpole_learnt_tensors(learnt))
+    _capi.check(getattr(lib, name)(
+        soa.data_ptr(), DT, ctypes.byref(model), ctypes.byref(pol), B, T,
+        F.CARTPOLE_MODES[mode], BALANCE_THRESH, 10, ints["steps"][CART_GUARD:].data_ptr(),
+        ints["upright"][CART_GUARD:].data_ptr(), sums["vel_sum"][CART_GUARD:].data_ptr(),
+        sums["vel_sq"][CART_GUARD:].data_ptr(), at("states"), at("actions"), ws.data_ptr(),
+        _capi.stream_of(soa)), name)
+    torch.cuda.synchronize(dev)
+    for k, buf in full.items():
+        used = T * cols[k]
+        assert torch.isnan(buf[:CART_GUARD]).all() and \
+            torch.isnan(buf[CART_GUARD + used:]).all(), (k, "wrote outside its view")
+    for k, buf in ints.items():
+        assert (buf[:CART_GUARD] == -7).all() and (buf[CART_GUARD + 1:] == -7).all(), k
+    for k, buf in sums.items():
+        assert torch.isnan(buf[:CART_GUARD]).all() and torch.isnan(buf[CART_GUARD + 1:]).all(), k
+    return {**full, **ints, **sums}
+
+
+@pytest.mark.parametrize("env,mode,B", BIT_CASES)
+def test_closed_loop_c_abi_guarded_buffers_and_optional_outputs(dev, env, mode, B):
+    """Nothing is written outside the views or after an episode's end (rows k <
+    steps are written, the rest keep their NaN); states and / or actions NULL
+    change no other bit; the wrapper's call gives the same bits."""
+    s0 = _bit_start(mode, B)
+    whole = _cart_abi(env, mode, s0, dev)
+    steps = whole["steps"][CART_GUARD]
+    assert (whole["upright"][CART_GUARD] >= 0).all() and (steps >= 1).all()
+    written = torch.arange(BIT_T, device=dev)[:, None] < steps[None, :]          # [T,B]
+    states = whole["states"][CART_GUARD:CART_GUARD + 4 * BIT_T].view(BIT_T, 4, B)
+    actions = whole["actions"][CART_GUARD:CART_GUARD + BIT_T]
+    assert (torch.isnan(states) == ~written[:, None, :]).all()
+    assert (torch.isnan(actions) == ~written).all()
+    out = _bit_run(env, mode, s0, dev)
+    assert _differing(torch.where(written[:, None, :], states, 0.0), out["states"]) == 0
+    assert _differing(torch.where(written, actions, 0.0), out["actions"]) == 0
+    for k in ("steps", "upright", "vel_sum", "vel_sq"):
+        assert _differing(whole[k][CART_GUARD], out[k]) == 0, k
+    for skip in (("states",), ("actions",), ("states", "actions")):
+        part = _cart_abi(env, mode, s0, dev, skip=skip)
+        assert set(part) == set(whole) - set(skip)
+        for k, buf in part.items():
+            assert _differing(buf, whole[k]) == 0, (skip, k)
