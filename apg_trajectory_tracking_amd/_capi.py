@@ -484,6 +484,16 @@ SIGNATURES = {
         ctypes.POINTER(ApgQuadLossWeights), ctypes.POINTER(ApgQuadMpcOptions), _I, _I,
         _P, _P, _P],
     "apg_quad_mpc_workspace_floats": [],
+    "apg_quad_learnt_mpc_workspace_floats": [],
+    "apg_quad_learnt_mpc_solve": [
+        _P, _P, _I, _F, ctypes.POINTER(ApgQuadParams), ctypes.POINTER(ApgLearntResidual),
+        ctypes.POINTER(ApgQuadLossWeights), ctypes.POINTER(ApgQuadMpcOptions), _I, _I,
+        _P, _P, _P, _P, _P],
+    "apg_quad_learnt_mpc_closed_loop": [
+        ctypes.POINTER(ApgQuadFlight), _F, ctypes.POINTER(ApgQuadParams),
+        ctypes.POINTER(ApgLearntResidual), ctypes.POINTER(ApgQuadParams),
+        ctypes.POINTER(ApgLearntResidual), ctypes.POINTER(ApgQuadLossWeights),
+        ctypes.POINTER(ApgQuadMpcOptions), _I, _I, _P, _P, _P],
     "apg_cartpole_mpc_solve": [
         _P, _P, _F, ctypes.POINTER(ApgCartpoleParams),
         ctypes.POINTER(ApgCartpoleMpcOptions), _I, _I, _P, _P, _P, _P],

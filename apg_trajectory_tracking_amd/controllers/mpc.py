@@ -21,6 +21,11 @@ Two deliberate differences:
     trajectory of a batch does the same work and the result is a deterministic
     function of the inputs.
 
+`MPC(learnt_model=module)` plans through a LearntDynamics module instead - the
+role of the reference's LearntDynamicsMPC (neural_control/dynamics/
+learnt_dynamics.py:5-55): MPC with the ADAPTED model; `params` are then the
+module's, `modified_params` cannot be given together with it.
+
 `QuadEvaluator(MPC(...), environment)` flies whole batches of reference
 trajectories with the solver inside the closed-loop kernel
 (functional.quad_mpc_closed_loop): plant = the evaluator's environment, model =
@@ -62,16 +67,27 @@ class MPC:
 
     def __init__(self, horizon=10, dt=0.1, dynamics="flightmare", modified_params={},
                  iters=10, beta=None, alpha_thrust=None, alpha_rate=None, alpha=None,
-                 device=None, **kwargs):
+                 device=None, learnt_model=None, **kwargs):
         if dynamics not in DYNAMICS:
             raise NotImplementedError(
                 f"MPC dynamics {dynamics!r}: implemented here: {', '.join(DYNAMICS)} "
                 "(the quadrotor and the cart-pole; no fixed-wing MPC)")
         if horizon not in (5, 10):
             raise ValueError("the batched MPC is built for horizon 5 or 10")
+        if learnt_model is not None:
+            if dynamics != "flightmare":
+                raise NotImplementedError(
+                    "learnt_model: the solver plans through a learnt simulator for "
+                    "dynamics='flightmare' only")
+            if modified_params:
+                raise ValueError(
+                    "learnt_model brings its own parameters (the module's): "
+                    "modified_params cannot be given together with it")
         self.horizon = horizon
         self.dt = dt
         self.dynamics_model = dynamics
+        # a LearntDynamics module: the solver's model is that module
+        self.learnt_model = learnt_model
         if dynamics == "cartpole":
             self.model = CartpoleDynamics(modified_params)
             self.options = dict(iters=iters, beta=beta, alpha=alpha)
@@ -79,7 +95,7 @@ class MPC:
             self.model = FlightmareDynamics(modified_params=modified_params)
             self.options = dict(iters=iters, beta=beta, alpha_thrust=alpha_thrust,
                                 alpha_rate=alpha_rate)
-        self.params = self.model.params
+        self.params = self.model.params if learnt_model is None else learnt_model.params
         self.device = device
         # [B,H,4] ([B,H,1] cart-pole): the previous solution, not yet shifted
         self.warm_start = None
@@ -137,8 +153,10 @@ class MPC:
             s, r = s[None], r[None]
         if r.shape[1:] != (self.horizon, 9) or s.shape != (r.shape[0], 12):
             raise ValueError(f"state [B,12] and reference rows [B,{self.horizon},9] expected")
+        planner = {} if self.learnt_model is None else dict(learnt=self.learnt_model)
         res = F.quad_mpc_solve(s, r, self.dt, self.params,
-                               u0=self._shifted_warm_start(s.shape[0]), **self.options)
+                               u0=self._shifted_warm_start(s.shape[0]), **self.options,
+                               **planner)
         self.warm_start, self.last_cost = res["u"], res["cost"]
         action = res["u"][:, 0]
         return action.cpu().numpy() if numpy_in else action

@@ -28,6 +28,7 @@
 #include "cartpole_train_math.h"
 #include "launch_chain.h"
 #include "quad_fit_math.h"
+#include "quad_learnt_mpc_math.h"
 #include "quad_math.h"
 #include "quad_mpc_math.h"
 #include "wing_learnt_math.h"
@@ -975,8 +976,8 @@ int check_mpc(const ApgQuadParams *model, const ApgQuadLossWeights *weights,
   return APG_OK;
 }
 
-template <int H>
-void mpc_solve_batch(const float *state0, const float *ref, int ref_cols, const QuadConst &c,
+template <int H, class Model>
+void mpc_solve_batch(const float *state0, const float *ref, int ref_cols, const Model &c,
                      const ApgQuadLossWeights &w, const ApgQuadMpcOptions &o, int B, float *u,
                      float *cost_out, float *cost_trace) {
   const size_t Bs = (size_t)B;
@@ -1014,9 +1015,11 @@ int apg_quad_mpc_solve_cpu(const float *state0, const float *ref, int ref_cols, 
   if (!state0 || !ref || !u || !cost_out) return fail("NULL buffer");
   const QuadConst c = make_const(*model, dt);
   if (H == 5)
-    mpc_solve_batch<5>(state0, ref, ref_cols, c, *weights, *opt, B, u, cost_out, cost_trace);
+    mpc_solve_batch<5>(state0, ref, ref_cols, MpcAnalytic{c}, *weights, *opt, B, u, cost_out,
+                       cost_trace);
   else
-    mpc_solve_batch<10>(state0, ref, ref_cols, c, *weights, *opt, B, u, cost_out, cost_trace);
+    mpc_solve_batch<10>(state0, ref, ref_cols, MpcAnalytic{c}, *weights, *opt, B, u, cost_out,
+                        cost_trace);
   return APG_OK;
 }
 
@@ -1039,7 +1042,85 @@ int apg_quad_mpc_closed_loop_cpu(const ApgQuadFlight *flight, float dt,
     flight->steps[b] = mpc_flight(
         [&](int r, int col) { return flight->traj[((size_t)r * 9 + col) * Bs + b]; },
         [&](float (&s)[12], const float (&u0)[4]) { quad_step(s, u0, cp, make_trig(&s[3])); },
-        cm, *weights, *opt, rule,
+        MpcAnalytic{cm}, *weights, *opt, rule,
+        MpcFlightLog{flight->div, flight->drone, flight->actions, flight->start_states, cost,
+                     Bs, b});
+  return APG_OK;
+}
+
+}  // extern "C"
+
+// apg_cpu_mpc.h: the same solver on the learnt model of quad_learnt_mpc_math.h
+namespace {
+
+// the block the kernels read, filled as learnt_pack_kernel fills it
+std::vector<float> learnt_pack_host(const ApgLearntResidual &m) {
+  std::vector<float> pack(kLearntFloats);
+  for (int t = 0; t < kLearntFloats; ++t) pack[t] = learnt_packed(t, m);
+  return pack;
+}
+
+}  // namespace
+
+extern "C" {
+
+int apg_quad_learnt_mpc_workspace_floats_cpu(void) { return 2 * kLearntFloats; }
+
+int apg_quad_learnt_mpc_solve_cpu(const float *state0, const float *ref, int ref_cols, float dt,
+                                  const ApgQuadParams *model,
+                                  const ApgLearntResidual *model_learnt,
+                                  const ApgQuadLossWeights *weights,
+                                  const ApgQuadMpcOptions *opt, int B, int H, float *u,
+                                  float *cost_out, float *cost_trace, float *workspace) {
+  (void)workspace;
+  if (int e = check_mpc(model, weights, opt, B, H, true)) return e;
+  if (const char *e = learnt_mpc_check_model(model_learnt)) return fail("%s", e);
+  if (ref_cols != 9 && ref_cols != 6)
+    return fail("ref_cols must be 9 ([pos, euler, vel]) or 6 ([pos, vel])");
+  if (B == 0) return APG_OK;
+  if (!state0 || !ref || !u || !cost_out) return fail("NULL buffer");
+  const QuadConst c = make_const(*model, dt);
+  const std::vector<float> pack = learnt_pack_host(*model_learnt);
+  float pre[10 * kMpcPreRow];
+  const MpcLearnt<const float *> m{c, pack.data(), pre};
+  if (H == 5)
+    mpc_solve_batch<5>(state0, ref, ref_cols, m, *weights, *opt, B, u, cost_out, cost_trace);
+  else
+    mpc_solve_batch<10>(state0, ref, ref_cols, m, *weights, *opt, B, u, cost_out, cost_trace);
+  return APG_OK;
+}
+
+int apg_quad_learnt_mpc_closed_loop_cpu(const ApgQuadFlight *flight, float dt,
+                                        const ApgQuadParams *plant,
+                                        const ApgLearntResidual *plant_learnt,
+                                        const ApgQuadParams *model,
+                                        const ApgLearntResidual *model_learnt,
+                                        const ApgQuadLossWeights *weights,
+                                        const ApgQuadMpcOptions *opt, int B, int H,
+                                        float *cost, float *workspace) {
+  (void)workspace;
+  if (int e = check_mpc(model, weights, opt, B, H, false)) return e;
+  if (!plant) return fail("plant is NULL");
+  if (const char *e = learnt_mpc_check_model(model_learnt)) return fail("%s", e);
+  QuadFlightRule rule;
+  if (const char *e = quad_flight_check(flight, plant_learnt, B, &rule)) return fail("%s", e);
+  const QuadConst cp = make_const(*plant, dt), cm = make_const(*model, dt);
+  const std::vector<float> pack = learnt_pack_host(*model_learnt);
+  const std::vector<float> plant_pack =
+      plant_learnt ? learnt_pack_host(*plant_learnt) : std::vector<float>();
+  const float *pl = plant_learnt ? plant_pack.data() : nullptr;
+  float pre[kFlightH * kMpcPreRow];
+  const MpcLearnt<const float *> m{cm, pack.data(), pre};
+  const size_t Bs = (size_t)B;
+  for (size_t b = 0; b < Bs; ++b)
+    flight->steps[b] = mpc_flight(
+        [&](int r, int col) { return flight->traj[((size_t)r * 9 + col) * Bs + b]; },
+        [&](float (&s)[12], const float (&u0)[4]) {
+          const Trig t = make_trig(&s[3]);
+          if (pl) learnt_quad_step_lane(s, u0, cp, t, pl);
+          else quad_step(s, u0, cp, t);
+        },
+        m, *weights, *opt, rule,
         MpcFlightLog{flight->div, flight->drone, flight->actions, flight->start_states, cost,
                      Bs, b});
   return APG_OK;

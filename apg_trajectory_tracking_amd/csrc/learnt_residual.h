@@ -11,15 +11,14 @@
 // half-waves of a trajectory take 32 of the 64 hidden units each and exchange
 // the 12 sums (one wave = 32 trajectories, policy_mfma.h).
 #pragma once
+#include "learnt_pack.h"
 #include "policy_mfma.h"
 #include "quad_math.h"
 
 namespace apg {
 
-constexpr int kLrW1 = 0, kLrB1 = 1024, kLrW2 = 1088, kLrB2 = 1856, kLrA = 1868,
-              kLearntFloats = 1920;   // (a multiple of 64: whole DMA rows)
-
-// [W1 [64][16] | b1 [64] | W2^T [64][12] | b2 [12] | A [4][4]] at dst
+// the block of learnt_pack.h at dst:
+// [W1 [64][16] | b1 [64] | W2^T [64][12] | b2 [12] | A [4][4]]
 static __global__ __launch_bounds__(256) void learnt_pack_kernel(ApgLearntResidual m, float *dst) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t < 1024) dst[kLrW1 + t] = m.w1[t];

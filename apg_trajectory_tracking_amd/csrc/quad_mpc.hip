@@ -9,8 +9,14 @@
 // (__launch_bounds__(64): the unified 512-entry file, the compiler parks what
 // does not fit in the accumulation half) - kernel_resources.json must show no
 // scratch and no spill for them (tests/test_quad_mpc_cpu.py).
+// The same solver with the LEARNT simulator as its model
+// (apg_quad_learnt_mpc_solve, apg_quad_learnt_mpc_closed_loop;
+// quad_learnt_mpc_math.h): the model's packed weights and the pre-step states of
+// the forward sweep live in LDS, everything else as above; the residual is a
+// 16 -> 64 -> 12 network per trajectory on per-lane inputs - no MFMA either
+// (DESIGN.md §7).
 #include "learnt_residual.h"
-#include "quad_mpc_math.h"
+#include "quad_learnt_mpc_math.h"
 
 namespace apg {
 namespace {
@@ -26,10 +32,9 @@ struct MpcSolveArgs {
   int B, ref_cols;
 };
 
-template <int H>
-__global__ __launch_bounds__(kMpcThreads) void quad_mpc_solve_kernel(MpcSolveArgs A) {
-  const int b = blockIdx.x * kMpcThreads + threadIdx.x;
-  if (b >= A.B) return;
+// one solve of trajectory b on `model` (quad_mpc_math.h: a model of the solver)
+template <int H, class Model>
+__device__ __forceinline__ void mpc_solve_lane(const MpcSolveArgs &A, int b, const Model &model) {
   const size_t B = (size_t)A.B;
   const int rc = A.ref_cols, vc = rc == 9 ? 6 : 3;
   float s0[12], ref[H][6], u[H][4];
@@ -46,7 +51,7 @@ __global__ __launch_bounds__(kMpcThreads) void quad_mpc_solve_kernel(MpcSolveArg
     for (int j = 0; j < 4; ++j) u[k][j] = A.u[((size_t)k * 4 + j) * B + b];
   }
   float *trace = A.cost_trace;
-  const float J = mpc_solve<H>(s0, ref, u, A.c, A.w, A.o, [&](int i, float Ji) {
+  const float J = mpc_solve<H>(s0, ref, u, model, A.w, A.o, [&](int i, float Ji) {
     if (trace) trace[(size_t)i * B + b] = Ji;
   });
   A.cost_out[b] = J;
@@ -56,32 +61,39 @@ __global__ __launch_bounds__(kMpcThreads) void quad_mpc_solve_kernel(MpcSolveArg
     for (int j = 0; j < 4; ++j) A.u[((size_t)k * 4 + j) * B + b] = u[k][j];
 }
 
-// LearntDynamics.forward for ONE trajectory per lane (learnt_residual.h has the
-// half-wave form of the policy kernels): a' = A a, the analytic step on a',
-// plus W2 relu(W1 [s, a'] + b1) + b2; `lr`: the packed weights in LDS
-__device__ __forceinline__ void learnt_quad_step_lane(float (&s)[12], const float (&act)[4],
-                                                      const QuadConst &c, const Trig &t,
-                                                      const float *lr) {
-  float x[16], at[4], add[12];
-#pragma unroll
-  for (int i = 0; i < 12; ++i) x[i] = s[i], add[i] = lr[kLrB2 + i];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float *a = lr + kLrA + 4 * i;
-    x[12 + i] = at[i] = fmaf(a[3], act[3], fmaf(a[2], act[2], fmaf(a[1], act[1], a[0] * act[0])));
-  }
-  quad_step(s, at, c, t);
-#pragma unroll 2
-  for (int m = 0; m < 64; ++m) {
-    float h = lr[kLrB1 + m];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) h = fmaf(lr[kLrW1 + m * 16 + j], x[j], h);
-    h = fmaxf(h, 0.f);
-#pragma unroll
-    for (int o = 0; o < 12; ++o) add[o] = fmaf(lr[kLrW2 + m * 12 + o], h, add[o]);
-  }
-#pragma unroll
-  for (int o = 0; o < 12; ++o) s[o] += add[o];
+template <int H>
+__global__ __launch_bounds__(kMpcThreads) void quad_mpc_solve_kernel(MpcSolveArgs A) {
+  const int b = blockIdx.x * kMpcThreads + threadIdx.x;
+  if (b >= A.B) return;
+  mpc_solve_lane<H>(A, b, MpcAnalytic{A.c});
+}
+
+// The learnt model's kernels keep two things in LDS: the model's packed block
+// (learnt_pack.h, 7.7 KB) and, behind it, the lanes' pre-step states of the
+// forward sweep, [H][12][64 lanes] (H = 10: 30 KB) - 37.5 KB per one-wave
+// workgroup, four workgroups per CU.
+template <int H>
+constexpr int kLearntMpcLds = kLearntFloats + H * kMpcPreRow * kMpcThreads;
+static_assert(4 * kLearntMpcLds<10> * sizeof(float) <= 160 * 1024, "four workgroups per CU");
+static_assert(kMpcPreStride == kMpcThreads || kMpcPreStride == 1, "one wave per workgroup");
+
+// lds <- the packed block at `packed`; -> the solver's model for this lane
+__device__ __forceinline__ MpcLearnt<const float *> learnt_model_in_lds(float *lds,
+                                                                         const float *packed,
+                                                                         const QuadConst &c) {
+  for (int i = threadIdx.x; i < kLearntFloats; i += kMpcThreads) lds[i] = packed[i];
+  __syncthreads();
+  return MpcLearnt<const float *>{c, lds, lds + kLearntFloats + threadIdx.x};
+}
+
+template <int H>
+__global__ __launch_bounds__(kMpcThreads) void quad_learnt_mpc_solve_kernel(
+    MpcSolveArgs A, const float *packed) {
+  __shared__ float lds[kLearntMpcLds<H>];
+  const MpcLearnt<const float *> model = learnt_model_in_lds(lds, packed, A.c);
+  const int b = blockIdx.x * kMpcThreads + threadIdx.x;
+  if (b >= A.B) return;
+  mpc_solve_lane<H>(A, b, model);
 }
 
 struct MpcLoopArgs {
@@ -114,10 +126,37 @@ __global__ __launch_bounds__(kMpcThreads) void quad_mpc_closed_loop_kernel(MpcLo
       [&](int r, int col) { return tr[((size_t)r * 9 + col) * B]; },
       [&](float (&s)[12], const float (&u0)[4]) {
         const Trig t = make_trig(&s[3]);
-        if (LEARNT) learnt_quad_step_lane(s, u0, A.cp, t, lr);
+        if (LEARNT) learnt_quad_step_lane(s, u0, A.cp, t, (const float *)lr);
         else quad_step(s, u0, A.cp, t);
       },
-      A.cm, A.w, A.o, A.rule, log);
+      MpcAnalytic{A.cm}, A.w, A.o, A.rule, log);
+}
+
+// The same flight with the solver planning on the learnt model (`packed`: its
+// block, into LDS).  The plant's block - another module's, or the same one's -
+// stays where learnt_pack_kernel put it: one plant step per control step against
+// 210 model steps and 100 adjoints, its weights wave-uniform reads through the
+// constant address space (scalar operands), no LDS for them.
+template <bool LEARNT>
+__global__ __launch_bounds__(kMpcThreads) void quad_learnt_mpc_closed_loop_kernel(
+    MpcLoopArgs A, const float *packed) {
+  typedef __attribute__((address_space(4))) const float *cfloat_ptr;
+  __shared__ float lds[kLearntMpcLds<kFlightH>];
+  const MpcLearnt<const float *> model = learnt_model_in_lds(lds, packed, A.cm);
+  const int b = blockIdx.x * kMpcThreads + threadIdx.x;
+  if (b >= A.B) return;
+  const size_t B = (size_t)A.B;
+  const float *tr = A.traj + b;
+  MpcFlightLog log = A.log;
+  log.B = B, log.b = (size_t)b;
+  A.steps[b] = mpc_flight(
+      [&](int r, int col) { return tr[((size_t)r * 9 + col) * B]; },
+      [&](float (&s)[12], const float (&u0)[4]) {
+        const Trig t = make_trig(&s[3]);
+        if (LEARNT) learnt_quad_step_lane(s, u0, A.cp, t, (cfloat_ptr)A.learnt);
+        else quad_step(s, u0, A.cp, t);
+      },
+      model, A.w, A.o, A.rule, log);
 }
 
 int check_mpc(const ApgQuadParams *model, const ApgQuadLossWeights *weights,
@@ -216,6 +255,102 @@ int apg_quad_mpc_closed_loop(const ApgQuadFlight *flight, float dt, const ApgQua
     hipLaunchKernelGGL(quad_mpc_closed_loop_kernel<false>, grid, dim3(kMpcThreads), 0, st, A);
   }
   return check_launch("quad_mpc_closed_loop");
+}
+
+// [0, kLearntFloats): the model's block, [kLearntFloats, 2 kLearntFloats): the plant's
+int apg_quad_learnt_mpc_workspace_floats(void) { return 2 * kLearntFloats; }
+
+int apg_quad_learnt_mpc_solve(const float *state0, const float *ref, int ref_cols, float dt,
+                              const ApgQuadParams *model, const ApgLearntResidual *model_learnt,
+                              const ApgQuadLossWeights *weights, const ApgQuadMpcOptions *opt,
+                              int B, int H, float *u, float *cost_out, float *cost_trace,
+                              float *workspace, apg_stream_t stream) {
+  if (int e = check_mpc(model, weights, opt, B)) return e;
+  if (const char *e = learnt_mpc_check_model(model_learnt)) {
+    set_error("%s", e);
+    return APG_ERR_ARG;
+  }
+  if (H != 5 && H != 10) {
+    set_error("H must be 5 or 10 (got %d)", H);
+    return APG_ERR_ARG;
+  }
+  if (ref_cols != 9 && ref_cols != 6) {
+    set_error("ref_cols must be 9 ([pos, euler, vel]) or 6 ([pos, vel])");
+    return APG_ERR_ARG;
+  }
+  if (B == 0) return APG_OK;
+  if (!state0 || !ref || !u || !cost_out || !workspace) {
+    set_error("NULL buffer");
+    return APG_ERR_ARG;
+  }
+  MpcSolveArgs A;
+  A.state0 = state0, A.ref = ref, A.u = u, A.cost_out = cost_out, A.cost_trace = cost_trace;
+  A.c = make_const(*model, dt);
+  A.w = *weights, A.o = *opt;
+  A.B = B, A.ref_cols = ref_cols;
+  const dim3 grid((B + kMpcThreads - 1) / kMpcThreads);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(learnt_pack_kernel, dim3((kLearntFloats + 255) / 256), dim3(256), 0, st,
+                     *model_learnt, workspace);
+  const float *packed = workspace;
+  if (H == 5)
+    hipLaunchKernelGGL(quad_learnt_mpc_solve_kernel<5>, grid, dim3(kMpcThreads), 0, st, A, packed);
+  else
+    hipLaunchKernelGGL(quad_learnt_mpc_solve_kernel<10>, grid, dim3(kMpcThreads), 0, st, A,
+                       packed);
+  return check_launch("quad_learnt_mpc_solve");
+}
+
+int apg_quad_learnt_mpc_closed_loop(const ApgQuadFlight *flight, float dt,
+                                    const ApgQuadParams *plant,
+                                    const ApgLearntResidual *plant_learnt,
+                                    const ApgQuadParams *model,
+                                    const ApgLearntResidual *model_learnt,
+                                    const ApgQuadLossWeights *weights,
+                                    const ApgQuadMpcOptions *opt, int B, int H, float *cost,
+                                    float *workspace, apg_stream_t stream) {
+  if (int e = check_mpc(model, weights, opt, B)) return e;
+  if (!plant) {
+    set_error("plant is NULL");
+    return APG_ERR_ARG;
+  }
+  if (const char *e = learnt_mpc_check_model(model_learnt)) {
+    set_error("%s", e);
+    return APG_ERR_ARG;
+  }
+  if (H != kFlightH) {
+    set_error("H must be %d (got %d)", kFlightH, H);
+    return APG_ERR_ARG;
+  }
+  MpcLoopArgs A;
+  if (const char *e = quad_flight_check(flight, plant_learnt, B, &A.rule)) {
+    set_error("%s", e);
+    return APG_ERR_ARG;
+  }
+  if (B == 0) return APG_OK;
+  if (!workspace) {
+    set_error("NULL buffer");
+    return APG_ERR_ARG;
+  }
+  A.traj = flight->traj, A.steps = flight->steps;
+  A.log = {flight->div, flight->drone, flight->actions, flight->start_states, cost, 0, 0};
+  A.learnt = plant_learnt ? workspace + kLearntFloats : nullptr;
+  A.cp = make_const(*plant, dt), A.cm = make_const(*model, dt);
+  A.w = *weights, A.o = *opt, A.B = B;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((B + kMpcThreads - 1) / kMpcThreads), pack((kLearntFloats + 255) / 256);
+  const float *packed = workspace;
+  hipLaunchKernelGGL(learnt_pack_kernel, pack, dim3(256), 0, st, *model_learnt, workspace);
+  if (plant_learnt) {
+    hipLaunchKernelGGL(learnt_pack_kernel, pack, dim3(256), 0, st, *plant_learnt,
+                       workspace + kLearntFloats);
+    hipLaunchKernelGGL(quad_learnt_mpc_closed_loop_kernel<true>, grid, dim3(kMpcThreads), 0, st,
+                       A, packed);
+  } else {
+    hipLaunchKernelGGL(quad_learnt_mpc_closed_loop_kernel<false>, grid, dim3(kMpcThreads), 0, st,
+                       A, packed);
+  }
+  return check_launch("quad_learnt_mpc_closed_loop");
 }
 
 }  // extern "C"

@@ -19,6 +19,8 @@
 //             reverse sweep: step k's adjoint is the last reader of u[k]
 // m = 0 at the start of every solve.  After the last update one more forward
 // sweep gives the cost that belongs to the returned u.
+// The solver is generic over the MODEL (below): quad_step here (MpcAnalytic),
+// the learnt simulator in quad_learnt_mpc_math.h.
 #pragma once
 #include "quad_flight_rule.h"
 #include "quad_math.h"
@@ -43,24 +45,56 @@ __host__ __device__ __forceinline__ Trig mpc_trig(const float att[3]) {
   return t;
 }
 
-// what the reverse sweep needs of the forward one: the sin / cos of the
-// attitude before every step, the body rates before and after it, and the
-// position / velocity residuals of the loss
-template <int H>
+// A MODEL is what one step of the horizon and its adjoint are.  The solver asks
+// of it:
+//   Stash<H>                         what its adjoint keeps of the forward sweep
+//   step<STASH>(k, s, u, st)         s <- f(s, u), row k of the stash filled
+//   adjoint(k, lam, ga, u, w, st)    lam <- (df/ds)^T lam, ga += (df/du)^T lam;
+//                                    u: the step's action, w: the body rates
+//                                    before it
+// The cost is the solver's, on the states the model returns and on u itself.
+//
+// The analytic model: FlightmareDynamics' step on the constants `c`; of the
+// forward sweep it keeps the sin / cos of the attitude before every step.
+struct MpcAnalytic {
+  const QuadConst &c;
+  template <int H>
+  struct Stash {
+    Trig trig[H];
+  };
+  template <bool STASH, int H>
+  __host__ __device__ __forceinline__ void step(int k, float (&s)[12], const float (&u)[4],
+                                                Stash<H> &st) const {
+    const Trig t = mpc_trig(&s[3]);
+    if (STASH) st.trig[k] = t;
+    quad_step(s, u, c, t);
+  }
+  template <int H>
+  __host__ __device__ __forceinline__ void adjoint(int k, float (&lam)[12], float (&ga)[4],
+                                                   const float (&u)[4], const float w[3],
+                                                   const Stash<H> &st) const {
+    quad_step_adjoint(lam, ga, u[0], w, c, st.trig[k]);
+  }
+};
+
+// what the reverse sweep needs of the forward one: the model's own stash, the
+// body rates before and after every step, and the position / velocity
+// residuals of the loss
+template <int H, class Model>
 struct MpcStash {
-  Trig trig[H];
+  typename Model::template Stash<H> model;
   float w[H + 1][3];
   float dp[H][3], dv[H][3];
 };
 
 // ref[k] = (position, velocity) of window row k.  Returns J.
-template <int H, bool STASH>
+template <int H, bool STASH, class Model>
 __host__ __device__ __forceinline__ float mpc_forward(const float (&s0)[12],
                                                       const float (&ref)[H][6],
                                                       const float (&u)[H][4],
-                                                      const QuadConst &c,
+                                                      const Model &model,
                                                       const ApgQuadLossWeights &w,
-                                                      MpcStash<H> &st) {
+                                                      MpcStash<H, Model> &st) {
   float s[12];
 #pragma unroll
   for (int i = 0; i < 12; ++i) s[i] = s0[i];
@@ -71,9 +105,7 @@ __host__ __device__ __forceinline__ float mpc_forward(const float (&s0)[12],
 #pragma unroll
       for (int i = 0; i < 3; ++i) st.w[k][i] = s[9 + i];
     }
-    const Trig t = mpc_trig(&s[3]);
-    if (STASH) st.trig[k] = t;
-    quad_step(s, u[k], c, t);
+    model.template step<STASH>(k, s, u[k], st.model);
     float lp = 0.f, lv = 0.f, lw = 0.f, lr = 0.f;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
@@ -94,11 +126,11 @@ __host__ __device__ __forceinline__ float mpc_forward(const float (&s0)[12],
 }
 
 // reverse sweep + update of u and m
-template <int H>
-__host__ __device__ __forceinline__ void mpc_reverse_update(const MpcStash<H> &st,
+template <int H, class Model>
+__host__ __device__ __forceinline__ void mpc_reverse_update(const MpcStash<H, Model> &st,
                                                             float (&u)[H][4],
                                                             float (&m)[H][4],
-                                                            const QuadConst &c,
+                                                            const Model &model,
                                                             const ApgQuadLossWeights &w,
                                                             const ApgQuadMpcOptions &o) {
   float lam[12];
@@ -116,7 +148,7 @@ __host__ __device__ __forceinline__ void mpc_reverse_update(const MpcStash<H> &s
     ga[0] = 2.f * w.thrust * (u[k][0] - 0.5f);
 #pragma unroll
     for (int j = 1; j < 4; ++j) ga[j] = 2.f * w.rates * (u[k][j] - 0.5f);
-    quad_step_adjoint(lam, ga, u[k][0], st.w[k], c, st.trig[k]);
+    model.adjoint(k, lam, ga, u[k], st.w[k], st.model);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       m[k][j] = o.beta * m[k][j] + (j == 0 ? o.alpha_thrust : o.alpha_rate) * ga[j];
@@ -127,10 +159,10 @@ __host__ __device__ __forceinline__ void mpc_reverse_update(const MpcStash<H> &s
 
 // o.iters iterations from u (in: start, out: solution); trace(i, J) is called
 // with the cost before iteration i and, for i = iters, with the returned cost
-template <int H, class Trace>
+template <int H, class Model, class Trace>
 __host__ __device__ __forceinline__ float mpc_solve(const float (&s0)[12],
                                                     const float (&ref)[H][6],
-                                                    float (&u)[H][4], const QuadConst &c,
+                                                    float (&u)[H][4], const Model &model,
                                                     const ApgQuadLossWeights &w,
                                                     const ApgQuadMpcOptions &o,
                                                     Trace &&trace) {
@@ -139,15 +171,15 @@ __host__ __device__ __forceinline__ float mpc_solve(const float (&s0)[12],
   for (int k = 0; k < H; ++k)
 #pragma unroll
     for (int j = 0; j < 4; ++j) m[k][j] = 0.f;
-  MpcStash<H> st;
+  MpcStash<H, Model> st;
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll 1
 #endif
   for (int it = 0; it < o.iters; ++it) {
-    trace(it, mpc_forward<H, true>(s0, ref, u, c, w, st));
-    mpc_reverse_update<H>(st, u, m, c, w, o);
+    trace(it, mpc_forward<H, true>(s0, ref, u, model, w, st));
+    mpc_reverse_update<H>(st, u, m, model, w, o);
   }
-  const float J = mpc_forward<H, false>(s0, ref, u, c, w, st);
+  const float J = mpc_forward<H, false>(s0, ref, u, model, w, st);
   trace(o.iters, J);
   return J;
 }
@@ -174,11 +206,11 @@ struct MpcFlightLog {
 };
 
 // One closed-loop flight (quad_flight_rule.h) with the controller "shift the warm
-// start, solve on the model `cm`, apply u[0]" (first step: from u = 0.5; the
+// start, solve on the model `model`, apply u[0]" (first step: from u = 0.5; the
 // warm start is kept through a reset).  row(r, col): the flight's reference;
 // plant(s, u0): the environment's step.  Returns the iterations executed.
-template <class Row, class Plant>
-__host__ __device__ __forceinline__ int mpc_flight(Row &&row, Plant &&plant, const QuadConst &cm,
+template <class Row, class Plant, class Model>
+__host__ __device__ __forceinline__ int mpc_flight(Row &&row, Plant &&plant, const Model &model,
                                                    const ApgQuadLossWeights &w,
                                                    const ApgQuadMpcOptions &o,
                                                    const QuadFlightRule &rule,
@@ -205,7 +237,7 @@ __host__ __device__ __forceinline__ int mpc_flight(Row &&row, Plant &&plant, con
   for (int k = 0; k < rule.T; ++k) {
     log.put(log.start, k, s);
     if (k > 0) mpc_shift<H>(u);
-    const float J[1] = {mpc_solve<H>(s, win, u, cm, w, o, [](int, float) {})};
+    const float J[1] = {mpc_solve<H>(s, win, u, model, w, o, [](int, float) {})};
     log.put(log.cost, k, J);
     log.put(log.actions, k, u[0]);
     plant(s, u[0]);

@@ -17,8 +17,9 @@ A controller that is a `controllers.mpc.MPC` - the comparator the reference
 judges its controllers against - is flown the same way, with the solver inside
 the closed-loop kernel (apg_quad_mpc_closed_loop): the plant is the evaluator's
 environment, the solver's model the MPC's own parameters (other parameters =
-the model-mismatch experiment).  There is no renderer here (out of scope,
-SURVEY §8)."""
+the model-mismatch experiment; `MPC(learnt_model=module)`: the solver plans
+through that LearntDynamics module, apg_quad_learnt_mpc_closed_loop).  There
+is no renderer here (out of scope)."""
 import numpy as np
 import torch
 
@@ -62,6 +63,9 @@ class QuadEvaluator:
     def _closed_loop(self, traj, **kw):
         """One launch for the whole batch; MLP or LSTM controller, or the MPC."""
         if self.mpc is not None:
+            planner = getattr(self.mpc, "learnt_model", None)
+            if planner is not None:     # the solver plans through that module
+                kw = dict(kw, model_learnt=planner)
             return F.quad_mpc_closed_loop(
                 traj, self.dt, self.dynamics.params, model_params=self.mpc.params,
                 learnt=self.learnt, **self.mpc.options, **kw)

@@ -2052,7 +2052,7 @@ def quad_mpc_options(iters=None, beta=None, alpha_thrust=None, alpha_rate=None):
 
 
 def quad_mpc_solve(state0, ref, dt, params, u0=None, weights=None, iters=10, beta=None,
-                   alpha_thrust=None, alpha_rate=None, want_trace=False):
+                   alpha_thrust=None, alpha_rate=None, want_trace=False, learnt=None):
     """One shooting-MPC solve per trajectory in one launch (apg_quad_mpc_solve):
     `iters` iterations of projected heavy-ball descent on quad_mpc_loss of the
     H-step unroll of the model `params` from state0 [B,12] against the window
@@ -2060,7 +2060,11 @@ def quad_mpc_solve(state0, ref, dt, params, u0=None, weights=None, iters=10, bet
     to [0, 1].  u0 [B,H,4]: the start (None: 0.5 - hover thrust, zero rates).
     H = 5 or 10.  Returns dict(u [B,H,4], cost [B] = the cost of u, trace
     [iters+1,B] with want_trace: the cost before every iteration and at the
-    end, else None)."""
+    end, else None).
+    learnt: a LearntDynamics module - the solver plans through it (action
+    transform, analytic step on `params`, which are then the module's, residual
+    network; apg_quad_learnt_mpc_solve) instead of the analytic model; the cost
+    stays on u."""
     if ref.dim() != 3 or state0.dim() != 2:
         raise ValueError("state0 [B,12] and ref [B,H,9|6] expected")
     B, H, C = ref.shape
@@ -2081,24 +2085,37 @@ def quad_mpc_solve(state0, ref, dt, params, u0=None, weights=None, iters=10, bet
     cost = torch.empty(B, dtype=torch.float32, device=dev)
     trace = (torch.empty(opt.iters + 1, B, dtype=torch.float32, device=dev)
              if want_trace else None)
-    check(lib().apg_quad_mpc_solve(
-        ptr(s), ptr(r), C, float(dt), ctypes.byref(params), ctypes.byref(weights),
-        ctypes.byref(opt), B, H, ptr(u), ptr(cost), ptr(trace), stream_of(s)),
-        "apg_quad_mpc_solve")
+    if learnt is not None:
+        model = _learnt_model(learnt)
+        ws = torch.empty(lib().apg_quad_learnt_mpc_workspace_floats(), dtype=torch.float32,
+                         device=dev)
+        check(lib().apg_quad_learnt_mpc_solve(
+            ptr(s), ptr(r), C, float(dt), ctypes.byref(params), ctypes.byref(model),
+            ctypes.byref(weights), ctypes.byref(opt), B, H, ptr(u), ptr(cost), ptr(trace),
+            ptr(ws), stream_of(s)), "apg_quad_learnt_mpc_solve")
+    else:
+        check(lib().apg_quad_mpc_solve(
+            ptr(s), ptr(r), C, float(dt), ctypes.byref(params), ctypes.byref(weights),
+            ctypes.byref(opt), B, H, ptr(u), ptr(cost), ptr(trace), stream_of(s)),
+            "apg_quad_mpc_solve")
     return dict(u=u.permute(2, 0, 1).contiguous(), cost=cost, trace=trace)
 
 
 def quad_mpc_closed_loop(traj, dt, params, model_params=None, learnt=None, weights=None,
                          iters=10, beta=None, alpha_thrust=None, alpha_rate=None,
                          max_steps=251, thresh_div=1.0, thresh_stable=1.0, test_time=0,
-                         want_trajectory=False):
+                         want_trajectory=False, model_learnt=None):
     """quad_mlp_closed_loop with the policy replaced by the shooting MPC: per
     control step "shift the warm start, solve, apply u[0]", every flight of the
     batch in one launch (apg_quad_mpc_closed_loop).  `params` (and `learnt`, a
     LearntDynamics module) step the flight; `model_params` is what the solver
     plans with (None: `params` - the nominal case; other parameters: the
-    model-mismatch experiment).  Returns the dict quad_mlp_closed_loop returns,
-    plus cost [T,B]: the solver's cost at every control step."""
+    model-mismatch experiment).  model_learnt: a LearntDynamics module - the
+    solver plans through it (apg_quad_learnt_mpc_closed_loop), `model_params`
+    are then that module's (None: model_learnt.params); `learnt` stays the
+    plant: the same module, another one, or None.  Returns the dict
+    quad_mlp_closed_loop returns, plus cost [T,B]: the solver's cost at every
+    control step."""
     fl = _QuadFlight(traj, max_steps, thresh_div, thresh_stable, test_time, want_trajectory)
     require_device(fl.tr)
     cost = fl.new(fl.T, fl.B)
@@ -2106,6 +2123,15 @@ def quad_mpc_closed_loop(traj, dt, params, model_params=None, learnt=None, weigh
     ws = fl.new(lib().apg_quad_mpc_workspace_floats()) if learnt is not None else None
     opt = quad_mpc_options(iters, beta, alpha_thrust, alpha_rate)
     weights = weights or quad_loss_weights()
+    if model_learnt is not None:
+        model = model_learnt.params if model_params is None else model_params
+        residual = _learnt_model(model_learnt)
+        ws = fl.new(lib().apg_quad_learnt_mpc_workspace_floats())
+        check(lib().apg_quad_learnt_mpc_closed_loop(
+            fl.ref, float(dt), ctypes.byref(params), env, ctypes.byref(model),
+            ctypes.byref(residual), ctypes.byref(weights), ctypes.byref(opt), fl.B, 10,
+            ptr(cost), ptr(ws), stream_of(fl.tr)), "apg_quad_learnt_mpc_closed_loop")
+        return dict(fl.out, cost=cost)
     model = params if model_params is None else model_params
     check(lib().apg_quad_mpc_closed_loop(
         fl.ref, float(dt), ctypes.byref(params), env, ctypes.byref(model),
@@ -2114,14 +2140,15 @@ def quad_mpc_closed_loop(traj, dt, params, model_params=None, learnt=None, weigh
     return dict(fl.out, cost=cost)
 
 
-def quad_policy_actions(net, state0, in_ref, dt, params):
+def quad_policy_actions(net, state0, in_ref, dt, params, learnt=None):
     """The action plan [B,H,4] a quadrotor policy commits to from state0 on the
     window in_ref ([B,>=H,9] policy-input rows; [B,>=2H,9] for a one-step
     policy): a `Net(15, H, 9, 4H)` gives it in one evaluation, a `Net(15, H, 9,
     4)` by the autoregressive unroll of scripts/train_drone.py:113-165 through
     the model `params` (window copied before the relative-position
     subtraction).  The module's own forward is the policy here - the object
-    under judgement, evaluated once."""
+    under judgement, evaluated once.  learnt: a LearntDynamics module - the
+    autoregressive unroll steps through it instead of `params`."""
     H = 10
     out_dim = net.fc_out.weight.shape[0]
     with torch.no_grad():
@@ -2135,23 +2162,27 @@ def quad_policy_actions(net, state0, in_ref, dt, params):
             rel = in_ref[:, k:k + H].clone()
             rel[:, :, :3] = rel[:, :, :3] - cur[:, None, :3]
             acts.append(torch.sigmoid(net(quad_features(cur), rel)))
-            cur = quad_step(cur, acts[-1], dt, params)
+            cur = (quad_step(cur, acts[-1], dt, params) if learnt is None
+                   else learnt(cur, acts[-1], dt))
         return torch.stack(acts, 1).contiguous()
 
 
-def quad_policy_optimality_gap(net, state0, in_ref, ref, dt, params, iters=50):
+def quad_policy_optimality_gap(net, state0, in_ref, ref, dt, params, iters=50, learnt=None):
     """How far is a policy from what the optimiser reaches on the same windows,
     the same cost and the same model?  Per trajectory: the cost of the policy's
     action plan (quad_policy_actions), the MPC cost after `iters` iterations
     started AT that plan, and the MPC cost after `iters` iterations from u =
     0.5.  ref [B,>=H,9|6]: the loss rows.  Returns dict(policy [B], mpc_from_policy
-    [B], mpc [B], actions [B,H,4])."""
+    [B], mpc [B], actions [B,H,4]).  learnt: a LearntDynamics module - the
+    model of all four is that module (`params` is then the module's): the loss
+    a controller trained through the learnt simulator is defined on."""
     H = 10
-    acts = quad_policy_actions(net, state0, in_ref, dt, params)
+    kw = {} if learnt is None else dict(learnt=learnt)
+    acts = quad_policy_actions(net, state0, in_ref, dt, params, **kw)
     window = ref[:, :H]
-    policy = quad_mpc_solve(state0, window, dt, params, u0=acts, iters=0)["cost"]
-    warm = quad_mpc_solve(state0, window, dt, params, u0=acts, iters=iters)["cost"]
-    cold = quad_mpc_solve(state0, window, dt, params, iters=iters)["cost"]
+    policy = quad_mpc_solve(state0, window, dt, params, u0=acts, iters=0, **kw)["cost"]
+    warm = quad_mpc_solve(state0, window, dt, params, u0=acts, iters=iters, **kw)["cost"]
+    cold = quad_mpc_solve(state0, window, dt, params, iters=iters, **kw)["cost"]
     return dict(policy=policy, mpc_from_policy=warm, mpc=cold, actions=acts)
 
 

@@ -813,6 +813,40 @@ int apg_quad_mpc_closed_loop(const ApgQuadFlight *flight, float dt,
                              float *cost, float *workspace, apg_stream_t stream);
 int apg_quad_mpc_workspace_floats(void);
 
+/* The same solver and the same flight with the solver planning on the LEARNT
+ * simulator (LearntDynamics: a' = linear_at a, the analytic step on `model`
+ * with a', plus W2 relu(W1 [s; a'] + b1) + b2) - the role of the reference's
+ * LearntDynamicsMPC (neural_control/dynamics/learnt_dynamics.py:5-55): MPC with
+ * the ADAPTED model, and the optimiser that reaches the loss a controller
+ * trained through the learnt simulator is judged by.  `model` = the parameters
+ * the module simulates with (as apg_quad_learnt_rollout_fwd_bwd takes them),
+ * `model_learnt` = its live device tensors; NULL is an error, never a fall back
+ * to the analytic model.  The cost stays on the action u (not on linear_at u);
+ * the simulator's parameters get no gradient.  Everything else - rule, shapes,
+ * H (solve: 5 or 10, closed loop: 10), outputs - as apg_quad_mpc_solve /
+ * apg_quad_mpc_closed_loop.  In the closed loop `plant` / `plant_learnt` step
+ * the flight as before (plant_learnt NULL: the analytic plant); plant and model
+ * are packed separately: the same module or two different ones.
+ * workspace: apg_quad_learnt_mpc_workspace_floats() floats, always needed (the
+ * packed weights; packing and solving run on `stream`, nothing is allocated or
+ * synchronised: the call can be captured into a graph). */
+int apg_quad_learnt_mpc_workspace_floats(void);
+int apg_quad_learnt_mpc_solve(const float *state0, const float *ref, int ref_cols, float dt,
+                              const ApgQuadParams *model,
+                              const ApgLearntResidual *model_learnt,
+                              const ApgQuadLossWeights *weights,
+                              const ApgQuadMpcOptions *opt, int B, int H, float *u,
+                              float *cost_out, float *cost_trace, float *workspace,
+                              apg_stream_t stream);
+int apg_quad_learnt_mpc_closed_loop(const ApgQuadFlight *flight, float dt,
+                                    const ApgQuadParams *plant,
+                                    const ApgLearntResidual *plant_learnt,
+                                    const ApgQuadParams *model,
+                                    const ApgLearntResidual *model_learnt,
+                                    const ApgQuadLossWeights *weights,
+                                    const ApgQuadMpcOptions *opt, int B, int H,
+                                    float *cost, float *workspace, apg_stream_t stream);
+
 /* "Planes x planes" reduction GEMM on the matrix cores (fp32 accuracy):
  *   C[m*ldc + j] = sum_{s<S} sum_{n<N} A[(m*S + s)*N + n] * B[bplane(j,s)*N + n]
  *   bplane(j, s) = bdesc[j] + (s / sdiv) * bdesc[J + j] + (s % sdiv) * bdesc[2J + j]

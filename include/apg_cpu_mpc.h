@@ -3,9 +3,9 @@
  * (apg_quad_mpc_solve, apg_quad_mpc_closed_loop), in libapg_cpu.so next to the
  * twins of apg_cpu.h and under the same rules: HOST pointers, synchronous, the
  * per-lane header of the kernels (csrc/quad_mpc_math.h) looped over the batch,
- * signatures of apg.h minus the stream.  The closed loop flies the analytic
- * plant only: `plant_learnt` must be NULL (the learnt simulator's step is a
- * device function), `workspace` is not used (may be NULL).  The cart-pole
+ * signatures of apg.h minus the stream.  apg_quad_mpc_closed_loop_cpu flies the
+ * analytic plant only: `plant_learnt` must be NULL, `workspace` is not used (may
+ * be NULL).  The cart-pole
  * twins (apg_cartpole_mpc_solve, apg_cartpole_mpc_closed_loop; per-lane header
  * csrc/cartpole_mpc_math.h) fly the learnt plant as well: `plant_learnt` then
  * holds HOST pointers.
@@ -30,6 +30,26 @@ int apg_quad_mpc_closed_loop_cpu(const ApgQuadFlight *flight, float dt,
                                  const ApgQuadLossWeights *weights,
                                  const ApgQuadMpcOptions *opt, int B, int H,
                                  float *cost, float *workspace);
+
+/* The learnt-model solver (apg_quad_learnt_mpc_solve,
+ * apg_quad_learnt_mpc_closed_loop; per-lane header csrc/quad_learnt_mpc_math.h).
+ * These twins fly the learnt plant as well: `plant_learnt` and `model_learnt`
+ * hold HOST pointers; `workspace` is not used (may be NULL). */
+int apg_quad_learnt_mpc_workspace_floats_cpu(void);
+int apg_quad_learnt_mpc_solve_cpu(const float *state0, const float *ref, int ref_cols, float dt,
+                                  const ApgQuadParams *model,
+                                  const ApgLearntResidual *model_learnt,
+                                  const ApgQuadLossWeights *weights,
+                                  const ApgQuadMpcOptions *opt, int B, int H, float *u,
+                                  float *cost_out, float *cost_trace, float *workspace);
+int apg_quad_learnt_mpc_closed_loop_cpu(const ApgQuadFlight *flight, float dt,
+                                        const ApgQuadParams *plant,
+                                        const ApgLearntResidual *plant_learnt,
+                                        const ApgQuadParams *model,
+                                        const ApgLearntResidual *model_learnt,
+                                        const ApgQuadLossWeights *weights,
+                                        const ApgQuadMpcOptions *opt, int B, int H,
+                                        float *cost, float *workspace);
 
 int apg_cartpole_mpc_solve_cpu(const float *state0, const float *u0, float dt,
                                const ApgCartpoleParams *model,

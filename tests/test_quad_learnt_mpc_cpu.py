@@ -1,0 +1,343 @@
+"""The shooting MPC that plans through the learnt simulator (include/apg.h:
+apg_quad_learnt_mpc_solve, apg_quad_learnt_mpc_closed_loop) through its host
+twins (include/apg_cpu_mpc.h) - the per-lane model of
+csrc/quad_learnt_mpc_math.h under the solver of csrc/quad_mpc_math.h, compiled
+for the CPU - against the float64 restatement of
+tests/quad_learnt_mpc_restatement.py (model: torch_port.LearntQuadOracle, cost:
+torch_port.quad_mpc_loss, gradient: torch autograd), the float32 restatement as
+the yardstick for rounding (conftest.assert_no_worse_than_fp32, its defaults).
+Runs without a GPU."""
+import ctypes
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import quad_learnt_mpc_restatement as L
+import quad_mpc_restatement as R
+from conftest import assert_no_worse_than_fp32
+
+DT = L.DT
+F64, F32 = torch.float64, torch.float32
+N = R.to_numpy
+
+
+@pytest.fixture(scope="module")
+def tw():
+    if not os.path.exists("/opt/rocm/bin/hipcc"):
+        from apg_trajectory_tracking_amd import build as b
+        if not os.path.exists(b.LIB_CPU):
+            pytest.fail("libapg_cpu.so is not built and there is no hipcc to build it")
+    return L.twins()
+
+
+def check_solve(got, f32, f64, iters, what):
+    """u, cost and every row of the trace under the fp64 arbiter on the
+    trajectories without a kink flag; void (failing) where the float64 run has
+    too many kinks or does not exercise the projection; on ALL trajectories u
+    stays in the box and the last trace row is the returned cost."""
+    kink = f64["kink"]
+    share = float(kink.mean())
+    on_bound = float(((f64["u"] <= 0.0) | (f64["u"] >= 1.0)).double().mean())
+    print(f"{what}: kink share {share:.3f}, unknowns on a bound {on_bound:.3f}")
+    assert share <= L.MAX_KINK_SHARE[iters], f"void: kink share {share}"
+    if iters >= 10:
+        assert 0.10 < on_bound < 0.90, f"void: {on_bound} of the unknowns on a bound"
+    u = N(got["u"])
+    assert u.min() >= 0.0 and u.max() <= 1.0
+    assert np.array_equal(N(got["trace"][-1]), N(got["cost"]))
+    ok = ~kink
+    assert_no_worse_than_fp32(u[ok], N(f32["u"])[ok], N(f64["u"])[ok], what + " u")
+    col = lambda t: N(t)[ok][:, None]
+    assert_no_worse_than_fp32(col(got["cost"]), col(f32["cost"]), col(f64["cost"]),
+                              what + " cost")
+    assert got["trace"].shape[0] == f64["trace"].shape[0] == iters + 1
+    for i in range(iters + 1):
+        assert_no_worse_than_fp32(col(got["trace"][i]), col(f32["trace"][i]),
+                                  col(f64["trace"][i]), f"{what} trace[{i}]")
+
+
+@pytest.mark.parametrize("iters", L.ITERS)
+@pytest.mark.parametrize("which", ["golden", "steps"])
+def test_solve_twin_under_the_fp64_arbiter(tw, which, iters):
+    """Cases S1 (`golden` weights) and S2 (`steps`): the 256 windows of the
+    experiment from u = 0.5.  iters = 0 checks the cost alone, iters = 1 the
+    adjoint alone.  Measured (float64 restatement): mean cost 85.26 -> 41.12 in
+    10 iterations, 40.98 in 20 (S1); 82.43 -> 39.30, 39.16 (S2); kink share
+    0.105 / 0.219 (S1) and 0.090 / 0.191 (S2) at 10 / 20 iterations - the final
+    cost sweep's steps counted; 0.33-0.34 of the unknowns on a bound.  The
+    twin's worst `u` error without kink trajectories: 3.6e-6 at 10 iterations,
+    2.1e-6 at 20 (float32 restatement: 1.0e-5, 2.5e-5)."""
+    s0, ref, u0 = L.windows()
+    got = L.twin_solve(tw, L.module(which), s0, ref, u0, DT, iters)
+    check_solve(got, L.solve_case(which, F32)[iters], L.solve_case(which, F64)[iters], iters,
+                f"twin {which} iters={iters}")
+
+
+def test_horizon_five(tw):
+    """H = 5 comes from the same template: S1 at 10 iterations."""
+    s0, ref, u0 = L.windows()
+    got = L.twin_solve(tw, L.module("golden"), s0, ref[:, :5], u0[:, :5], DT, 10)
+    check_solve(got, L.solve_case("golden", F32, 5)[10], L.solve_case("golden", F64, 5)[10], 10,
+                "twin golden H=5")
+
+
+def test_the_model_is_really_used(tw):
+    """On S1 the solution differs from the nominal-model solve by more than 1e-2
+    on at least half the trajectories, and the rule optimises the learnt model:
+    the float64 mean cost falls below 0.6 x its start in 10 iterations
+    (measured: 0.48)."""
+    s0, ref, u0 = L.windows()
+    learnt = L.twin_solve(tw, L.module("golden"), s0, ref, u0, DT, 10)
+    nominal = R.twin_solve(tw, s0, ref, u0, DT, 10)
+    apart = np.abs(N(learnt["u"]) - N(nominal["u"])).reshape(s0.shape[0], -1).max(1)
+    print("trajectories more than 1e-2 apart:", float((apart > 1e-2).mean()))
+    assert (apart > 1e-2).mean() >= 0.5
+    trace = L.solve_case("golden", F64)[10]["trace"].mean(1)
+    print("float64 mean cost: %.4f -> %.4f" % (float(trace[0]), float(trace[10])))
+    assert float(trace[10]) < 0.6 * float(trace[0])
+    ends = L.solve_case("golden", F64)[20]
+    assert int((ends["cost"] > ends["trace"][0]).sum()) == 0   # nobody ends above its start
+
+
+def analytic_twin_solve(tw, params, s0, ref, u0, iters):
+    """apg_quad_mpc_solve_cpu on the parameter struct `params`."""
+    from apg_trajectory_tracking_amd import functional as F
+    B, Hh, C = ref.shape
+    s, r = s0.float().t().contiguous(), ref.float().permute(1, 2, 0).contiguous()
+    u = u0.float().permute(1, 2, 0).contiguous()
+    cost = torch.zeros(B)
+    rc = tw.apg_quad_mpc_solve_cpu(
+        s.data_ptr(), r.data_ptr(), C, DT, ctypes.byref(params),
+        ctypes.byref(F.quad_loss_weights()), ctypes.byref(R._options(iters)), B, Hh,
+        u.data_ptr(), cost.data_ptr(), None)
+    assert rc == 0, tw.apg_cpu_last_error_string()
+    return dict(u=u.permute(2, 0, 1).contiguous(), cost=cost)
+
+
+def test_a_zero_residual_is_the_analytic_solver(tw):
+    """A freshly constructed LearntDynamics (zero residual, identity linear_at):
+    u and cost equal those of apg_quad_mpc_solve_cpu on the module's parameters
+    within 1e-6."""
+    s0, ref, u0 = L.windows()
+    dyn = L.module("zero")
+    got = L.twin_solve(tw, dyn, s0, ref, u0, DT, 10)
+    want = analytic_twin_solve(tw, dyn.params, s0, ref, u0, 10)
+    assert np.abs(N(got["u"]) - N(want["u"])).max() <= 1e-6
+    assert np.abs(N(got["cost"]) - N(want["cost"])).max() <= 1e-6 * N(want["cost"]).max()
+
+
+def _loop_twin(tw, plant, test_time, B=300, steps=30, thresh_div=0.6):
+    from apg_trajectory_tracking_amd.dynamics.quad_dynamics_flightmare import (
+        FlightmareDynamics)
+    dyn = L.module("loop")
+    learnt = plant == "learnt"
+    params = dyn.params if learnt else FlightmareDynamics(modified_params=R.DRAGS).params
+    return L.twin_closed_loop(tw, L.loop_trajectories(B), DT, 10, steps, thresh_div, 1.0,
+                              test_time, params, dyn if learnt else None, dyn)
+
+
+@pytest.mark.parametrize("test_time", [0, 1])
+@pytest.mark.parametrize("plant", ["learnt", "drags"])
+def test_closed_loop_twin_vs_the_restated_loop(tw, plant, test_time):
+    """Plant and model both the closed_loop_learnt.npz module, and an analytic
+    plant (the two drags) under the same learnt model: B = 300,
+    quad_eval_trajectories(seed=9) lifted 3 m, 30 steps, thresh_div 0.6,
+    thresh_stable 1, 10 iterations, against the float64 restatement by the rule
+    of the learnt-plant flights: same `steps` on > 97 % of the flights, `div`
+    within 2e-3 on all but 3 % of those."""
+    got = _loop_twin(tw, plant, test_time)
+    L.same_flights(got["steps"], got["div"], L.loop_case(plant, test_time), 300,
+                   f"twin plant={plant} test_time={test_time}")
+
+
+def experiment(fly):
+    """The model-mismatch experiment with its second arm: 32 flights, 100
+    steps, thresh_div 3, plant the closed_loop_learnt.npz module.  fly(model) ->
+    dict(div [B,T], steps [B], start [B,T,12], drone [B,T+1,12]) for model "nominal" / "learnt".  Planning with
+    the adapted model pays: its mean divergence is below 0.8 x the nominal
+    model's (float64 restatement: 0.251 m against 0.383 m), and no flight is
+    reset in either run.  Plant and model blocks swapped or aliased would fly
+    the same path twice."""
+    div = {}
+    for model in ("nominal", "learnt"):
+        out = fly(model)
+        d, steps = N(out["div"]), N(out["steps"])
+        assert d.shape == (32, 100) and (steps == 100).all()
+        # a reset shows as a start state that is not the state the step before left
+        assert np.array_equal(N(out["start"])[:, 1:], N(out["drone"])[:, 1:100]), \
+            f"{model}: a flight was reset"
+        div[model] = float(d.mean())
+    print("mean divergence: nominal model %.4f m, learnt model %.4f m, ratio %.3f"
+          % (div["nominal"], div["learnt"], div["learnt"] / div["nominal"]))
+    assert div["learnt"] < 0.8 * div["nominal"]
+    return div
+
+
+def test_planning_with_the_adapted_model_pays(tw):
+    """The nominal arm on the twin: a freshly constructed module (zero
+    residual, the nominal parameters) as the model -
+    test_a_zero_residual_is_the_analytic_solver shows that this IS the analytic
+    solver (apg_quad_mpc_closed_loop_cpu itself flies no learnt plant)."""
+    plant = L.module("loop")
+    traj = L.loop_trajectories(32, 120)
+
+    def fly(model):
+        m = plant if model == "learnt" else L.module("zero")
+        return L.twin_closed_loop(tw, traj, DT, 10, 100, 3.0, 1.0, 0, plant.params, plant, m)
+    experiment(fly)
+
+
+def _twin_behind_functional(tw, monkeypatch):
+    """functional.quad_mpc_solve on CPU tensors: the host twins behind the
+    signature of the package's function (tests only - the package itself never
+    loads the twins)."""
+    from apg_trajectory_tracking_amd import functional as F
+
+    def stand_in(state0, ref, dt, params, u0=None, weights=None, iters=10, beta=None,
+                 alpha_thrust=None, alpha_rate=None, want_trace=False, learnt=None):
+        B, Hh, _ = ref.shape
+        u0 = torch.full((B, Hh, 4), 0.5) if u0 is None else u0
+        assert learnt is not None and params is learnt.params
+        return L.twin_solve(tw, learnt, state0, ref, u0, dt, iters)
+    monkeypatch.setattr(F, "quad_mpc_solve", stand_in)
+
+
+def test_mpc_object_with_a_learnt_model(tw, monkeypatch):
+    """`MPC(learnt_model=m).predict_actions`: numpy [12] + [H,9] -> [1,4] equal
+    to row 0 of the batched call; the warm start is shifted per call (call 2 =
+    the closed loop's second action) and dropped by reset(); what cannot be
+    combined is refused."""
+    from apg_trajectory_tracking_amd.controllers import MPC
+    _twin_behind_functional(tw, monkeypatch)
+    dyn = L.module("loop")
+    traj = L.loop_trajectories(8)
+    loop = L.twin_closed_loop(tw, traj, DT, 10, 3, 3.0, 1.0, 0, dyn.params, dyn, dyn)
+    B = traj.shape[0]
+    s0 = torch.zeros(B, 12)
+    s0[:, :3] = traj[:, 0, :3]
+    batched = MPC(horizon=10, dt=DT, device="cpu", learnt_model=dyn)
+    assert batched.params is dyn.params and batched.learnt_model is dyn
+    a = batched.predict_actions(s0, traj[:, 1:11])
+    assert torch.is_tensor(a) and a.shape == (B, 4)
+    assert np.abs(N(a) - N(loop["actions"][:, 0])).max() <= 1e-6
+    single = MPC(horizon=10, dt=DT, device="cpu", learnt_model=dyn)
+    a0 = single.predict_actions(s0[0].numpy(), traj[0, 1:11].numpy())
+    assert isinstance(a0, np.ndarray) and a0.shape == (1, 4)
+    assert np.array_equal(a0[0], a[0].numpy())
+    a2 = batched.predict_actions(loop["start"][:, 1], traj[:, 2:12])
+    assert np.abs(N(a2) - N(loop["actions"][:, 1])).max() <= 1e-6
+    batched.reset()
+    assert batched.warm_start is None
+    assert torch.equal(batched.predict_actions(s0, traj[:, 1:11]), a)
+    with pytest.raises(ValueError, match="modified_params"):
+        MPC(learnt_model=dyn, modified_params={"mass": 1.0})
+    with pytest.raises(NotImplementedError, match="flightmare"):
+        MPC(dynamics="cartpole", dt=0.05, learnt_model=dyn)
+    assert MPC(device="cpu").learnt_model is None
+
+
+def test_evaluator_routes_a_learnt_model_to_the_new_closed_loop(tw, monkeypatch):
+    """QuadEvaluator(MPC(learnt_model=m), env): plant parameters from `env`,
+    model parameters and model block from `m` (the host twin stands behind
+    functional.quad_mpc_closed_loop)."""
+    from apg_trajectory_tracking_amd import functional as F
+    from apg_trajectory_tracking_amd.controllers import MPC
+    from apg_trajectory_tracking_amd.dynamics.quad_dynamics_flightmare import (
+        FlightmareDynamics)
+    from apg_trajectory_tracking_amd.evaluate_drone import QuadEvaluator
+    dyn = L.module("loop")
+    env = FlightmareDynamics(modified_params=R.DRAGS)
+    seen = {}
+
+    def stand_in(traj, dt, params, model_params=None, learnt=None, weights=None, iters=10,
+                 beta=None, alpha_thrust=None, alpha_rate=None, max_steps=251,
+                 thresh_div=1.0, thresh_stable=1.0, test_time=0, want_trajectory=False,
+                 model_learnt=None):
+        seen.update(plant=params, model=model_params, learnt=learnt, model_learnt=model_learnt,
+                    iters=iters)
+        o = L.twin_closed_loop(tw, traj, dt, iters, max_steps, thresh_div, thresh_stable,
+                               test_time, params, learnt, model_learnt)
+        return dict(div=o["div"].t().contiguous(), steps=o["steps"].to(torch.int32),
+                    cost=o["cost"].t().contiguous(),
+                    drone=o["drone"].permute(1, 2, 0).contiguous(),
+                    actions=o["actions"].permute(1, 2, 0).contiguous(),
+                    start_states=o["start"].permute(1, 2, 0).contiguous())
+    monkeypatch.setattr(F, "quad_mpc_closed_loop", stand_in)
+    ev = QuadEvaluator(MPC(horizon=10, dt=DT, iters=5, device="cpu", learnt_model=dyn), env,
+                       dt=DT)
+    traj = L.loop_trajectories(6)
+    stats = ev.run_eval(nr_test=6, max_steps=12, thresh_div=3, trajectories=traj)
+    assert len(stats) == 6 and stats[0] == 12.0
+    assert seen["plant"] is env.params and seen["model"] is dyn.params
+    assert seen["model_learnt"] is dyn and seen["learnt"] is None and seen["iters"] == 5
+    want = L.twin_closed_loop(tw, traj, DT, 5, 12, 3.0, 1.0, 0, env.params, None, dyn)
+    refs, drone, divs, acts = ev.follow_trajectory("rand", max_nr_steps=12, thresh_div=3,
+                                                   thresh_stable=1, trajectories=traj)
+    assert len(divs) == 6 and drone[0].shape == (13, 12) and acts[0].shape == (12, 4)
+    assert np.abs(N(divs[0]) - N(want["div"][0])).max() == 0
+    # and the learnt environment stays the plant
+    ev = QuadEvaluator(MPC(horizon=10, dt=DT, device="cpu", learnt_model=dyn), dyn, dt=DT)
+    ev.run_eval(nr_test=6, max_steps=3, thresh_div=3, trajectories=traj)
+    assert seen["learnt"] is dyn and seen["plant"] is dyn.params
+
+
+def test_twin_argument_errors(tw):
+    from apg_trajectory_tracking_amd import _capi, functional as F
+    s0, ref, u0 = L.windows()
+    s, r = s0.t().contiguous(), ref.permute(1, 2, 0).contiguous()
+    u = u0.permute(1, 2, 0).contiguous()
+    cost = torch.zeros(s0.shape[0])
+    dyn = L.module("golden")
+    res, _keep = L.host_residual(dyn)
+    w = F.quad_loss_weights()
+
+    def call(H=10, rc=9, opt=None, model=res):
+        o = opt or R._options(1)
+        return tw.apg_quad_learnt_mpc_solve_cpu(
+            s.data_ptr(), r.data_ptr(), rc, DT, ctypes.byref(dyn.params),
+            ctypes.byref(model) if model is not None else None, ctypes.byref(w),
+            ctypes.byref(o), s0.shape[0], H, u.data_ptr(), cost.data_ptr(), None, None)
+    assert call() == 0
+    assert call(H=7) == -1 and b"H must be 5 or 10" in tw.apg_cpu_last_error_string()
+    assert call(rc=5) == -1 and b"ref_cols" in tw.apg_cpu_last_error_string()
+    assert call(model=None) == -1 and b"model_learnt is NULL" in tw.apg_cpu_last_error_string()
+    hole = _capi.ApgLearntResidual(res.linear_at, res.w1, None, res.w2, res.b2)
+    assert call(model=hole) == -1 and b"weight pointer" in tw.apg_cpu_last_error_string()
+    assert call(opt=_capi.ApgQuadMpcOptions(1, 1.5, 0.1, 0.1)) == -1
+    assert call(opt=_capi.ApgQuadMpcOptions(-1, 0.5, 0.1, 0.1)) == -1
+    # the closed loop: H = 10 only, and no model is no model there either
+    traj = L.loop_trajectories(4)
+    tr = traj.permute(1, 2, 0).contiguous()
+    div, steps = torch.zeros(5, 4), torch.zeros(4, dtype=torch.int32)
+    flight = _capi.ApgQuadFlight(tr.data_ptr(), 40, 5, 3.0, 1.0, 0, div.data_ptr(),
+                                 steps.data_ptr(), None, None, None)
+
+    def loop(H=10, model=res):
+        return tw.apg_quad_learnt_mpc_closed_loop_cpu(
+            ctypes.byref(flight), DT, ctypes.byref(dyn.params), None, ctypes.byref(dyn.params),
+            ctypes.byref(model) if model is not None else None, ctypes.byref(w),
+            ctypes.byref(R._options(1)), 4, H, None, None)
+    assert loop() == 0 and int(steps.min()) == 5
+    assert loop(H=5) == -1 and b"H must be 10" in tw.apg_cpu_last_error_string()
+    assert loop(model=None) == -1 and b"model_learnt is NULL" in tw.apg_cpu_last_error_string()
+
+
+def test_kernels_keep_scratch_free():
+    """Every instantiation of the learnt-model kernels in the build's
+    kernel_resources.json - the solve at H = 10 and H = 5, the closed loop with
+    the analytic and with the learnt plant - without scratch and without
+    spilled VGPRs."""
+    from apg_trajectory_tracking_amd import build
+    build.build()
+    with open(build.RESOURCES) as f:
+        res = json.load(f)
+    solve = {k: v for k, v in res.items() if "quad_learnt_mpc_solve_kernel" in k}
+    loop = {k: v for k, v in res.items() if "quad_learnt_mpc_closed_loop_kernel" in k}
+    assert len(solve) >= 2 and len(loop) >= 1, (sorted(solve), sorted(loop))
+    assert any("ILi10E" in k for k in solve) and any("ILi5E" in k for k in solve)
+    for k, v in {**solve, **loop}.items():
+        print(k, v)
+        assert v["scratch"] == 0 and v["vgpr_spill"] == 0, (k, v)
