@@ -15,6 +15,18 @@
 #include "launch_chain.h"
 
 namespace apg {
+
+// quad.hip: apg_quad_rollout_fwd_bwd with the choice of the rows kernel's
+// chained instantiation
+int quad_rollout_fwd_bwd_launch(const float *state0, const float *actions,
+                                const float *ref, int ref_cols, float dt,
+                                const ApgQuadParams *params,
+                                const ApgQuadLossWeights *weights, int B, int H,
+                                int layout, float *loss_partials, float *loss,
+                                float *grad_actions, float *grad_state0,
+                                float *states_out, const ApgDeferredLoss *deferred,
+                                hipStream_t st, bool chained);
+
 namespace {
 
 struct Chain {
@@ -220,10 +232,10 @@ int apg_quad_rollout_fwd_bwd_chained(const float *state0, const float *actions,
                                      apg_stream_t stream) {
   return chained((hipStream_t)stream, loss_partials, B, loss, deferred,
                  [&](const ApgDeferredLoss *d, hipStream_t st) {
-                   return apg_quad_rollout_fwd_bwd(
+                   return quad_rollout_fwd_bwd_launch(
                        state0, actions, ref, ref_cols, dt, params, weights, B, H,
                        layout, loss_partials, nullptr, grad_actions, grad_state0,
-                       states_out, d, st);
+                       states_out, d, st, true);
                  });
 }
 

@@ -438,10 +438,39 @@ constexpr bool kStoreAtEnd = APG_ROWS_TUNE(1, APG_ROWS_STORE_AT_END) != 0;
 constexpr int kStoreFlushAt = APG_ROWS_TUNE(-1, APG_ROWS_STORE_FLUSH_AT);
 // true: rows below H - kRefLook all requested at the top of the reverse sweep
 constexpr bool kRefTop = APG_ROWS_TUNE(0, APG_ROWS_REF_TOP) != 0;
+// The CHAINED instantiation (launches of the two-lane chain, launch_chain.hip):
+// with two launches in flight a wave of launch i+1 starts only where a wave of
+// launch i has retired, so what counts is resident waves and wave lifetime.
+// The store timing of dL/dactions is the chain's own: one store per reverse
+// step (the serial form's reason for "after the sweep" does not hold under the
+// chain: 7.79 -> 7.43 us).  kChainAngles (NOT shipped, variant builds only):
+// the stash between the sweeps holds the three attitude angles of a step
+// instead of their six sin/cos values, and the reverse sweep calls make_trig
+// again - 30 registers less at H = 10, two waves per SIMD, another 0.4 us -
+// but the compiler contracts the reverse sweep's sums differently once its
+// products are no longer shared with the forward sweep, and dL/dactions comes
+// out up to 32 ulp off the serial form.  profiles/ab_chained_rows_kernel.txt.
+#if !defined(APG_EXPERIMENT_BUILD) &&                                          \
+    (defined(APG_ROWS_CHAIN_ANGLES) || defined(APG_ROWS_CHAIN_STORE_AT_END) || \
+     defined(APG_ROWS_CHAIN_STORE_FLUSH_AT))
+#error "experiment macro in a product build (variants: -DAPG_EXPERIMENT_BUILD, tools/build_variant.py)"
+#endif
+#ifndef APG_ROWS_CHAIN_ANGLES
+#define APG_ROWS_CHAIN_ANGLES 0
+#endif
+#ifndef APG_ROWS_CHAIN_STORE_AT_END
+#define APG_ROWS_CHAIN_STORE_AT_END 0
+#endif
+#ifndef APG_ROWS_CHAIN_STORE_FLUSH_AT
+#define APG_ROWS_CHAIN_STORE_FLUSH_AT (-1)
+#endif
+constexpr bool kChainAngles = APG_ROWS_TUNE(0, APG_ROWS_CHAIN_ANGLES) != 0;
+constexpr bool kChainStoreAtEnd = APG_ROWS_TUNE(0, APG_ROWS_CHAIN_STORE_AT_END) != 0;
+constexpr int kChainStoreFlushAt = APG_ROWS_TUNE(-1, APG_ROWS_CHAIN_STORE_FLUSH_AT);
 #undef APG_ROWS_TUNE
 }  // namespace rows_tune
 
-template <int HT, bool STATES_OUT>
+template <int HT, bool STATES_OUT, bool CHAINED>
 __global__ __launch_bounds__(rows_tune::kBlock) void quad_rollout_rows_kernel(
     const float *state0, const float *actions, const float *ref, int B, float dt,
     float half_dt, float half_dt2, float g0, float g1, float g2, float k0,
@@ -461,6 +490,9 @@ __global__ __launch_bounds__(rows_tune::kBlock) void quad_rollout_rows_kernel(
   using namespace rows_tune;
   constexpr int kActPre = HT < kActPreMax ? HT : kActPreMax;
   constexpr int kRefLook = kRefLookMax > HT ? HT : kRefLookMax;
+  constexpr bool kAngles = CHAINED && kChainAngles;
+  constexpr bool kAtEnd = CHAINED ? kChainStoreAtEnd : kStoreAtEnd;
+  constexpr int kFlush = CHAINED ? kChainStoreFlushAt : kStoreFlushAt;
   const auto r_s0 = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float *>(state0), 0, 3 * B * 16, 0x00020000);
   const auto r_act = __builtin_amdgcn_make_buffer_rsrc(
@@ -504,7 +536,8 @@ __global__ __launch_bounds__(rows_tune::kBlock) void quad_rollout_rows_kernel(
   __builtin_amdgcn_sched_barrier(0);
 
   float s[12];
-  Trig st_trig[HT];
+  Trig st_trig[kAngles ? 1 : HT];
+  float st_att[kAngles ? HT : 1][3];
   float st_w[HT + 1][3];
   float st_pv[HT][6];
 #pragma unroll
@@ -534,8 +567,22 @@ __global__ __launch_bounds__(rows_tune::kBlock) void quad_rollout_rows_kernel(
     const float act[4] = {u2f(a4[k].x), u2f(a4[k].y), u2f(a4[k].z), u2f(a4[k].w)};
 #pragma unroll
     for (int i = 0; i < 3; ++i) st_w[k][i] = s[9 + i];
-    st_trig[k] = make_trig(&s[3]);
-    quad_step(s, act, c, st_trig[k]);
+    if constexpr (kAngles) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) st_att[k][i] = s[3 + i];
+      const Trig t = make_trig(&s[3]);
+      // Bit-identity with the serial form: there sr * sy of thrust_dir is
+      // ALSO read by the reverse sweep (quad_step_adjoint's z0), and with that
+      // second use the compiler contracts z[0] as fma(cr, cy * sp, sr * sy).
+      // Without it, it contracts the other product - fma(sr, sy, cy * sp * cr) -
+      // and p_x, v_x come out a few ulp off.  The empty asm is that second use.
+      const float srsy = t.sr * t.sy;
+      asm volatile("" : : "v"(srsy));
+      quad_step(s, act, c, t);
+    } else {
+      st_trig[k] = make_trig(&s[3]);
+      quad_step(s, act, c, st_trig[k]);
+    }
 #pragma unroll
     for (int i = 0; i < 3; ++i) st_pv[k][i] = s[i], st_pv[k][3 + i] = s[6 + i];
     if constexpr (STATES_OUT) {
@@ -596,12 +643,20 @@ __global__ __launch_bounds__(rows_tune::kBlock) void quad_rollout_rows_kernel(
       sum_r = fmaf(d, d, sum_r);
       ga[i] = wr2 * d;
     }
-    quad_step_adjoint(lam, ga, a0, st_w[k], c, st_trig[k]);
-    if constexpr (kStoreAtEnd) {
+    if constexpr (kAngles) {
+      // the same function of the same bits as in the forward sweep; the empty
+      // asm keeps the compiler from recognising that and carrying the forward
+      // sweep's six values across after all
+      float att[3] = {st_att[k][0], st_att[k][1], st_att[k][2]};
+      asm volatile("" : "+v"(att[0]), "+v"(att[1]), "+v"(att[2]));
+      quad_step_adjoint(lam, ga, a0, st_w[k], c, make_trig(att));
+    } else {
+      quad_step_adjoint(lam, ga, a0, st_w[k], c, st_trig[k]);
+    }
+    if constexpr (kAtEnd) {
       // rows k > kFlush are kept in registers and written when step kFlush is
-      // done (kFlush = -1, shipped: all of them after the sweep), later rows at
-      // once (profiles/r03_ab_quad.json `store_timing`)
-      constexpr int kFlush = kStoreFlushAt;
+      // done (kFlush = -1, serial launches: all of them after the sweep), later
+      // rows at once (profiles/r03_ab_quad.json `store_timing`)
       a4[k] = (u4v){f2u(ga[0]), f2u(ga[1]), f2u(ga[2]), f2u(ga[3])};
       if (k <= kFlush) {
         if (k == kFlush) {
@@ -618,7 +673,7 @@ __global__ __launch_bounds__(rows_tune::kBlock) void quad_rollout_rows_kernel(
     }
     if (k == HT / 2) APG_STAMP_AT(6);
   }
-  if constexpr (kStoreAtEnd && kStoreFlushAt < 0) {
+  if constexpr (kAtEnd && kFlush < 0) {
 #pragma unroll
     for (int k = HT - 1; k >= 0; --k)
       __builtin_amdgcn_raw_buffer_store_b128(a4[k], r_ga, st16, k * p16, kStAux);
@@ -1230,7 +1285,7 @@ int launch_rollout(const RolloutArgs &A, hipStream_t st) {
 }
 
 // APG_LAYOUT_PACKED: register-resident horizons only (the reference configs)
-template <bool SO>
+template <bool SO, bool CHAINED>
 int launch_rollout_rows(const RolloutArgs &A, hipStream_t st) {
   if (A.H != 5 && A.H != 10) {
     set_error("APG_LAYOUT_PACKED: H must be 5 or 10 (got %d)", A.H);
@@ -1252,10 +1307,10 @@ int launch_rollout_rows(const RolloutArgs &A, hipStream_t st) {
   R.prev = A.prev;
   const QuadConst &c = A.c;
   const dim3 grid(grid_for(A.B, rows_tune::kBlock)), block(rows_tune::kBlock);
-#define APG_ROWS(HT)                                                        \
-  hipLaunchKernelGGL((quad_rollout_rows_kernel<HT, SO>), grid, block, 0, st,  \
-                     A.state0, A.actions, A.ref, A.B, c.dt, c.half_dt,        \
-                     c.half_dt2, c.g[0], c.g[1], c.g[2], c.kdt[0], c.kdt[1],  \
+#define APG_ROWS(HT)                                                          \
+  hipLaunchKernelGGL((quad_rollout_rows_kernel<HT, SO, CHAINED>), grid, block, \
+                     0, st, A.state0, A.actions, A.ref, A.B, c.dt, c.half_dt,  \
+                     c.half_dt2, c.g[0], c.g[1], c.g[2], c.kdt[0], c.kdt[1],   \
                      c.kdt[2], R)
   if (A.H == 10) APG_ROWS(10);
   else APG_ROWS(5);
@@ -1264,6 +1319,78 @@ int launch_rollout_rows(const RolloutArgs &A, hipStream_t st) {
 }
 
 }  // namespace
+
+// apg_quad_rollout_fwd_bwd behind its checks and its chained form
+// (launch_chain.hip).  `chained`: the launch is one of a two-lane chain;
+// APG_LAYOUT_PACKED then runs the chained instantiation of the rows kernel,
+// every other layout the kernel it always runs.
+int quad_rollout_fwd_bwd_launch(const float *state0, const float *actions,
+                                const float *ref, int ref_cols, float dt,
+                                const ApgQuadParams *params,
+                                const ApgQuadLossWeights *weights, int B, int H,
+                                int layout, float *loss_partials, float *loss,
+                                float *grad_actions, float *grad_state0,
+                                float *states_out, const ApgDeferredLoss *deferred,
+                                hipStream_t st, bool chained) {
+  if (int e = check_common(state0, actions, params, B, layout, true)) return e;
+  if (!weights) { set_error("weights is NULL"); return APG_ERR_ARG; }
+  if (deferred && deferred->prev_partials) {
+    if (!deferred->prev_loss || deferred->prev_count < 0 ||
+        deferred->prev_partials == loss_partials) {
+      set_error("deferred: prev_loss NULL, prev_count < 0 or prev_partials "
+                "aliases loss_partials");
+      return APG_ERR_ARG;
+    }
+  }
+  if (H < 1 || H > APG_MAX_HORIZON) {
+    set_error("H must be in [1, %d] (got %d)", APG_MAX_HORIZON, H);
+    return APG_ERR_ARG;
+  }
+  if (ref_cols != 9 && ref_cols != 6) {
+    set_error("ref_cols must be 9 ([pos, euler, vel]) or 6 ([pos, vel])");
+    return APG_ERR_ARG;
+  }
+  const bool has_prev = deferred && deferred->prev_partials;
+  if (B == 0) {  // empty batch: loss = 0, nothing else to write
+    if (loss) {
+      if (hipMemsetAsync(loss, 0, sizeof(float), st) != hipSuccess)
+        return check_launch("memset(loss)");
+    }
+    if (has_prev)
+      return launch_reduce_partials(deferred->prev_partials,
+                                    deferred->prev_count, deferred->prev_loss, st);
+    return APG_OK;
+  }
+  if (!ref || !loss_partials || !grad_actions) {
+    set_error("ref / loss_partials / grad_actions must not be NULL");
+    return APG_ERR_ARG;
+  }
+  RolloutArgs A;
+  A.state0 = state0, A.actions = actions, A.ref = ref;
+  A.loss_partials = loss_partials, A.grad_actions = grad_actions;
+  A.grad_state0 = grad_state0, A.states_out = states_out;
+  A.c = make_const(*params, dt);
+  A.w = *weights;
+  A.prev = has_prev ? *deferred : ApgDeferredLoss{nullptr, 0, nullptr};
+  A.B = B, A.H = H, A.ref_cols = ref_cols, A.vel_col = ref_cols == 9 ? 6 : 3;
+  int e;
+  if (layout == APG_LAYOUT_PACKED && chained)
+    e = states_out ? launch_rollout_rows<true, true>(A, st)
+                   : launch_rollout_rows<false, true>(A, st);
+  else if (layout == APG_LAYOUT_PACKED)
+    e = states_out ? launch_rollout_rows<true, false>(A, st)
+                   : launch_rollout_rows<false, false>(A, st);
+  else if (layout == APG_LAYOUT_SOA)
+    e = states_out ? launch_rollout<APG_LAYOUT_SOA, true>(A, st)
+                   : launch_rollout<APG_LAYOUT_SOA, false>(A, st);
+  else
+    e = states_out ? launch_rollout<APG_LAYOUT_AOS, true>(A, st)
+                   : launch_rollout<APG_LAYOUT_AOS, false>(A, st);
+  if (e) return e;
+  if (loss) return launch_reduce_partials(loss_partials, apg_loss_partials_count(B), loss, st);
+  return APG_OK;
+}
+
 }  // namespace apg
 
 using namespace apg;
@@ -1322,61 +1449,10 @@ int apg_quad_rollout_fwd_bwd(const float *state0, const float *actions,
                              float *states_out,
                              const ApgDeferredLoss *deferred,
                              apg_stream_t stream) {
-  if (int e = check_common(state0, actions, params, B, layout, true)) return e;
-  if (!weights) { set_error("weights is NULL"); return APG_ERR_ARG; }
-  if (deferred && deferred->prev_partials) {
-    if (!deferred->prev_loss || deferred->prev_count < 0 ||
-        deferred->prev_partials == loss_partials) {
-      set_error("deferred: prev_loss NULL, prev_count < 0 or prev_partials "
-                "aliases loss_partials");
-      return APG_ERR_ARG;
-    }
-  }
-  if (H < 1 || H > APG_MAX_HORIZON) {
-    set_error("H must be in [1, %d] (got %d)", APG_MAX_HORIZON, H);
-    return APG_ERR_ARG;
-  }
-  if (ref_cols != 9 && ref_cols != 6) {
-    set_error("ref_cols must be 9 ([pos, euler, vel]) or 6 ([pos, vel])");
-    return APG_ERR_ARG;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const bool has_prev = deferred && deferred->prev_partials;
-  if (B == 0) {  // empty batch: loss = 0, nothing else to write
-    if (loss) {
-      if (hipMemsetAsync(loss, 0, sizeof(float), st) != hipSuccess)
-        return check_launch("memset(loss)");
-    }
-    if (has_prev)
-      return launch_reduce_partials(deferred->prev_partials,
-                                    deferred->prev_count, deferred->prev_loss, st);
-    return APG_OK;
-  }
-  if (!ref || !loss_partials || !grad_actions) {
-    set_error("ref / loss_partials / grad_actions must not be NULL");
-    return APG_ERR_ARG;
-  }
-  RolloutArgs A;
-  A.state0 = state0, A.actions = actions, A.ref = ref;
-  A.loss_partials = loss_partials, A.grad_actions = grad_actions;
-  A.grad_state0 = grad_state0, A.states_out = states_out;
-  A.c = make_const(*params, dt);
-  A.w = *weights;
-  A.prev = has_prev ? *deferred : ApgDeferredLoss{nullptr, 0, nullptr};
-  A.B = B, A.H = H, A.ref_cols = ref_cols, A.vel_col = ref_cols == 9 ? 6 : 3;
-  int e;
-  if (layout == APG_LAYOUT_PACKED)
-    e = states_out ? launch_rollout_rows<true>(A, st)
-                   : launch_rollout_rows<false>(A, st);
-  else if (layout == APG_LAYOUT_SOA)
-    e = states_out ? launch_rollout<APG_LAYOUT_SOA, true>(A, st)
-                   : launch_rollout<APG_LAYOUT_SOA, false>(A, st);
-  else
-    e = states_out ? launch_rollout<APG_LAYOUT_AOS, true>(A, st)
-                   : launch_rollout<APG_LAYOUT_AOS, false>(A, st);
-  if (e) return e;
-  if (loss) return launch_reduce_partials(loss_partials, apg_loss_partials_count(B), loss, st);
-  return APG_OK;
+  return quad_rollout_fwd_bwd_launch(state0, actions, ref, ref_cols, dt, params,
+                                     weights, B, H, layout, loss_partials, loss,
+                                     grad_actions, grad_state0, states_out,
+                                     deferred, (hipStream_t)stream, false);
 }
 
 int apg_quad_learnt_rollout_fwd_bwd(const float *state0, const float *actions,

@@ -1,5 +1,5 @@
 """Build an experimental variant of libapg_hip.so: quad.hip recompiled with
-extra flags, linked with the other (shipped) objects -> tools/exp/libapg_<name>.so
+the product's flags plus extra ones, linked with the other (shipped) objects -> tools/exp/libapg_<name>.so
     python tools/build_variant.py <name> [-DAPG_QX=5 -DAPG_HW_TRIG ...]
 Also dumps the ISA statistics of the bench kernel instance."""
 import os
@@ -12,7 +12,8 @@ sys.path.insert(0, REPO)
 from apg_trajectory_tracking_amd import build as B  # noqa: E402
 
 KERNELS = ["quad_rollout_reg_kernelILi0ELi10ELb0ELb1E",
-           "quad_rollout_rows_kernelILi10ELb0E"]
+           "quad_rollout_rows_kernelILi10ELb0ELb0E",   # serial launches
+           "quad_rollout_rows_kernelILi10ELb0ELb1E"]   # launches of a chain
 
 
 def main():
@@ -23,7 +24,8 @@ def main():
     src = os.path.join(B.CSRC, "quad.hip")
     obj = os.path.join(out, f"quad_{name}.o")
     base = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17",
-            "-fPIC", *B.COMMON_FLAGS, "-DAPG_EXPERIMENT_BUILD", *flags, "-I",
+            "-fPIC", *B.COMMON_FLAGS, *B.EXTRA_FLAGS.get("quad.hip", []),
+            "-DAPG_EXPERIMENT_BUILD", *flags, "-I",
             os.path.join(REPO, "include"), "-I", B.CSRC]
     subprocess.run(base + ["-c", src, "-o", obj], check=True)
     objs = [os.path.join(B.CSRC, s.replace(".hip", ".o")) for s in B.SOURCES
@@ -52,7 +54,7 @@ def report(name, KERNEL, txt, stderr):
            and not l.strip().startswith((".", ";"))]
     cnt = lambda p: sum(1 for i in ins if re.match(p, i))
     regs = re.search(r"%s.*?VGPRs: (\d+).*?AGPRs: (\d+)" % KERNEL, r.stderr, re.S)
-    print(f"{name} {KERNEL[13:24]}: instr {len(ins)} valu {cnt('v_')} accvgpr {cnt('v_accvgpr')} "
+    print(f"{name} {KERNEL[13:]}: instr {len(ins)} valu {cnt('v_')} accvgpr {cnt('v_accvgpr')} "
           f"trans {cnt('v_(sin|cos|rcp|sqrt|exp|log)')} salu {cnt('s_') - cnt('s_waitcnt')} "
           f"waitcnt {cnt('s_waitcnt')} vmem_ld {cnt('buffer_load')} "
           f"vmem_st {cnt('buffer_store')} ds {cnt('ds_')} "
