@@ -501,6 +501,13 @@ SIGNATURES = {
         _P, _F, ctypes.POINTER(ApgCartpoleParams), ctypes.POINTER(ApgCartpoleLearnt),
         ctypes.POINTER(ApgCartpoleParams), ctypes.POINTER(ApgCartpoleMpcOptions),
         _I, _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "apg_cartpole_learnt_mpc_solve": [
+        _P, _P, _F, ctypes.POINTER(ApgCartpoleLearnt),
+        ctypes.POINTER(ApgCartpoleMpcOptions), _I, _I, _P, _P, _P, _P],
+    "apg_cartpole_learnt_mpc_closed_loop": [
+        _P, _F, ctypes.POINTER(ApgCartpoleParams), ctypes.POINTER(ApgCartpoleLearnt),
+        ctypes.POINTER(ApgCartpoleLearnt), ctypes.POINTER(ApgCartpoleMpcOptions),
+        _I, _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P],
     "apg_launch_chain_prepare": [_P],
     "apg_launch_chain_flush": [_P],
     "apg_launch_chain_set_lane_priority": [_I],

@@ -50,6 +50,10 @@ Two deliberate differences from the reference's NLP follow from that:
     the last stage's state cost (here: the state fading to zero over H rows,
     every row with its cost).
 The solver is the same first-order single shooting (apg_cartpole_mpc_solve).
+`MPC(dynamics="cartpole", learnt_model=m)` plans through a
+LearntCartpoleDynamics module (apg_cartpole_learnt_mpc_solve: the same unwrapped
+step on the module's six live parameters plus its residual); `params` is then
+None - the module has no parameter struct.
 `evaluate_cartpole.Evaluator(MPC(...), env)` flies whole batches of episodes
 with the solver inside the closed-loop kernel
 (functional.cartpole_mpc_closed_loop)."""
@@ -57,7 +61,7 @@ import numpy as np
 import torch
 
 from .. import functional as F
-from ..dynamics.cartpole_dynamics import CartpoleDynamics
+from ..dynamics.cartpole_dynamics import CartpoleDynamics, LearntCartpoleDynamics
 from ..dynamics.quad_dynamics_flightmare import FlightmareDynamics
 
 DYNAMICS = ("flightmare", "cartpole")
@@ -75,10 +79,13 @@ class MPC:
         if horizon not in (5, 10):
             raise ValueError("the batched MPC is built for horizon 5 or 10")
         if learnt_model is not None:
-            if dynamics != "flightmare":
+            cart_module = isinstance(learnt_model, LearntCartpoleDynamics)
+            if cart_module != (dynamics == "cartpole"):
                 raise NotImplementedError(
-                    "learnt_model: the solver plans through a learnt simulator for "
-                    "dynamics='flightmare' only")
+                    "learnt_model: the solver plans through a LearntDynamics module "
+                    "for dynamics='flightmare' and through a LearntCartpoleDynamics "
+                    f"module for dynamics='cartpole' (got {type(learnt_model).__name__} "
+                    f"with dynamics={dynamics!r})")
             if modified_params:
                 raise ValueError(
                     "learnt_model brings its own parameters (the module's): "
@@ -86,7 +93,8 @@ class MPC:
         self.horizon = horizon
         self.dt = dt
         self.dynamics_model = dynamics
-        # a LearntDynamics module: the solver's model is that module
+        # a LearntDynamics / LearntCartpoleDynamics module: the solver's model is
+        # that module
         self.learnt_model = learnt_model
         if dynamics == "cartpole":
             self.model = CartpoleDynamics(modified_params)
@@ -95,7 +103,12 @@ class MPC:
             self.model = FlightmareDynamics(modified_params=modified_params)
             self.options = dict(iters=iters, beta=beta, alpha_thrust=alpha_thrust,
                                 alpha_rate=alpha_rate)
-        self.params = self.model.params if learnt_model is None else learnt_model.params
+        if learnt_model is None:
+            self.params = self.model.params
+        else:
+            # (a LearntCartpoleDynamics has no parameter struct: its parameters
+            # are the module's tensors)
+            self.params = None if dynamics == "cartpole" else learnt_model.params
         self.device = device
         # [B,H,4] ([B,H,1] cart-pole): the previous solution, not yet shifted
         self.warm_start = None
@@ -125,9 +138,10 @@ class MPC:
             s = s[None]
         if s.dim() != 2 or s.shape[1] != 4:
             raise ValueError(f"state [4] or [B,4] expected, got {tuple(s.shape)}")
+        planner = {} if self.learnt_model is None else dict(learnt=self.learnt_model)
         res = F.cartpole_mpc_solve(s, self.dt, self.params,
                                    u0=self._shifted_warm_start(s.shape[0]),
-                                   horizon=self.horizon, **self.options)
+                                   horizon=self.horizon, **self.options, **planner)
         self.warm_start, self.last_cost = res["u"], res["cost"]
         action = res["u"][:, 0]
         return action.cpu().numpy() if numpy_in else action

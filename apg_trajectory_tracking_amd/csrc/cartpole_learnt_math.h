@@ -146,12 +146,15 @@ __host__ __device__ __forceinline__ void cart_residual_unit_grads(const float *w
 
 // One learnt step in place: physics on the live parameters, then the residual
 // (all 64 units) on the PRE-step state and the raw action.  rows NULL: physics
-// only (simulate_cartpole).
+// only (simulate_cartpole).  WRAP = false: the physics' angle is advanced
+// without the atan2 wrap (cart_step<false>: the planning model of
+// cartpole_mpc_math.h); the residual is added to it all the same.
+template <bool WRAP = true>
 __host__ __device__ __forceinline__ CartAux cart_learnt_step(float (&s)[4], float a,
                                                              const CartConst &c,
                                                              const float *rows) {
   const float z[5] = {s[0], s[1], s[2], s[3], a};
-  const CartAux x = cart_step(s, a, c);
+  const CartAux x = cart_step<WRAP>(s, a, c);
   if (rows) {
     float r[4] = {0.f, 0.f, 0.f, 0.f};
     cart_residual_add(r, z, rows, 0, kCartResHidden);

@@ -38,6 +38,23 @@
 //   full-range and swing-up starts, alpha 5e-4: no trajectory ends above its
 //   start cost.
 // 5e-4 is a factor 2-4 below the stability limit.
+//
+// The solver is stated once, generic over the MODEL inside the horizon:
+//   CartMpcAnalytic  cart_step<false> on ApgCartpoleParams' constants
+//   CartMpcLearnt    LearntCartpoleDynamics with the same unwrapped step
+//                    (cart_learnt_step<false>): the physics on the module's six
+//                    live parameters plus W2 relu(W1 [s; a] + b1) on the pre-step
+//                    state and the raw action, added to all four components.
+//                    The role of the reference's LearntDynamicsMPC
+//                    (neural_control/dynamics/learnt_dynamics.py:5-55).
+// A model has step(s, a) -> CartAux, adjoint(lam, pre, a, x) -> dJ/da and
+// kPre: whether the adjoint reads the pre-step x and theta (the residual's
+// hidden layer is recomputed from them in the reverse sweep, by
+// cart_learnt_step_adjoint as the rollout kernels have it); they join the
+// stash then, 14 floats per step instead of 12.  Cost, reference, update rule,
+// box, warm start and defaults are the same for both (float64 restatement with
+// the fitted module of tests/golden/cartpole_learnt.npz, 256 starts in thirds:
+// no trajectory ends above its start cost after 1, 10 or 20 iterations).
 #pragma once
 #include "cart_flight_rule.h"
 #include "cartpole_learnt_math.h"
@@ -47,12 +64,41 @@ namespace {
 
 // what the reverse sweep needs of the forward one, per step: cart_step's aux,
 // the two pre-step velocities and the three weighted residuals (2 w_i d_i for
-// x_dot, theta, theta_dot; the cart position carries no cost) - 12 floats
-template <int H>
+// x_dot, theta, theta_dot; the cart position carries no cost) - 12 floats;
+// PRE: the pre-step x and theta as well
+template <int H, bool PRE>
 struct CartMpcStash {
   CartAux x[H];
   float xd[H], thd[H];
   float seed[H][3];
+  float px[PRE ? H : 1], pth[PRE ? H : 1];
+};
+
+struct CartMpcAnalytic {
+  static constexpr bool kPre = false;
+  CartConst c;
+  __host__ __device__ __forceinline__ CartAux step(float (&s)[4], float a) const {
+    return cart_step<false>(s, a, c);
+  }
+  __host__ __device__ __forceinline__ float adjoint(float (&lam)[4], const float (&pre)[4],
+                                                    float, const CartAux &x) const {
+    return cart_step_adjoint(lam, pre[1], pre[3], x, c);
+  }
+};
+
+// rows: the residual's 640 packed floats (cart_residual_packed; LDS on the
+// device), c: make_learnt_const of the module's six parameters
+struct CartMpcLearnt {
+  static constexpr bool kPre = true;
+  CartConst c;
+  const float *rows;
+  __host__ __device__ __forceinline__ CartAux step(float (&s)[4], float a) const {
+    return cart_learnt_step<false>(s, a, c, rows);
+  }
+  __host__ __device__ __forceinline__ float adjoint(float (&lam)[4], const float (&pre)[4],
+                                                    float a, const CartAux &x) const {
+    return cart_learnt_step_adjoint(lam, pre, a, x, c, rows);
+  }
 };
 
 // make_reference's fade of row k (a compile-time constant once unrolled)
@@ -62,18 +108,19 @@ __host__ __device__ __forceinline__ float cart_mpc_fade(int k) {
 }
 
 // Returns J of the plan u from s0.
-template <int H, bool STASH>
+template <int H, bool STASH, class Model>
 __host__ __device__ __forceinline__ float cart_mpc_forward(const float (&s0)[4],
                                                            const float (&u)[H],
-                                                           const CartConst &c,
-                                                           CartMpcStash<H> &st) {
+                                                           const Model &c,
+                                                           CartMpcStash<H, Model::kPre> &st) {
   const float wq[3] = {3.f, 10.f, 1.f};
   float s[4] = {s0[0], s0[1], s0[2], s0[3]};
   float J = 0.f;
 #pragma unroll
   for (int k = 0; k < H; ++k) {
     if (STASH) st.xd[k] = s[1], st.thd[k] = s[3];
-    const CartAux x = cart_step<false>(s, u[k], c);
+    if (STASH && Model::kPre) st.px[k] = s[0], st.pth[k] = s[2];
+    const CartAux x = c.step(s, u[k]);
     if (STASH) st.x[k] = x;
     const float f = cart_mpc_fade<H>(k);
     float l = 0.f;
@@ -89,16 +136,18 @@ __host__ __device__ __forceinline__ float cart_mpc_forward(const float (&s0)[4],
 }
 
 // reverse sweep + update of u and m
-template <int H>
+template <int H, class Model>
 __host__ __device__ __forceinline__ void cart_mpc_reverse_update(
-    const CartMpcStash<H> &st, float (&u)[H], float (&m)[H], const CartConst &c,
+    const CartMpcStash<H, Model::kPre> &st, float (&u)[H], float (&m)[H], const Model &c,
     const ApgCartpoleMpcOptions &o) {
   float lam[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int k = H - 1; k >= 0; --k) {
 #pragma unroll
     for (int i = 0; i < 3; ++i) lam[1 + i] += st.seed[k][i];
-    const float g = cart_step_adjoint(lam, st.xd[k], st.thd[k], st.x[k], c) + 0.02f * u[k];
+    const float pre[4] = {Model::kPre ? st.px[k] : 0.f, st.xd[k],
+                          Model::kPre ? st.pth[k] : 0.f, st.thd[k]};
+    const float g = c.adjoint(lam, pre, u[k], st.x[k]) + 0.02f * u[k];
     m[k] = o.beta * m[k] + o.alpha * g;
     u[k] = fminf(fmaxf(u[k] - m[k], -1.f), 1.f);
   }
@@ -106,15 +155,15 @@ __host__ __device__ __forceinline__ void cart_mpc_reverse_update(
 
 // o.iters iterations from u (in: start, out: solution); trace(i, J) is called
 // with the cost before iteration i and, for i = iters, with the returned cost
-template <int H, class Trace>
+template <int H, class Model, class Trace>
 __host__ __device__ __forceinline__ float cart_mpc_solve(const float (&s0)[4], float (&u)[H],
-                                                         const CartConst &c,
+                                                         const Model &c,
                                                          const ApgCartpoleMpcOptions &o,
                                                          Trace &&trace) {
   float m[H];
 #pragma unroll
   for (int k = 0; k < H; ++k) m[k] = 0.f;
-  CartMpcStash<H> st;
+  CartMpcStash<H, Model::kPre> st;
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll 1
 #endif
@@ -147,14 +196,15 @@ struct CartMpcFlightLog {
 };
 
 // One closed-loop episode (cart_flight_rule.h) with the controller "shift the
-// warm start, solve on the model `cm`, apply u[0]" (first step: from u = 0).
+// warm start, solve on the model `cm` (CartMpcAnalytic / CartMpcLearnt), apply
+// u[0]" (first step: from u = 0).
 // plant(s, a): the environment's step, before the theta wrap.  The cart
 // position is NOT zeroed between steps (that is Net.forward's side effect in
 // the network controller's loop).  go_on(alive): false ends the loop - the
 // wave's vote on the device, the flight's own flag on the host.
-template <int H, class Plant, class GoOn>
+template <int H, class Plant, class GoOn, class Model>
 __host__ __device__ __forceinline__ CartFlightBook cart_mpc_flight(
-    const float (&s0)[4], Plant &&plant, GoOn &&go_on, const CartConst &cm,
+    const float (&s0)[4], Plant &&plant, GoOn &&go_on, const Model &cm,
     const ApgCartpoleMpcOptions &o, const CartFlightRule &rule, const CartMpcFlightLog &log,
     bool live) {
   float s[4] = {s0[0], s0[1], s0[2], s0[3]}, u[H];
@@ -183,15 +233,26 @@ __host__ __device__ __forceinline__ CartFlightBook cart_mpc_flight(
 }
 
 // argument rules shared by the device entry points and the twins; NULL: fine
-inline const char *cart_mpc_check(const ApgCartpoleParams *model,
-                                  const ApgCartpoleMpcOptions *o, int H) {
-  if (!model) return "model is NULL";
+inline const char *cart_mpc_check_options(const ApgCartpoleMpcOptions *o, int H) {
   if (!o) return "options is NULL";
   if (o->iters < 0 || o->iters > 100000) return "iters must be in [0, 100000]";
   if (!(o->beta >= 0.f && o->beta < 1.f)) return "beta must be in [0, 1)";
   if (!(o->alpha > 0.f)) return "alpha must be positive";
   if (H != 5 && H != 10) return "H must be 5 or 10";
   return nullptr;
+}
+
+inline const char *cart_mpc_check(const ApgCartpoleParams *model,
+                                  const ApgCartpoleMpcOptions *o, int H) {
+  if (!model) return "model is NULL";
+  return cart_mpc_check_options(o, H);
+}
+
+// the learnt model: its residual must be given
+inline const char *cart_mpc_check(const ApgCartpoleLearnt *model,
+                                  const ApgCartpoleMpcOptions *o, int H) {
+  if (const char *e = cart_learnt_check(model, true)) return e;
+  return cart_mpc_check_options(o, H);
 }
 
 // the optional learnt plant: NULL is "none", a given one carries its residual

@@ -1130,11 +1130,12 @@ int apg_quad_learnt_mpc_closed_loop_cpu(const ApgQuadFlight *flight, float dt,
 
 // ------------------------------------------------- shooting MPC, cart-pole
 // apg_cpu_mpc.h: the solver and the flight of cartpole_mpc_math.h looped over
-// the batch
+// the batch, on the analytic model (CartMpcAnalytic) and on the learnt one
+// (CartMpcLearnt)
 namespace {
 
-template <int H>
-void cart_mpc_solve_batch(const float *state0, const float *u0, const CartConst &c,
+template <int H, class Model>
+void cart_mpc_solve_batch(const float *state0, const float *u0, const Model &c,
                           const ApgCartpoleMpcOptions &o, int B, float *u, float *cost_out,
                           float *cost_trace) {
   const size_t Bs = (size_t)B;
@@ -1151,12 +1152,29 @@ void cart_mpc_solve_batch(const float *state0, const float *u0, const CartConst 
   }
 }
 
-template <int H>
+template <class Model>
+int cart_mpc_solve_twin(const float *state0, const float *u0, const Model &c,
+                        const ApgCartpoleMpcOptions &o, int B, int H, float *u,
+                        float *cost_out, float *cost_trace) {
+  if (B == 0) return APG_OK;
+  if (!state0) return fail("state0 is NULL");
+  if (H == 5)
+    cart_mpc_solve_batch<5>(state0, u0, c, o, B, u, cost_out, cost_trace);
+  else
+    cart_mpc_solve_batch<10>(state0, u0, c, o, B, u, cost_out, cost_trace);
+  return APG_OK;
+}
+
+struct CartLoopOut {
+  int *steps, *upright;
+  double *vel_sum, *vel_sq;
+  float *states, *actions, *cost;
+};
+
+template <int H, class Model>
 void cart_mpc_loop_batch(const float *state0, const CartConst &cp, const float *rows,
-                         const CartConst &cm, const ApgCartpoleMpcOptions &o,
-                         const CartFlightRule &rule, int B, int *steps, int *upright,
-                         double *vel_sum, double *vel_sq, float *states, float *actions,
-                         float *cost) {
+                         const Model &cm, const ApgCartpoleMpcOptions &o,
+                         const CartFlightRule &rule, int B, const CartLoopOut &out) {
   const size_t Bs = (size_t)B;
   for (size_t b = 0; b < Bs; ++b) {
     float s0[4];
@@ -1164,10 +1182,39 @@ void cart_mpc_loop_batch(const float *state0, const CartConst &cp, const float *
     const CartFlightBook f = cart_mpc_flight<H>(
         s0, [&](float (&s)[4], float a) { cart_learnt_step(s, a, cp, rows); },
         [](bool alive) { return alive; }, cm, o, rule,
-        CartMpcFlightLog{states, actions, cost, Bs, b}, true);
-    steps[b] = f.steps, upright[b] = f.upright ? 1 : 0;
-    vel_sum[b] = f.vel_sum, vel_sq[b] = f.vel_sq;
+        CartMpcFlightLog{out.states, out.actions, out.cost, Bs, b}, true);
+    out.steps[b] = f.steps, out.upright[b] = f.upright ? 1 : 0;
+    out.vel_sum[b] = f.vel_sum, out.vel_sq[b] = f.vel_sq;
   }
+}
+
+// the closed loop behind both twins, after the model's own check: the plant's
+// checks and setup, then the flights on the model `cm`
+template <class Model>
+int cart_mpc_loop_twin(const float *state0, float dt, const ApgCartpoleParams *plant,
+                       const ApgCartpoleLearnt *plant_learnt, const Model &cm,
+                       const ApgCartpoleMpcOptions &o, int B, int H, int max_steps, int mode,
+                       float thresh_div, int burn_in, const CartLoopOut &out) {
+  if (!plant && !plant_learnt) return fail("plant is NULL");
+  if (const char *e = cart_mpc_check_learnt(plant_learnt)) return fail("%s", e);
+  if (const char *e = cart_flight_check(B, max_steps, mode)) return fail("%s", e);
+  if (!state0 || !out.steps || !out.upright || !out.vel_sum || !out.vel_sq)
+    return fail("NULL buffer");
+  CartConst cp;
+  std::vector<float> rows;
+  if (plant_learnt) {
+    CartLearntParams p;
+    learnt_setup(*plant_learnt, dt, p, cp, rows);
+  } else {
+    cp = make_const(*plant, dt);
+  }
+  const float *r = plant_learnt ? rows.data() : nullptr;   // NULL: cart_step alone
+  const CartFlightRule rule{max_steps, mode, burn_in, thresh_div};
+  if (H == 5)
+    cart_mpc_loop_batch<5>(state0, cp, r, cm, o, rule, B, out);
+  else
+    cart_mpc_loop_batch<10>(state0, cp, r, cm, o, rule, B, out);
+  return APG_OK;
 }
 
 }  // namespace
@@ -1180,14 +1227,8 @@ int apg_cartpole_mpc_solve_cpu(const float *state0, const float *u0, float dt,
                                float *cost_out, float *cost_trace) {
   if (B < 0) return fail("B must be >= 0 (got %d)", B);
   if (const char *e = cart_mpc_check(model, opt, H)) return fail("%s", e);
-  if (B == 0) return APG_OK;
-  if (!state0) return fail("state0 is NULL");
-  const CartConst c = make_const(*model, dt);
-  if (H == 5)
-    cart_mpc_solve_batch<5>(state0, u0, c, *opt, B, u, cost_out, cost_trace);
-  else
-    cart_mpc_solve_batch<10>(state0, u0, c, *opt, B, u, cost_out, cost_trace);
-  return APG_OK;
+  return cart_mpc_solve_twin(state0, u0, CartMpcAnalytic{make_const(*model, dt)}, *opt, B, H,
+                             u, cost_out, cost_trace);
 }
 
 int apg_cartpole_mpc_closed_loop_cpu(const float *state0, float dt,
@@ -1200,28 +1241,43 @@ int apg_cartpole_mpc_closed_loop_cpu(const float *state0, float dt,
                                      double *vel_sq, float *states, float *actions,
                                      float *cost) {
   if (const char *e = cart_mpc_check(model, opt, H)) return fail("%s", e);
-  if (!plant && !plant_learnt) return fail("plant is NULL");
-  if (const char *e = cart_mpc_check_learnt(plant_learnt)) return fail("%s", e);
-  if (const char *e = cart_flight_check(B, max_steps, mode)) return fail("%s", e);
-  if (!state0 || !steps || !upright || !vel_sum || !vel_sq) return fail("NULL buffer");
-  CartConst cp;
+  return cart_mpc_loop_twin(state0, dt, plant, plant_learnt,
+                            CartMpcAnalytic{make_const(*model, dt)}, *opt, B, H, max_steps,
+                            mode, thresh_div, burn_in,
+                            CartLoopOut{steps, upright, vel_sum, vel_sq, states, actions, cost});
+}
+
+int apg_cartpole_learnt_mpc_solve_cpu(const float *state0, const float *u0, float dt,
+                                      const ApgCartpoleLearnt *model,
+                                      const ApgCartpoleMpcOptions *opt, int B, int H, float *u,
+                                      float *cost_out, float *cost_trace) {
+  if (B < 0) return fail("B must be >= 0 (got %d)", B);
+  if (const char *e = cart_mpc_check(model, opt, H)) return fail("%s", e);
+  CartLearntParams p;
+  CartConst c;
   std::vector<float> rows;
-  if (plant_learnt) {
-    CartLearntParams p;
-    learnt_setup(*plant_learnt, dt, p, cp, rows);
-  } else {
-    cp = make_const(*plant, dt);
-  }
-  const float *r = plant_learnt ? rows.data() : nullptr;   // NULL: cart_step alone
-  const CartConst cm = make_const(*model, dt);
-  const CartFlightRule rule{max_steps, mode, burn_in, thresh_div};
-  if (H == 5)
-    cart_mpc_loop_batch<5>(state0, cp, r, cm, *opt, rule, B, steps, upright, vel_sum, vel_sq,
-                           states, actions, cost);
-  else
-    cart_mpc_loop_batch<10>(state0, cp, r, cm, *opt, rule, B, steps, upright, vel_sum, vel_sq,
-                            states, actions, cost);
-  return APG_OK;
+  learnt_setup(*model, dt, p, c, rows);
+  return cart_mpc_solve_twin(state0, u0, CartMpcLearnt{c, rows.data()}, *opt, B, H, u,
+                             cost_out, cost_trace);
+}
+
+int apg_cartpole_learnt_mpc_closed_loop_cpu(const float *state0, float dt,
+                                            const ApgCartpoleParams *plant,
+                                            const ApgCartpoleLearnt *plant_learnt,
+                                            const ApgCartpoleLearnt *model,
+                                            const ApgCartpoleMpcOptions *opt, int B, int H,
+                                            int max_steps, int mode, float thresh_div,
+                                            int burn_in, int *steps, int *upright,
+                                            double *vel_sum, double *vel_sq, float *states,
+                                            float *actions, float *cost) {
+  if (const char *e = cart_mpc_check(model, opt, H)) return fail("%s", e);
+  CartLearntParams p;
+  CartConst c;
+  std::vector<float> rows;
+  learnt_setup(*model, dt, p, c, rows);
+  return cart_mpc_loop_twin(state0, dt, plant, plant_learnt, CartMpcLearnt{c, rows.data()},
+                            *opt, B, H, max_steps, mode, thresh_div, burn_in,
+                            CartLoopOut{steps, upright, vel_sum, vel_sq, states, actions, cost});
 }
 
 }  // extern "C"

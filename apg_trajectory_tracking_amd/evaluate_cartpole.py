@@ -18,7 +18,9 @@ comparison (`eval_dyn`) here.
 With a `controllers.MPC(dynamics="cartpole")` controller - the comparator of
 scripts/evaluate_cartpole.py:399-407 - the same Evaluator flies the batch with
 the solver inside the kernel (apg_cartpole_mpc_closed_loop): the plant is the
-environment's dynamics, the model the MPC object's parameters."""
+environment's dynamics, the model the MPC object's parameters - or, with
+`MPC(dynamics="cartpole", learnt_model=m)`, the module `m`
+(apg_cartpole_learnt_mpc_closed_loop)."""
 import numpy as np
 import torch
 
@@ -155,12 +157,14 @@ class Evaluator:
         learnt = _is_learnt(env.dynamics)
         dev = torch.device(mpc.device or (
             next(env.dynamics.parameters()).device if learnt else "cuda"))
+        # MPC(learnt_model=m): the solver plans through the module
+        planner = {} if mpc.learnt_model is None else dict(model_learnt=mpc.learnt_model)
         out = F.cartpole_mpc_closed_loop(
             torch.from_numpy(starts).to(dev), env.dt,
             None if learnt else env.dynamics.params, model_params=mpc.params,
             learnt=env.dynamics if learnt else None, max_steps=max_steps, mode=mode,
             thresh_div=env.thresh_div, burn_in=burn_in, want_trajectory=True,
-            horizon=mpc.horizon, **mpc.options)
+            horizon=mpc.horizon, **mpc.options, **planner)
         self.last_flights = out
         return out
 

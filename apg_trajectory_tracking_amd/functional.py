@@ -2373,13 +2373,17 @@ def cartpole_mpc_options(iters=None, beta=None, alpha=None):
 
 
 def cartpole_mpc_solve(state0, dt, params, u0=None, horizon=10, iters=None, beta=None,
-                       alpha=None, want_trace=False):
+                       alpha=None, want_trace=False, learnt=None):
     """One shooting-MPC solve per trajectory in one launch
     (apg_cartpole_mpc_solve): `iters` iterations of projected heavy-ball descent
     on the training loss (cartpole_loss_mpc against make_reference(state0)) of
     the `horizon`-step unroll of the model `params` from state0 [B,4], the
     angle advanced without the atan2 wrap, actions boxed to [-1, 1].  u0
     [B,H,1]: the start (None: 0); it is not written.  horizon = 5 or 10.
+    `learnt`: a LearntCartpoleDynamics module on the device - the solver plans
+    through it (apg_cartpole_learnt_mpc_solve: the same unwrapped step on the
+    module's six live parameters plus its residual, read on the device when the
+    kernel runs); `params` is then not read and may be None.
     Returns dict(u [B,H,1], cost [B] = the cost of u, trace [iters+1,B] with
     want_trace: the cost before every iteration and at the end, else None)."""
     if state0.dim() != 2 or state0.shape[1] != 4:
@@ -2396,23 +2400,32 @@ def cartpole_mpc_solve(state0, dt, params, u0=None, horizon=10, iters=None, beta
     cost = torch.empty(B, dtype=torch.float32, device=dev)
     trace = (torch.empty(opt.iters + 1, B, dtype=torch.float32, device=dev)
              if want_trace else None)
-    check(lib().apg_cartpole_mpc_solve(
-        ptr(s), ptr(start), float(dt), ctypes.byref(params), ctypes.byref(opt), B, H,
-        ptr(u), ptr(cost), ptr(trace), stream_of(s)), "apg_cartpole_mpc_solve")
+    if learnt is None:
+        name, model = "apg_cartpole_mpc_solve", params
+    else:
+        name = "apg_cartpole_learnt_mpc_solve"
+        tensors = _cartpole_learnt_tensors(learnt)       # (kept alive to the launch)
+        model = _cartpole_learnt_model(tensors)
+    check(getattr(lib(), name)(
+        ptr(s), ptr(start), float(dt), ctypes.byref(model), ctypes.byref(opt), B, H,
+        ptr(u), ptr(cost), ptr(trace), stream_of(s)), name)
     return dict(u=u.t().contiguous()[:, :, None], cost=cost, trace=trace)
 
 
 def cartpole_mpc_closed_loop(state0, dt, params, model_params=None, learnt=None,
                              max_steps=250, mode="balance", thresh_div=0.21, burn_in=50,
-                             want_trajectory=False, **options):
+                             want_trajectory=False, model_learnt=None, **options):
     """cartpole_mlp_closed_loop with the policy replaced by the shooting MPC:
     per control step "shift the warm start, solve, apply u[0]", every episode
     of the batch in one launch (apg_cartpole_mpc_closed_loop).  `params` (or
     `learnt`, a LearntCartpoleDynamics module; `params` is then not read) steps
     the environment; `model_params` is what the solver plans with (None:
     `params` - the nominal case; other parameters: the model-mismatch
-    experiment; required with `learnt`).  options: horizon (5 or 10, default
-    10), iters, beta, alpha.  The cart position is not zeroed between steps.
+    experiment; required with `learnt`) - or `model_learnt`, a
+    LearntCartpoleDynamics module the solver plans THROUGH
+    (apg_cartpole_learnt_mpc_closed_loop; `model_params` is then not required);
+    `learnt` stays the plant: the same module, another one, or None with
+    `params`.  options: horizon (5 or 10, default 10), iters, beta, alpha.  The cart position is not zeroed between steps.
     Returns the dict cartpole_mlp_closed_loop returns, plus cost [T,B]: the
     solver's cost at every control step."""
     horizon = int(options.pop("horizon", 10))
@@ -2425,9 +2438,15 @@ def cartpole_mpc_closed_loop(state0, dt, params, model_params=None, learnt=None,
     B, T = state0.shape[0], int(max_steps)
     if T < 1:
         raise ValueError(f"max_steps must be >= 1, got {T}")
-    model = params if model_params is None else model_params
-    if model is None:
-        raise ValueError("model_params is required when the plant is a learnt module")
+    if model_learnt is not None:
+        name = "apg_cartpole_learnt_mpc_closed_loop"
+        model_tensors = _cartpole_learnt_tensors(model_learnt)
+        model = _cartpole_learnt_model(model_tensors)
+    else:
+        name = "apg_cartpole_mpc_closed_loop"
+        model = params if model_params is None else model_params
+        if model is None:
+            raise ValueError("model_params is required when the plant is a learnt module")
     dev = state0.device
     s0 = _f32c(state0).t().contiguous()
     require_device(s0)
@@ -2441,34 +2460,38 @@ def cartpole_mpc_closed_loop(state0, dt, params, model_params=None, learnt=None,
         states = torch.zeros(T, 4, B, dtype=torch.float32, device=dev)
         actions = torch.zeros(T, B, dtype=torch.float32, device=dev)
     env = None
+    if learnt is None and params is None:
+        raise ValueError("params (or a learnt plant module) is required")
     if learnt is not None:
         tensors = _cartpole_learnt_tensors(learnt)       # (kept alive to the launch)
         env = ctypes.byref(_cartpole_learnt_model(tensors))
-    check(lib().apg_cartpole_mpc_closed_loop(
+    check(getattr(lib(), name)(
         ptr(s0), float(dt), None if learnt is not None else ctypes.byref(params), env,
         ctypes.byref(model), ctypes.byref(opt), B, horizon, T, m, float(thresh_div),
         int(burn_in), steps.data_ptr(), upright.data_ptr(), vel_sum.data_ptr(),
-        vel_sq.data_ptr(), ptr(states), ptr(actions), ptr(cost), stream_of(s0)),
-        "apg_cartpole_mpc_closed_loop")
+        vel_sq.data_ptr(), ptr(states), ptr(actions), ptr(cost), stream_of(s0)), name)
     out = dict(steps=steps, upright=upright, vel_sum=vel_sum, vel_sq=vel_sq, cost=cost)
     if want_trajectory:
         out.update(states=states, actions=actions)
     return out
 
 
-def cartpole_policy_optimality_gap(net, state0, dt, params, iters=50):
+def cartpole_policy_optimality_gap(net, state0, dt, params, iters=50, learnt=None):
     """How far is a cart-pole policy from what the optimiser reaches from the
     same states, on the same cost and the same model?  Per trajectory: the cost
     of the policy's plan - net(state0) reshaped to [B,H,1] - the MPC cost after
     `iters` iterations started AT that plan, and the MPC cost after `iters`
     iterations from u = 0.  All three are evaluated on the solver's UNWRAPPED
     model (theta + dt theta_dot): the "policy cost" equals the training loss
-    (cartpole_rollout_loss) only for windows that do not cross +-pi.  Returns
-    dict(policy [B], mpc_from_policy [B], mpc [B], actions [B,H,1])."""
+    (cartpole_rollout_loss) only for windows that do not cross +-pi.  `learnt`:
+    a LearntCartpoleDynamics module - all three costs are taken on the learnt
+    model (the model an adapted policy was trained through); `params` is then
+    not read.  Returns dict(policy [B], mpc_from_policy [B], mpc [B], actions
+    [B,H,1])."""
     H = net.fc_out.weight.shape[0]
     with torch.no_grad():
         acts = net(_f32c(state0).clone()).reshape(-1, H, 1).contiguous()
-    kw = dict(horizon=H)
+    kw = dict(horizon=H) if learnt is None else dict(horizon=H, learnt=learnt)
     policy = cartpole_mpc_solve(state0, dt, params, u0=acts, iters=0, **kw)["cost"]
     warm = cartpole_mpc_solve(state0, dt, params, u0=acts, iters=iters, **kw)["cost"]
     cold = cartpole_mpc_solve(state0, dt, params, iters=iters, **kw)["cost"]

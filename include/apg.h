@@ -1523,6 +1523,34 @@ int apg_cartpole_mpc_closed_loop(const float *state0, float dt, const ApgCartpol
                                  int *upright, double *vel_sum, double *vel_sq, float *states,
                                  float *actions, float *cost, apg_stream_t stream);
 
+/* The same solver planning through the LEARNT simulator - the role of the
+ * reference's LearntDynamicsMPC (neural_control/dynamics/learnt_dynamics.py:
+ * 5-55): MPC with the adapted model.  Inside the horizon the model is
+ *   s' = step(s, a) + W2 relu(W1 [s; a] + b1)
+ * with `step` the unwrapped step above (theta + dt theta_dot) on constants
+ * built from the module's six live parameters, the residual evaluated on the
+ * pre-step state and the raw action and added to all four components, theta
+ * included.  Cost, reference, update rule, box and warm start are those of
+ * apg_cartpole_mpc_solve; layouts and NULL rules are those of the two entry
+ * points above.  `model` holds DEVICE pointers to the module's tensors, read
+ * inside the kernel when it runs (no device-to-host read; a captured launch
+ * sees the values of the moment it is replayed); its residual must be given.
+ * In the closed loop the plant is `plant`, or `plant_learnt` (the same module as
+ * `model` or another one) as above. */
+int apg_cartpole_learnt_mpc_solve(const float *state0, const float *u0, float dt,
+                                  const ApgCartpoleLearnt *model,
+                                  const ApgCartpoleMpcOptions *opt, int B, int H, float *u,
+                                  float *cost_out, float *cost_trace, apg_stream_t stream);
+int apg_cartpole_learnt_mpc_closed_loop(const float *state0, float dt,
+                                        const ApgCartpoleParams *plant,
+                                        const ApgCartpoleLearnt *plant_learnt,
+                                        const ApgCartpoleLearnt *model,
+                                        const ApgCartpoleMpcOptions *opt, int B, int H,
+                                        int max_steps, int mode, float thresh_div, int burn_in,
+                                        int *steps, int *upright, double *vel_sum,
+                                        double *vel_sq, float *states, float *actions,
+                                        float *cost, apg_stream_t stream);
+
 /* ------------------------------------------------------- launch chain --- */
 /* A chain of deferred-loss rollout launches run as TWO overlapping lanes.
  * Launched one `after` the other through the entry points above, kernel i+1
