@@ -15,12 +15,10 @@
 // device tensors here - no device-to-host read, a captured launch sees the
 // values of the moment it is replayed.  The stash grows by the pre-step x and
 // theta (14 H floats): still no scratch and no spill
-// (tests/test_cartpole_learnt_mpc_cpu.py).  Their names carry neither
-// "cart_mpc_solve_kernel" / "cart_mpc_closed_loop_kernel" nor "cart_learnt": the
-// resource tests of the analytic solver and of cartpole_learnt.hip count their
-// kernels by those substrings.
+// (tests/test_cartpole_learnt_mpc_cpu.py).
 #include "cartpole_learnt_stage.h"
 #include "cartpole_mpc_math.h"
+#include "static_dispatch.h"
 
 namespace apg {
 namespace {
@@ -127,12 +125,11 @@ __global__ __launch_bounds__(kCartMpcThreads) void cart_mpc_closed_loop_kernel(C
   __shared__ float rows[LEARNT ? kCartResFloats : 1];
   CartConst cp = A.cp;
   if constexpr (LEARNT) {
+    // (the plant's rows by a loop of the compile-time stride, here and below:
+    // stage_residual strides by blockDim.x and compiles to other instructions)
     for (int t = threadIdx.x; t < kCartResFloats; t += kCartMpcThreads)
       rows[t] = cart_residual_packed(t, A.m.w1, A.m.b1, A.m.w2);
-    cp = make_learnt_const(CartLearntParams{*A.m.max_force_mag, *A.m.masspole, *A.m.length,
-                                            *A.m.friction, *A.m.total_mass,
-                                            *A.m.polemass_length},
-                           A.cp.dt);
+    cp = make_learnt_const(load_params(A.m), A.cp.dt);
     __syncthreads();
   }
   cart_mpc_loop_lane<H>(
@@ -187,6 +184,86 @@ int fail_arg(const char *e) {
   return APG_ERR_ARG;
 }
 
+// the solver's model into a kernel's arguments: the analytic one as its
+// constants, the learnt one as the module's tensors and dt
+void set_model(CartMpcSolveArgs &A, const ApgCartpoleParams &m, float dt) {
+  A.c = make_const(m, dt);
+}
+void set_model(CartMpcLoopArgs &A, const ApgCartpoleParams &m, float dt) {
+  A.cm = make_const(m, dt);
+}
+template <class Args>
+void set_model(Args &A, const ApgCartpoleLearnt &m, float dt) {
+  A.model = m, A.dt = dt;
+}
+
+// The solve behind both entry points; Args / Model: CartMpcSolveArgs with the
+// analytic model's parameters, CartLearntMpcSolveArgs with a learnt module.
+template <class Args, class Model>
+int cart_mpc_solve_launch(const char *name, const float *state0, const float *u0, float dt,
+                          const Model *model, const ApgCartpoleMpcOptions *opt, int B, int H,
+                          float *u, float *cost_out, float *cost_trace, apg_stream_t stream) {
+  if (B < 0) return fail_arg("B must be >= 0");
+  if (const char *e = cart_mpc_check(model, opt, H)) return fail_arg(e);
+  if (B == 0) return APG_OK;
+  if (!state0) return fail_arg("state0 is NULL");
+  Args A;
+  A.state0 = state0, A.u0 = u0, A.u = u, A.cost_out = cost_out, A.cost_trace = cost_trace;
+  set_model(A, *model, dt);
+  A.o = *opt, A.B = B;
+  const dim3 grid((B + kCartMpcThreads - 1) / kCartMpcThreads), block(kCartMpcThreads);
+  hipStream_t st = (hipStream_t)stream;
+  with_horizon(H, [&](auto h) {
+    if constexpr (std::is_same<Model, ApgCartpoleLearnt>::value)
+      hipLaunchKernelGGL(cart_mpc_learnt_solve_kernel<h()>, grid, block, 0, st, A);
+    else
+      hipLaunchKernelGGL(cart_mpc_solve_kernel<h()>, grid, block, 0, st, A);
+  });
+  return check_launch(name);
+}
+
+// The closed loop behind both entry points, Args / Model as above.
+template <class Args, class Model>
+int cart_mpc_loop_launch(const char *name, const float *state0, float dt,
+                         const ApgCartpoleParams *plant, const ApgCartpoleLearnt *plant_learnt,
+                         const Model *model, const ApgCartpoleMpcOptions *opt, int B, int H,
+                         int max_steps, int mode, float thresh_div, int burn_in, int *steps,
+                         int *upright, double *vel_sum, double *vel_sq, float *states,
+                         float *actions, float *cost, apg_stream_t stream) {
+  if (const char *e = cart_mpc_check(model, opt, H)) return fail_arg(e);
+  if (!plant && !plant_learnt) return fail_arg("plant is NULL");
+  if (const char *e = cart_mpc_check_learnt(plant_learnt)) return fail_arg(e);
+  if (const char *e = cart_flight_check(B, max_steps, mode)) return fail_arg(e);
+  if (!state0 || !steps || !upright || !vel_sum || !vel_sq) return fail_arg("NULL buffer");
+  Args A = {};
+  A.state0 = state0, A.steps = steps, A.upright = upright;
+  A.vel_sum = vel_sum, A.vel_sq = vel_sq;
+  A.log = {states, actions, cost, 0, 0};
+  if (plant_learnt) {
+    A.m = *plant_learnt;
+    A.cp.dt = dt;          // (the rest is built in the kernel from the tensors)
+  } else {
+    A.cp = make_const(*plant, dt);
+  }
+  set_model(A, *model, dt);
+  A.o = *opt, A.B = B;
+  A.rule = CartFlightRule{max_steps, mode, burn_in, thresh_div};
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((B + kCartMpcThreads - 1) / kCartMpcThreads), block(kCartMpcThreads);
+  with_horizon(H, [&](auto h) {
+    with_flag(plant_learnt != nullptr, [&](auto learnt_plant) {
+      constexpr int kH = decltype(h)::value;
+      constexpr bool kPlant = decltype(learnt_plant)::value;
+      if constexpr (std::is_same<Model, ApgCartpoleLearnt>::value)
+        hipLaunchKernelGGL((cart_mpc_learnt_closed_loop_kernel<kH, kPlant>), grid, block, 0, st,
+                           A);
+      else
+        hipLaunchKernelGGL((cart_mpc_closed_loop_kernel<kH, kPlant>), grid, block, 0, st, A);
+    });
+  });
+  return check_launch(name);
+}
+
 }  // namespace
 }  // namespace apg
 
@@ -198,21 +275,8 @@ int apg_cartpole_mpc_solve(const float *state0, const float *u0, float dt,
                            const ApgCartpoleParams *model, const ApgCartpoleMpcOptions *opt,
                            int B, int H, float *u, float *cost_out, float *cost_trace,
                            apg_stream_t stream) {
-  if (B < 0) return fail_arg("B must be >= 0");
-  if (const char *e = cart_mpc_check(model, opt, H)) return fail_arg(e);
-  if (B == 0) return APG_OK;
-  if (!state0) return fail_arg("state0 is NULL");
-  CartMpcSolveArgs A;
-  A.state0 = state0, A.u0 = u0, A.u = u, A.cost_out = cost_out, A.cost_trace = cost_trace;
-  A.c = make_const(*model, dt);
-  A.o = *opt, A.B = B;
-  const dim3 grid((B + kCartMpcThreads - 1) / kCartMpcThreads);
-  hipStream_t st = (hipStream_t)stream;
-  if (H == 5)
-    hipLaunchKernelGGL(cart_mpc_solve_kernel<5>, grid, dim3(kCartMpcThreads), 0, st, A);
-  else
-    hipLaunchKernelGGL(cart_mpc_solve_kernel<10>, grid, dim3(kCartMpcThreads), 0, st, A);
-  return check_launch("cartpole_mpc_solve");
+  return cart_mpc_solve_launch<CartMpcSolveArgs>("cartpole_mpc_solve", state0, u0, dt, model,
+                                                 opt, B, H, u, cost_out, cost_trace, stream);
 }
 
 int apg_cartpole_mpc_closed_loop(const float *state0, float dt, const ApgCartpoleParams *plant,
@@ -222,59 +286,18 @@ int apg_cartpole_mpc_closed_loop(const float *state0, float dt, const ApgCartpol
                                  int mode, float thresh_div, int burn_in, int *steps,
                                  int *upright, double *vel_sum, double *vel_sq, float *states,
                                  float *actions, float *cost, apg_stream_t stream) {
-  if (const char *e = cart_mpc_check(model, opt, H)) return fail_arg(e);
-  if (!plant && !plant_learnt) return fail_arg("plant is NULL");
-  if (const char *e = cart_mpc_check_learnt(plant_learnt)) return fail_arg(e);
-  if (const char *e = cart_flight_check(B, max_steps, mode)) return fail_arg(e);
-  if (!state0 || !steps || !upright || !vel_sum || !vel_sq) return fail_arg("NULL buffer");
-  CartMpcLoopArgs A = {};
-  A.state0 = state0, A.steps = steps, A.upright = upright;
-  A.vel_sum = vel_sum, A.vel_sq = vel_sq;
-  A.log = {states, actions, cost, 0, 0};
-  if (plant_learnt) {
-    A.m = *plant_learnt;
-    A.cp.dt = dt;          // (the rest is built in the kernel from the tensors)
-  } else {
-    A.cp = make_const(*plant, dt);
-  }
-  A.cm = make_const(*model, dt);
-  A.o = *opt, A.B = B;
-  A.rule = CartFlightRule{max_steps, mode, burn_in, thresh_div};
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((B + kCartMpcThreads - 1) / kCartMpcThreads), block(kCartMpcThreads);
-  if (H == 5) {
-    if (plant_learnt)
-      hipLaunchKernelGGL((cart_mpc_closed_loop_kernel<5, true>), grid, block, 0, st, A);
-    else
-      hipLaunchKernelGGL((cart_mpc_closed_loop_kernel<5, false>), grid, block, 0, st, A);
-  } else {
-    if (plant_learnt)
-      hipLaunchKernelGGL((cart_mpc_closed_loop_kernel<10, true>), grid, block, 0, st, A);
-    else
-      hipLaunchKernelGGL((cart_mpc_closed_loop_kernel<10, false>), grid, block, 0, st, A);
-  }
-  return check_launch("cartpole_mpc_closed_loop");
+  return cart_mpc_loop_launch<CartMpcLoopArgs>(
+      "cartpole_mpc_closed_loop", state0, dt, plant, plant_learnt, model, opt, B, H, max_steps,
+      mode, thresh_div, burn_in, steps, upright, vel_sum, vel_sq, states, actions, cost, stream);
 }
 
 int apg_cartpole_learnt_mpc_solve(const float *state0, const float *u0, float dt,
                                   const ApgCartpoleLearnt *model,
                                   const ApgCartpoleMpcOptions *opt, int B, int H, float *u,
                                   float *cost_out, float *cost_trace, apg_stream_t stream) {
-  if (B < 0) return fail_arg("B must be >= 0");
-  if (const char *e = cart_mpc_check(model, opt, H)) return fail_arg(e);
-  if (B == 0) return APG_OK;
-  if (!state0) return fail_arg("state0 is NULL");
-  CartLearntMpcSolveArgs A;
-  A.state0 = state0, A.u0 = u0, A.u = u, A.cost_out = cost_out, A.cost_trace = cost_trace;
-  A.model = *model, A.dt = dt;
-  A.o = *opt, A.B = B;
-  const dim3 grid((B + kCartMpcThreads - 1) / kCartMpcThreads);
-  hipStream_t st = (hipStream_t)stream;
-  if (H == 5)
-    hipLaunchKernelGGL(cart_mpc_learnt_solve_kernel<5>, grid, dim3(kCartMpcThreads), 0, st, A);
-  else
-    hipLaunchKernelGGL(cart_mpc_learnt_solve_kernel<10>, grid, dim3(kCartMpcThreads), 0, st, A);
-  return check_launch("cartpole_learnt_mpc_solve");
+  return cart_mpc_solve_launch<CartLearntMpcSolveArgs>("cartpole_learnt_mpc_solve", state0, u0,
+                                                       dt, model, opt, B, H, u, cost_out,
+                                                       cost_trace, stream);
 }
 
 int apg_cartpole_learnt_mpc_closed_loop(const float *state0, float dt,
@@ -286,35 +309,10 @@ int apg_cartpole_learnt_mpc_closed_loop(const float *state0, float dt,
                                         int *steps, int *upright, double *vel_sum,
                                         double *vel_sq, float *states, float *actions,
                                         float *cost, apg_stream_t stream) {
-  if (const char *e = cart_mpc_check(model, opt, H)) return fail_arg(e);
-  if (!plant && !plant_learnt) return fail_arg("plant is NULL");
-  if (const char *e = cart_mpc_check_learnt(plant_learnt)) return fail_arg(e);
-  if (const char *e = cart_flight_check(B, max_steps, mode)) return fail_arg(e);
-  if (!state0 || !steps || !upright || !vel_sum || !vel_sq) return fail_arg("NULL buffer");
-  CartLearntMpcLoopArgs A = {};
-  A.state0 = state0, A.steps = steps, A.upright = upright;
-  A.vel_sum = vel_sum, A.vel_sq = vel_sq;
-  A.log = {states, actions, cost, 0, 0};
-  if (plant_learnt) A.m = *plant_learnt;
-  else A.cp = make_const(*plant, dt);
-  A.model = *model, A.dt = dt;
-  A.o = *opt, A.B = B;
-  A.rule = CartFlightRule{max_steps, mode, burn_in, thresh_div};
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((B + kCartMpcThreads - 1) / kCartMpcThreads), block(kCartMpcThreads);
-  if (H == 5) {
-    if (plant_learnt)
-      hipLaunchKernelGGL((cart_mpc_learnt_closed_loop_kernel<5, true>), grid, block, 0, st, A);
-    else
-      hipLaunchKernelGGL((cart_mpc_learnt_closed_loop_kernel<5, false>), grid, block, 0, st, A);
-  } else {
-    if (plant_learnt)
-      hipLaunchKernelGGL((cart_mpc_learnt_closed_loop_kernel<10, true>), grid, block, 0, st, A);
-    else
-      hipLaunchKernelGGL((cart_mpc_learnt_closed_loop_kernel<10, false>), grid, block, 0, st,
-                         A);
-  }
-  return check_launch("cartpole_learnt_mpc_closed_loop");
+  return cart_mpc_loop_launch<CartLearntMpcLoopArgs>(
+      "cartpole_learnt_mpc_closed_loop", state0, dt, plant, plant_learnt, model, opt, B, H,
+      max_steps, mode, thresh_div, burn_in, steps, upright, vel_sum, vel_sq, states, actions,
+      cost, stream);
 }
 
 }  // extern "C"

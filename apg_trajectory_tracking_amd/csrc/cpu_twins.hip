@@ -31,6 +31,7 @@
 #include "quad_learnt_mpc_math.h"
 #include "quad_math.h"
 #include "quad_mpc_math.h"
+#include "static_dispatch.h"
 #include "wing_learnt_math.h"
 #include "wing_math.h"
 #include "wing_rollout_math.h"
@@ -963,7 +964,9 @@ int apg_quad_learnt_fit_fwd_bwd_cpu(const float *state, const float *action, flo
 }  // extern "C"
 
 // ------------------------------------------------------------ shooting MPC
-// apg_cpu_mpc.h: the solver of quad_mpc_math.h looped over the batch
+// apg_cpu_mpc.h: the solver and the flight of quad_mpc_math.h looped over the
+// batch, on the analytic model (MpcAnalytic) and on the learnt one (MpcLearnt,
+// quad_learnt_mpc_math.h)
 namespace {
 
 int check_mpc(const ApgQuadParams *model, const ApgQuadLossWeights *weights,
@@ -1000,6 +1003,62 @@ void mpc_solve_batch(const float *state0, const float *ref, int ref_cols, const 
   }
 }
 
+// the block the kernels read, filled as learnt_pack_kernel fills it (`m` as
+// learnt_mpc_check_model or quad_flight_check passed it; NULL: no block)
+std::vector<float> learnt_pack_host(const ApgLearntResidual *m) {
+  std::vector<float> pack(m ? kLearntFloats : 0);
+  for (size_t t = 0; t < pack.size(); ++t) pack[t] = learnt_packed((int)t, *m);
+  return pack;
+}
+
+// the solve behind both twins, after check_mpc, on the model `m`.  objection:
+// what the entry point's own model check said (NULL: nothing), raised here in
+// its place among the shared checks
+template <class Model>
+int quad_mpc_solve_twin(const char *objection, const float *state0, const float *ref,
+                        int ref_cols, const Model &m, const ApgQuadLossWeights &w,
+                        const ApgQuadMpcOptions &o, int B, int H, float *u, float *cost_out,
+                        float *cost_trace) {
+  if (objection) return fail("%s", objection);
+  if (ref_cols != 9 && ref_cols != 6)
+    return fail("ref_cols must be 9 ([pos, euler, vel]) or 6 ([pos, vel])");
+  if (B == 0) return APG_OK;
+  if (!state0 || !ref || !u || !cost_out) return fail("NULL buffer");
+  with_horizon(H, [&](auto h) {
+    mpc_solve_batch<h()>(state0, ref, ref_cols, m, w, o, B, u, cost_out, cost_trace);
+  });
+  return APG_OK;
+}
+
+// the closed loop behind both twins, after check_mpc: the plant's checks and
+// block, then the flights on the model `m`; objection as above
+template <class Model>
+int quad_mpc_loop_twin(const char *objection, const ApgQuadFlight *flight, float dt,
+                       const ApgQuadParams *plant, const ApgLearntResidual *plant_learnt,
+                       const Model &m, const ApgQuadLossWeights &w, const ApgQuadMpcOptions &o,
+                       int B, float *cost) {
+  if (!plant) return fail("plant is NULL");
+  if (objection) return fail("%s", objection);
+  QuadFlightRule rule;
+  if (const char *e = quad_flight_check(flight, plant_learnt, B, &rule)) return fail("%s", e);
+  const QuadConst cp = make_const(*plant, dt);
+  const std::vector<float> plant_pack = learnt_pack_host(plant_learnt);
+  const float *pl = plant_learnt ? plant_pack.data() : nullptr;   // NULL: quad_step alone
+  const size_t Bs = (size_t)B;
+  for (size_t b = 0; b < Bs; ++b)
+    flight->steps[b] = mpc_flight(
+        [&](int r, int col) { return flight->traj[((size_t)r * 9 + col) * Bs + b]; },
+        [&](float (&s)[12], const float (&u0)[4]) {
+          const Trig t = make_trig(&s[3]);
+          if (pl) learnt_quad_step_lane(s, u0, cp, t, pl);
+          else quad_step(s, u0, cp, t);
+        },
+        m, w, o, rule,
+        MpcFlightLog{flight->div, flight->drone, flight->actions, flight->start_states, cost,
+                     Bs, b});
+  return APG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1009,18 +1068,9 @@ int apg_quad_mpc_solve_cpu(const float *state0, const float *ref, int ref_cols, 
                            const ApgQuadMpcOptions *opt, int B, int H, float *u,
                            float *cost_out, float *cost_trace) {
   if (int e = check_mpc(model, weights, opt, B, H, true)) return e;
-  if (ref_cols != 9 && ref_cols != 6)
-    return fail("ref_cols must be 9 ([pos, euler, vel]) or 6 ([pos, vel])");
-  if (B == 0) return APG_OK;
-  if (!state0 || !ref || !u || !cost_out) return fail("NULL buffer");
   const QuadConst c = make_const(*model, dt);
-  if (H == 5)
-    mpc_solve_batch<5>(state0, ref, ref_cols, MpcAnalytic{c}, *weights, *opt, B, u, cost_out,
-                       cost_trace);
-  else
-    mpc_solve_batch<10>(state0, ref, ref_cols, MpcAnalytic{c}, *weights, *opt, B, u, cost_out,
-                        cost_trace);
-  return APG_OK;
+  return quad_mpc_solve_twin(nullptr, state0, ref, ref_cols, MpcAnalytic{c}, *weights, *opt, B,
+                             H, u, cost_out, cost_trace);
 }
 
 int apg_quad_mpc_closed_loop_cpu(const ApgQuadFlight *flight, float dt,
@@ -1032,37 +1082,11 @@ int apg_quad_mpc_closed_loop_cpu(const ApgQuadFlight *flight, float dt,
                                  float *workspace) {
   (void)workspace;
   if (int e = check_mpc(model, weights, opt, B, H, false)) return e;
-  if (!plant) return fail("plant is NULL");
-  if (plant_learnt) return fail("the host twin flies the analytic plant only");
-  QuadFlightRule rule;
-  if (const char *e = quad_flight_check(flight, plant_learnt, B, &rule)) return fail("%s", e);
-  const QuadConst cp = make_const(*plant, dt), cm = make_const(*model, dt);
-  const size_t Bs = (size_t)B;
-  for (size_t b = 0; b < Bs; ++b)
-    flight->steps[b] = mpc_flight(
-        [&](int r, int col) { return flight->traj[((size_t)r * 9 + col) * Bs + b]; },
-        [&](float (&s)[12], const float (&u0)[4]) { quad_step(s, u0, cp, make_trig(&s[3])); },
-        MpcAnalytic{cm}, *weights, *opt, rule,
-        MpcFlightLog{flight->div, flight->drone, flight->actions, flight->start_states, cost,
-                     Bs, b});
-  return APG_OK;
+  const QuadConst cm = make_const(*model, dt);
+  return quad_mpc_loop_twin(
+      plant_learnt ? "the host twin flies the analytic plant only" : nullptr, flight, dt, plant,
+      plant_learnt, MpcAnalytic{cm}, *weights, *opt, B, cost);
 }
-
-}  // extern "C"
-
-// apg_cpu_mpc.h: the same solver on the learnt model of quad_learnt_mpc_math.h
-namespace {
-
-// the block the kernels read, filled as learnt_pack_kernel fills it
-std::vector<float> learnt_pack_host(const ApgLearntResidual &m) {
-  std::vector<float> pack(kLearntFloats);
-  for (int t = 0; t < kLearntFloats; ++t) pack[t] = learnt_packed(t, m);
-  return pack;
-}
-
-}  // namespace
-
-extern "C" {
 
 int apg_quad_learnt_mpc_workspace_floats_cpu(void) { return 2 * kLearntFloats; }
 
@@ -1074,20 +1098,13 @@ int apg_quad_learnt_mpc_solve_cpu(const float *state0, const float *ref, int ref
                                   float *cost_out, float *cost_trace, float *workspace) {
   (void)workspace;
   if (int e = check_mpc(model, weights, opt, B, H, true)) return e;
-  if (const char *e = learnt_mpc_check_model(model_learnt)) return fail("%s", e);
-  if (ref_cols != 9 && ref_cols != 6)
-    return fail("ref_cols must be 9 ([pos, euler, vel]) or 6 ([pos, vel])");
-  if (B == 0) return APG_OK;
-  if (!state0 || !ref || !u || !cost_out) return fail("NULL buffer");
+  const char *objection = learnt_mpc_check_model(model_learnt);
+  const std::vector<float> pack = learnt_pack_host(objection ? nullptr : model_learnt);
   const QuadConst c = make_const(*model, dt);
-  const std::vector<float> pack = learnt_pack_host(*model_learnt);
   float pre[10 * kMpcPreRow];
-  const MpcLearnt<const float *> m{c, pack.data(), pre};
-  if (H == 5)
-    mpc_solve_batch<5>(state0, ref, ref_cols, m, *weights, *opt, B, u, cost_out, cost_trace);
-  else
-    mpc_solve_batch<10>(state0, ref, ref_cols, m, *weights, *opt, B, u, cost_out, cost_trace);
-  return APG_OK;
+  return quad_mpc_solve_twin(objection, state0, ref, ref_cols,
+                             MpcLearnt<const float *>{c, pack.data(), pre}, *weights, *opt, B, H,
+                             u, cost_out, cost_trace);
 }
 
 int apg_quad_learnt_mpc_closed_loop_cpu(const ApgQuadFlight *flight, float dt,
@@ -1100,30 +1117,13 @@ int apg_quad_learnt_mpc_closed_loop_cpu(const ApgQuadFlight *flight, float dt,
                                         float *cost, float *workspace) {
   (void)workspace;
   if (int e = check_mpc(model, weights, opt, B, H, false)) return e;
-  if (!plant) return fail("plant is NULL");
-  if (const char *e = learnt_mpc_check_model(model_learnt)) return fail("%s", e);
-  QuadFlightRule rule;
-  if (const char *e = quad_flight_check(flight, plant_learnt, B, &rule)) return fail("%s", e);
-  const QuadConst cp = make_const(*plant, dt), cm = make_const(*model, dt);
-  const std::vector<float> pack = learnt_pack_host(*model_learnt);
-  const std::vector<float> plant_pack =
-      plant_learnt ? learnt_pack_host(*plant_learnt) : std::vector<float>();
-  const float *pl = plant_learnt ? plant_pack.data() : nullptr;
+  const char *objection = learnt_mpc_check_model(model_learnt);
+  const std::vector<float> pack = learnt_pack_host(objection ? nullptr : model_learnt);
+  const QuadConst cm = make_const(*model, dt);
   float pre[kFlightH * kMpcPreRow];
-  const MpcLearnt<const float *> m{cm, pack.data(), pre};
-  const size_t Bs = (size_t)B;
-  for (size_t b = 0; b < Bs; ++b)
-    flight->steps[b] = mpc_flight(
-        [&](int r, int col) { return flight->traj[((size_t)r * 9 + col) * Bs + b]; },
-        [&](float (&s)[12], const float (&u0)[4]) {
-          const Trig t = make_trig(&s[3]);
-          if (pl) learnt_quad_step_lane(s, u0, cp, t, pl);
-          else quad_step(s, u0, cp, t);
-        },
-        m, *weights, *opt, rule,
-        MpcFlightLog{flight->div, flight->drone, flight->actions, flight->start_states, cost,
-                     Bs, b});
-  return APG_OK;
+  return quad_mpc_loop_twin(objection, flight, dt, plant, plant_learnt,
+                            MpcLearnt<const float *>{cm, pack.data(), pre}, *weights, *opt, B,
+                            cost);
 }
 
 }  // extern "C"

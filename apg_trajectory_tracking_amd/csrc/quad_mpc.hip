@@ -17,6 +17,7 @@
 // (DESIGN.md §7).
 #include "learnt_residual.h"
 #include "quad_learnt_mpc_math.h"
+#include "static_dispatch.h"
 
 namespace apg {
 namespace {
@@ -108,7 +109,11 @@ struct MpcLoopArgs {
   int B;
 };
 
-// mpc_flight (quad_mpc_math.h), one flight per lane
+// mpc_flight (quad_mpc_math.h), one flight per lane.  (The lane body stands in
+// both closed-loop kernels: moved into one __forceinline__ function - by
+// reference or by value, with the plant step passed in or built inside - hipcc
+// schedules all four instantiations differently, the learnt-model ones by 300
+// instructions; they are kept as measured.)
 template <bool LEARNT>
 __global__ __launch_bounds__(kMpcThreads) void quad_mpc_closed_loop_kernel(MpcLoopArgs A) {
   __shared__ float lr[LEARNT ? kLearntFloats : 1];
@@ -159,21 +164,100 @@ __global__ __launch_bounds__(kMpcThreads) void quad_learnt_mpc_closed_loop_kerne
       model, A.w, A.o, A.rule, log);
 }
 
+int fail_arg(const char *e) {
+  set_error("%s", e);
+  return APG_ERR_ARG;
+}
+
 int check_mpc(const ApgQuadParams *model, const ApgQuadLossWeights *weights,
               const ApgQuadMpcOptions *opt, int B) {
   if (B < 0) {
     set_error("B must be >= 0 (got %d)", B);
     return APG_ERR_ARG;
   }
-  if (!model || !weights) {
-    set_error("model / weights is NULL");
-    return APG_ERR_ARG;
-  }
-  if (const char *e = mpc_check_options(opt)) {
-    set_error("%s", e);
-    return APG_ERR_ARG;
-  }
+  if (!model || !weights) return fail_arg("model / weights is NULL");
+  if (const char *e = mpc_check_options(opt)) return fail_arg(e);
   return APG_OK;
+}
+
+void pack_learnt(const ApgLearntResidual &m, float *block, hipStream_t st) {
+  hipLaunchKernelGGL(learnt_pack_kernel, dim3((kLearntFloats + 255) / 256), dim3(256), 0, st, m,
+                     block);
+}
+
+// The solve behind both entry points.  learnt: the solver plans through
+// `model_learnt`, packed into workspace[0, kLearntFloats); else neither is read.
+int mpc_solve_launch(const char *name, bool learnt, const float *state0, const float *ref,
+                     int ref_cols, float dt, const ApgQuadParams *model,
+                     const ApgLearntResidual *model_learnt, const ApgQuadLossWeights *weights,
+                     const ApgQuadMpcOptions *opt, int B, int H, float *u, float *cost_out,
+                     float *cost_trace, float *workspace, apg_stream_t stream) {
+  if (int e = check_mpc(model, weights, opt, B)) return e;
+  if (const char *e = learnt ? learnt_mpc_check_model(model_learnt) : nullptr) return fail_arg(e);
+  if (H != 5 && H != 10) {
+    set_error("H must be 5 or 10 (got %d)", H);
+    return APG_ERR_ARG;
+  }
+  if (ref_cols != 9 && ref_cols != 6)
+    return fail_arg("ref_cols must be 9 ([pos, euler, vel]) or 6 ([pos, vel])");
+  if (B == 0) return APG_OK;
+  if (!state0 || !ref || !u || !cost_out || (learnt && !workspace))
+    return fail_arg("NULL buffer");
+  MpcSolveArgs A;
+  A.state0 = state0, A.ref = ref, A.u = u, A.cost_out = cost_out, A.cost_trace = cost_trace;
+  A.c = make_const(*model, dt);
+  A.w = *weights, A.o = *opt;
+  A.B = B, A.ref_cols = ref_cols;
+  const dim3 grid((B + kMpcThreads - 1) / kMpcThreads), block(kMpcThreads);
+  hipStream_t st = (hipStream_t)stream;
+  const float *packed = workspace;
+  if (learnt) pack_learnt(*model_learnt, workspace, st);
+  with_horizon(H, [&](auto h) {
+    if (learnt)
+      hipLaunchKernelGGL(quad_learnt_mpc_solve_kernel<h()>, grid, block, 0, st, A, packed);
+    else
+      hipLaunchKernelGGL(quad_mpc_solve_kernel<h()>, grid, block, 0, st, A);
+  });
+  return check_launch(name);
+}
+
+// The closed loop behind both entry points.  learnt: the solver plans through
+// `model_learnt`, packed into workspace[0, kLearntFloats), and the plant's block
+// (plant_learnt) follows it; else the plant's block is at workspace[0].
+int mpc_loop_launch(const char *name, bool learnt, const ApgQuadFlight *flight, float dt,
+                    const ApgQuadParams *plant, const ApgLearntResidual *plant_learnt,
+                    const ApgQuadParams *model, const ApgLearntResidual *model_learnt,
+                    const ApgQuadLossWeights *weights, const ApgQuadMpcOptions *opt, int B,
+                    int H, float *cost, float *workspace, apg_stream_t stream) {
+  if (int e = check_mpc(model, weights, opt, B)) return e;
+  if (!plant) return fail_arg("plant is NULL");
+  if (const char *e = learnt ? learnt_mpc_check_model(model_learnt) : nullptr) return fail_arg(e);
+  if (H != kFlightH) {
+    set_error("H must be %d (got %d)", kFlightH, H);
+    return APG_ERR_ARG;
+  }
+  MpcLoopArgs A;
+  if (const char *e = quad_flight_check(flight, plant_learnt, B, &A.rule)) return fail_arg(e);
+  if (B == 0) return APG_OK;
+  if ((learnt || plant_learnt) && !workspace) return fail_arg("NULL buffer");
+  float *plant_block = learnt ? workspace + kLearntFloats : workspace;
+  A.traj = flight->traj, A.steps = flight->steps;
+  A.log = {flight->div, flight->drone, flight->actions, flight->start_states, cost, 0, 0};
+  A.learnt = plant_learnt ? plant_block : nullptr;
+  A.cp = make_const(*plant, dt), A.cm = make_const(*model, dt);
+  A.w = *weights, A.o = *opt, A.B = B;
+  const dim3 grid((B + kMpcThreads - 1) / kMpcThreads), block(kMpcThreads);
+  hipStream_t st = (hipStream_t)stream;
+  const float *packed = workspace;
+  if (learnt) pack_learnt(*model_learnt, workspace, st);
+  if (plant_learnt) pack_learnt(*plant_learnt, plant_block, st);
+  with_flag(plant_learnt != nullptr, [&](auto pl) {
+    if (learnt)
+      hipLaunchKernelGGL(quad_learnt_mpc_closed_loop_kernel<pl()>, grid, block, 0, st, A, packed);
+    else
+      hipLaunchKernelGGL(quad_mpc_closed_loop_kernel<pl()>, grid, block, 0, st, A);
+  });
+  return check_launch(name);
 }
 
 }  // namespace
@@ -187,32 +271,8 @@ int apg_quad_mpc_solve(const float *state0, const float *ref, int ref_cols, floa
                        const ApgQuadParams *model, const ApgQuadLossWeights *weights,
                        const ApgQuadMpcOptions *opt, int B, int H, float *u,
                        float *cost_out, float *cost_trace, apg_stream_t stream) {
-  if (int e = check_mpc(model, weights, opt, B)) return e;
-  if (H != 5 && H != 10) {
-    set_error("H must be 5 or 10 (got %d)", H);
-    return APG_ERR_ARG;
-  }
-  if (ref_cols != 9 && ref_cols != 6) {
-    set_error("ref_cols must be 9 ([pos, euler, vel]) or 6 ([pos, vel])");
-    return APG_ERR_ARG;
-  }
-  if (B == 0) return APG_OK;
-  if (!state0 || !ref || !u || !cost_out) {
-    set_error("NULL buffer");
-    return APG_ERR_ARG;
-  }
-  MpcSolveArgs A;
-  A.state0 = state0, A.ref = ref, A.u = u, A.cost_out = cost_out, A.cost_trace = cost_trace;
-  A.c = make_const(*model, dt);
-  A.w = *weights, A.o = *opt;
-  A.B = B, A.ref_cols = ref_cols;
-  const dim3 grid((B + kMpcThreads - 1) / kMpcThreads);
-  hipStream_t st = (hipStream_t)stream;
-  if (H == 5)
-    hipLaunchKernelGGL(quad_mpc_solve_kernel<5>, grid, dim3(kMpcThreads), 0, st, A);
-  else
-    hipLaunchKernelGGL(quad_mpc_solve_kernel<10>, grid, dim3(kMpcThreads), 0, st, A);
-  return check_launch("quad_mpc_solve");
+  return mpc_solve_launch("quad_mpc_solve", false, state0, ref, ref_cols, dt, model, nullptr,
+                          weights, opt, B, H, u, cost_out, cost_trace, nullptr, stream);
 }
 
 int apg_quad_mpc_workspace_floats(void) { return kLearntFloats; }
@@ -221,40 +281,8 @@ int apg_quad_mpc_closed_loop(const ApgQuadFlight *flight, float dt, const ApgQua
                              const ApgLearntResidual *plant_learnt, const ApgQuadParams *model,
                              const ApgQuadLossWeights *weights, const ApgQuadMpcOptions *opt,
                              int B, int H, float *cost, float *workspace, apg_stream_t stream) {
-  if (int e = check_mpc(model, weights, opt, B)) return e;
-  if (!plant) {
-    set_error("plant is NULL");
-    return APG_ERR_ARG;
-  }
-  if (H != kFlightH) {
-    set_error("H must be %d (got %d)", kFlightH, H);
-    return APG_ERR_ARG;
-  }
-  MpcLoopArgs A;
-  if (const char *e = quad_flight_check(flight, plant_learnt, B, &A.rule)) {
-    set_error("%s", e);
-    return APG_ERR_ARG;
-  }
-  if (B == 0) return APG_OK;
-  if (plant_learnt && !workspace) {
-    set_error("NULL buffer");
-    return APG_ERR_ARG;
-  }
-  A.traj = flight->traj, A.steps = flight->steps;
-  A.log = {flight->div, flight->drone, flight->actions, flight->start_states, cost, 0, 0};
-  A.learnt = plant_learnt ? workspace : nullptr;
-  A.cp = make_const(*plant, dt), A.cm = make_const(*model, dt);
-  A.w = *weights, A.o = *opt, A.B = B;
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((B + kMpcThreads - 1) / kMpcThreads);
-  if (plant_learnt) {
-    hipLaunchKernelGGL(learnt_pack_kernel, dim3((kLearntFloats + 255) / 256), dim3(256), 0, st,
-                       *plant_learnt, workspace);
-    hipLaunchKernelGGL(quad_mpc_closed_loop_kernel<true>, grid, dim3(kMpcThreads), 0, st, A);
-  } else {
-    hipLaunchKernelGGL(quad_mpc_closed_loop_kernel<false>, grid, dim3(kMpcThreads), 0, st, A);
-  }
-  return check_launch("quad_mpc_closed_loop");
+  return mpc_loop_launch("quad_mpc_closed_loop", false, flight, dt, plant, plant_learnt, model,
+                         nullptr, weights, opt, B, H, cost, workspace, stream);
 }
 
 // [0, kLearntFloats): the model's block, [kLearntFloats, 2 kLearntFloats): the plant's
@@ -265,40 +293,9 @@ int apg_quad_learnt_mpc_solve(const float *state0, const float *ref, int ref_col
                               const ApgQuadLossWeights *weights, const ApgQuadMpcOptions *opt,
                               int B, int H, float *u, float *cost_out, float *cost_trace,
                               float *workspace, apg_stream_t stream) {
-  if (int e = check_mpc(model, weights, opt, B)) return e;
-  if (const char *e = learnt_mpc_check_model(model_learnt)) {
-    set_error("%s", e);
-    return APG_ERR_ARG;
-  }
-  if (H != 5 && H != 10) {
-    set_error("H must be 5 or 10 (got %d)", H);
-    return APG_ERR_ARG;
-  }
-  if (ref_cols != 9 && ref_cols != 6) {
-    set_error("ref_cols must be 9 ([pos, euler, vel]) or 6 ([pos, vel])");
-    return APG_ERR_ARG;
-  }
-  if (B == 0) return APG_OK;
-  if (!state0 || !ref || !u || !cost_out || !workspace) {
-    set_error("NULL buffer");
-    return APG_ERR_ARG;
-  }
-  MpcSolveArgs A;
-  A.state0 = state0, A.ref = ref, A.u = u, A.cost_out = cost_out, A.cost_trace = cost_trace;
-  A.c = make_const(*model, dt);
-  A.w = *weights, A.o = *opt;
-  A.B = B, A.ref_cols = ref_cols;
-  const dim3 grid((B + kMpcThreads - 1) / kMpcThreads);
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(learnt_pack_kernel, dim3((kLearntFloats + 255) / 256), dim3(256), 0, st,
-                     *model_learnt, workspace);
-  const float *packed = workspace;
-  if (H == 5)
-    hipLaunchKernelGGL(quad_learnt_mpc_solve_kernel<5>, grid, dim3(kMpcThreads), 0, st, A, packed);
-  else
-    hipLaunchKernelGGL(quad_learnt_mpc_solve_kernel<10>, grid, dim3(kMpcThreads), 0, st, A,
-                       packed);
-  return check_launch("quad_learnt_mpc_solve");
+  return mpc_solve_launch("quad_learnt_mpc_solve", true, state0, ref, ref_cols, dt, model,
+                          model_learnt, weights, opt, B, H, u, cost_out, cost_trace, workspace,
+                          stream);
 }
 
 int apg_quad_learnt_mpc_closed_loop(const ApgQuadFlight *flight, float dt,
@@ -309,48 +306,9 @@ int apg_quad_learnt_mpc_closed_loop(const ApgQuadFlight *flight, float dt,
                                     const ApgQuadLossWeights *weights,
                                     const ApgQuadMpcOptions *opt, int B, int H, float *cost,
                                     float *workspace, apg_stream_t stream) {
-  if (int e = check_mpc(model, weights, opt, B)) return e;
-  if (!plant) {
-    set_error("plant is NULL");
-    return APG_ERR_ARG;
-  }
-  if (const char *e = learnt_mpc_check_model(model_learnt)) {
-    set_error("%s", e);
-    return APG_ERR_ARG;
-  }
-  if (H != kFlightH) {
-    set_error("H must be %d (got %d)", kFlightH, H);
-    return APG_ERR_ARG;
-  }
-  MpcLoopArgs A;
-  if (const char *e = quad_flight_check(flight, plant_learnt, B, &A.rule)) {
-    set_error("%s", e);
-    return APG_ERR_ARG;
-  }
-  if (B == 0) return APG_OK;
-  if (!workspace) {
-    set_error("NULL buffer");
-    return APG_ERR_ARG;
-  }
-  A.traj = flight->traj, A.steps = flight->steps;
-  A.log = {flight->div, flight->drone, flight->actions, flight->start_states, cost, 0, 0};
-  A.learnt = plant_learnt ? workspace + kLearntFloats : nullptr;
-  A.cp = make_const(*plant, dt), A.cm = make_const(*model, dt);
-  A.w = *weights, A.o = *opt, A.B = B;
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((B + kMpcThreads - 1) / kMpcThreads), pack((kLearntFloats + 255) / 256);
-  const float *packed = workspace;
-  hipLaunchKernelGGL(learnt_pack_kernel, pack, dim3(256), 0, st, *model_learnt, workspace);
-  if (plant_learnt) {
-    hipLaunchKernelGGL(learnt_pack_kernel, pack, dim3(256), 0, st, *plant_learnt,
-                       workspace + kLearntFloats);
-    hipLaunchKernelGGL(quad_learnt_mpc_closed_loop_kernel<true>, grid, dim3(kMpcThreads), 0, st,
-                       A, packed);
-  } else {
-    hipLaunchKernelGGL(quad_learnt_mpc_closed_loop_kernel<false>, grid, dim3(kMpcThreads), 0, st,
-                       A, packed);
-  }
-  return check_launch("quad_learnt_mpc_closed_loop");
+  return mpc_loop_launch("quad_learnt_mpc_closed_loop", true, flight, dt, plant, plant_learnt,
+                         model, model_learnt, weights, opt, B, H, cost, workspace, stream);
 }
 
 }  // extern "C"
+

@@ -2085,19 +2085,17 @@ def quad_mpc_solve(state0, ref, dt, params, u0=None, weights=None, iters=10, bet
     cost = torch.empty(B, dtype=torch.float32, device=dev)
     trace = (torch.empty(opt.iters + 1, B, dtype=torch.float32, device=dev)
              if want_trace else None)
+    # the learnt entry point takes the module after `params` and a workspace
+    # before the stream
+    name, model, ws = "apg_quad_mpc_solve", (), ()
     if learnt is not None:
-        model = _learnt_model(learnt)
-        ws = torch.empty(lib().apg_quad_learnt_mpc_workspace_floats(), dtype=torch.float32,
-                         device=dev)
-        check(lib().apg_quad_learnt_mpc_solve(
-            ptr(s), ptr(r), C, float(dt), ctypes.byref(params), ctypes.byref(model),
-            ctypes.byref(weights), ctypes.byref(opt), B, H, ptr(u), ptr(cost), ptr(trace),
-            ptr(ws), stream_of(s)), "apg_quad_learnt_mpc_solve")
-    else:
-        check(lib().apg_quad_mpc_solve(
-            ptr(s), ptr(r), C, float(dt), ctypes.byref(params), ctypes.byref(weights),
-            ctypes.byref(opt), B, H, ptr(u), ptr(cost), ptr(trace), stream_of(s)),
-            "apg_quad_mpc_solve")
+        name, model = "apg_quad_learnt_mpc_solve", (ctypes.byref(_learnt_model(learnt)),)
+        block = torch.empty(lib().apg_quad_learnt_mpc_workspace_floats(), dtype=torch.float32,
+                            device=dev)
+        ws = (ptr(block),)
+    check(getattr(lib(), name)(
+        ptr(s), ptr(r), C, float(dt), ctypes.byref(params), *model, ctypes.byref(weights),
+        ctypes.byref(opt), B, H, ptr(u), ptr(cost), ptr(trace), *ws, stream_of(s)), name)
     return dict(u=u.permute(2, 0, 1).contiguous(), cost=cost, trace=trace)
 
 
@@ -2120,23 +2118,22 @@ def quad_mpc_closed_loop(traj, dt, params, model_params=None, learnt=None, weigh
     require_device(fl.tr)
     cost = fl.new(fl.T, fl.B)
     env, _keep = _learnt_env(learnt)
-    ws = fl.new(lib().apg_quad_mpc_workspace_floats()) if learnt is not None else None
     opt = quad_mpc_options(iters, beta, alpha_thrust, alpha_rate)
     weights = weights or quad_loss_weights()
-    if model_learnt is not None:
-        model = model_learnt.params if model_params is None else model_params
-        residual = _learnt_model(model_learnt)
+    # the learnt entry point takes the module after the model's parameters
+    if model_learnt is None:
+        name, model, residual = "apg_quad_mpc_closed_loop", params, ()
+        ws = fl.new(lib().apg_quad_mpc_workspace_floats()) if learnt is not None else None
+    else:
+        name, model = "apg_quad_learnt_mpc_closed_loop", model_learnt.params
+        residual = (ctypes.byref(_learnt_model(model_learnt)),)
         ws = fl.new(lib().apg_quad_learnt_mpc_workspace_floats())
-        check(lib().apg_quad_learnt_mpc_closed_loop(
-            fl.ref, float(dt), ctypes.byref(params), env, ctypes.byref(model),
-            ctypes.byref(residual), ctypes.byref(weights), ctypes.byref(opt), fl.B, 10,
-            ptr(cost), ptr(ws), stream_of(fl.tr)), "apg_quad_learnt_mpc_closed_loop")
-        return dict(fl.out, cost=cost)
-    model = params if model_params is None else model_params
-    check(lib().apg_quad_mpc_closed_loop(
-        fl.ref, float(dt), ctypes.byref(params), env, ctypes.byref(model),
+    if model_params is not None:
+        model = model_params
+    check(getattr(lib(), name)(
+        fl.ref, float(dt), ctypes.byref(params), env, ctypes.byref(model), *residual,
         ctypes.byref(weights), ctypes.byref(opt), fl.B, 10, ptr(cost), ptr(ws),
-        stream_of(fl.tr)), "apg_quad_mpc_closed_loop")
+        stream_of(fl.tr)), name)
     return dict(fl.out, cost=cost)
 
 

@@ -249,17 +249,20 @@ def test_run_dynamics_schedule_with_stubbed_epochs(tmp_path, monkeypatch):
 def test_new_kernels_no_scratch_and_analytic_closed_loop_unchanged():
     """Zero scratch and spills in every learnt cart-pole kernel; the analytic
     closed loop keeps the registers and occupancy of the parent build."""
-    import json
-    from apg_trajectory_tracking_amd import build
-    build.build()
-    with open(build.RESOURCES) as f:
-        res = json.load(f)
-    learnt = {k: v for k, v in res.items()
-              if "cart_learnt" in k or "cart_closed_loop_kernelILb1E" in k}
+    import kernel_names
+    res = kernel_names.resources()
+    loop = kernel_names.instances(res, "cart_closed_loop_kernel")
+    assert sorted(loop) == ["ILb0E", "ILb1E"], sorted(loop)
+    learnt = {("cart_closed_loop_kernel", "ILb1E"): loop["ILb1E"]}
+    # the kernels of cartpole_learnt.hip, by name and number of instantiations
+    for name, count in (("cart_learnt_rollout_kernel", 2), ("cart_learnt_reduce_kernel", 1),
+                        ("cart_learnt_step_fwd_kernel", 1), ("cart_learnt_step_bwd_kernel", 1)):
+        found = kernel_names.instances(res, name)
+        assert len(found) == count, (name, sorted(found))
+        learnt.update({(name, args): v for args, v in found.items()})
     assert len(learnt) == 6, sorted(learnt)
     for k, v in learnt.items():
         assert v["scratch"] == 0 and v["vgpr_spill"] == 0, (k, v)
-    ana = [v for k, v in res.items() if "cart_closed_loop_kernelILb0E" in k]
-    assert len(ana) == 1
-    assert {k: ana[0][k] for k in ("vgprs", "agprs", "sgprs", "occupancy", "scratch")} == \
+    ana = loop["ILb0E"]
+    assert {k: ana[k] for k in ("vgprs", "agprs", "sgprs", "occupancy", "scratch")} == \
         {"vgprs": 71, "agprs": 64, "sgprs": 84, "occupancy": 3, "scratch": 0}

@@ -8,7 +8,6 @@ residual, gradient: torch autograd), the float32 restatement as the yardstick
 for rounding (conftest.assert_no_worse_than_fp32, its defaults).  Runs without
 a GPU."""
 import ctypes
-import json
 import os
 
 import numpy as np
@@ -17,6 +16,7 @@ import torch
 
 import cartpole_learnt_mpc_restatement as L
 import cartpole_mpc_restatement as R
+import kernel_names
 from test_cartpole_mpc_cpu import check_solve
 
 DT = L.DT
@@ -358,13 +358,10 @@ def test_kernels_keep_the_solver_in_registers():
     """The build's kernel_resources.json lists the two learnt-model kernels in
     every instantiation (solve: H = 5, 10; closed loop: H = 5, 10 x analytic /
     learnt plant) without scratch and without spilled VGPRs."""
-    from apg_trajectory_tracking_amd import build
-    build.build()
-    with open(build.RESOURCES) as f:
-        res = json.load(f)
+    res = kernel_names.resources()
     for name, count in (("cart_mpc_learnt_solve_kernel", 2),
                         ("cart_mpc_learnt_closed_loop_kernel", 4)):
-        found = {k: v for k, v in res.items() if name in k}
+        found = kernel_names.instances(res, name)
         assert len(found) == count, (name, sorted(found))
         for k, v in found.items():
             print(k, v)

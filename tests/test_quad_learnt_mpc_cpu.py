@@ -8,13 +8,13 @@ torch_port.quad_mpc_loss, gradient: torch autograd), the float32 restatement as
 the yardstick for rounding (conftest.assert_no_worse_than_fp32, its defaults).
 Runs without a GPU."""
 import ctypes
-import json
 import os
 
 import numpy as np
 import pytest
 import torch
 
+import kernel_names
 import quad_learnt_mpc_restatement as L
 import quad_mpc_restatement as R
 from conftest import assert_no_worse_than_fp32
@@ -330,14 +330,11 @@ def test_kernels_keep_scratch_free():
     kernel_resources.json - the solve at H = 10 and H = 5, the closed loop with
     the analytic and with the learnt plant - without scratch and without
     spilled VGPRs."""
-    from apg_trajectory_tracking_amd import build
-    build.build()
-    with open(build.RESOURCES) as f:
-        res = json.load(f)
-    solve = {k: v for k, v in res.items() if "quad_learnt_mpc_solve_kernel" in k}
-    loop = {k: v for k, v in res.items() if "quad_learnt_mpc_closed_loop_kernel" in k}
+    res = kernel_names.resources()
+    solve = kernel_names.instances(res, "quad_learnt_mpc_solve_kernel")
+    loop = kernel_names.instances(res, "quad_learnt_mpc_closed_loop_kernel")
     assert len(solve) >= 2 and len(loop) >= 1, (sorted(solve), sorted(loop))
-    assert any("ILi10E" in k for k in solve) and any("ILi5E" in k for k in solve)
-    for k, v in {**solve, **loop}.items():
+    assert "ILi10E" in solve and "ILi5E" in solve
+    for k, v in [*solve.items(), *loop.items()]:
         print(k, v)
         assert v["scratch"] == 0 and v["vgpr_spill"] == 0, (k, v)

@@ -5,13 +5,13 @@ float64 restatement of the algorithm in tests/quad_mpc_restatement.py (model:
 oracle.torch_port.QuadOracle, cost: torch_port.quad_mpc_loss, gradient: torch
 autograd), with the float32 restatement as the yardstick for rounding
 (conftest.assert_no_worse_than_fp32, its defaults).  Runs without a GPU."""
-import json
 import os
 
 import numpy as np
 import pytest
 import torch
 
+import kernel_names
 import quad_mpc_restatement as R
 from conftest import assert_no_worse_than_fp32
 
@@ -296,12 +296,9 @@ def test_horizon_five(tw):
 def test_kernels_keep_the_solver_in_registers():
     """The build's kernel_resources.json lists the two kernels (every
     instantiation) without scratch and without spilled VGPRs."""
-    from apg_trajectory_tracking_amd import build
-    build.build()
-    with open(build.RESOURCES) as f:
-        res = json.load(f)
+    res = kernel_names.resources()
     for name, least in (("quad_mpc_solve_kernel", 2), ("quad_mpc_closed_loop_kernel", 2)):
-        found = {k: v for k, v in res.items() if name in k}
+        found = kernel_names.instances(res, name)
         assert len(found) >= least, (name, sorted(found))
         for k, v in found.items():
             assert v["scratch"] == 0 and v["vgpr_spill"] == 0, (k, v)
