@@ -275,6 +275,12 @@ class ApgCartpoleMpcOptions(ctypes.Structure):
                 ("alpha", ctypes.c_float)]
 
 
+class ApgWingMpcOptions(ctypes.Structure):
+    """include/apg.h: the fixed-wing shooting MPC's iteration count and step rule."""
+    _fields_ = [("iters", ctypes.c_int), ("beta", ctypes.c_float),
+                ("alpha_thrust", ctypes.c_float), ("alpha_surface", ctypes.c_float)]
+
+
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 _F = ctypes.c_float
@@ -508,6 +514,13 @@ SIGNATURES = {
         _P, _F, ctypes.POINTER(ApgCartpoleParams), ctypes.POINTER(ApgCartpoleLearnt),
         ctypes.POINTER(ApgCartpoleLearnt), ctypes.POINTER(ApgCartpoleMpcOptions),
         _I, _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "apg_wing_mpc_solve": [
+        _P, _P, _F, ctypes.POINTER(ApgWingParams), ctypes.POINTER(ApgWingLossWeights),
+        ctypes.POINTER(ApgWingMpcOptions), _I, _I, _P, _P, _P, _P],
+    "apg_wing_mpc_closed_loop": [
+        _P, _I, _P, _F, ctypes.POINTER(ApgWingParams), ctypes.POINTER(ApgWingParams),
+        ctypes.POINTER(ApgWingLossWeights), ctypes.POINTER(ApgWingMpcOptions), _I, _I, _I,
+        _F, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P],
     "apg_launch_chain_prepare": [_P],
     "apg_launch_chain_flush": [_P],
     "apg_launch_chain_set_lane_priority": [_I],

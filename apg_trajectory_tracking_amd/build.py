@@ -15,7 +15,7 @@ SOURCES = ["common.hip", "quad.hip", "wing.hip", "cartpole.hip", "lstm.hip",
            "mlp_rollout.hip", "mlp_concurrent.hip", "mlp_wing.hip", "wing_learnt.hip",
            "linear_wgrad.hip", "planes_gemm.hip", "mlp_cartpole.hip",
            "cartpole_learnt.hip", "quad_mpc.hip", "cartpole_mpc.hip", "quad_fit.hip",
-           "cartpole_fit.hip", "cartpole_train.hip", "launch_chain.hip"]
+           "cartpole_fit.hip", "cartpole_train.hip", "launch_chain.hip", "wing_mpc.hip"]
 # -fno-slp-vectorize: hipcc's SLP pass packs neighbouring f32 ops into
 # v_pk_fma/mul/add_f32; on gfx950 a packed op issues no faster than two plain
 # ones here and needs v_mov shuffles to form register pairs - measured on
@@ -141,7 +141,8 @@ def build_cpu(force=False, verbose=False):
             os.path.join(REPO, "include", "apg_cpu_cartpole_fit.h"),
             os.path.join(REPO, "include", "apg_cpu_cartpole_train.h"),
             os.path.join(REPO, "include", "apg_cpu_cartpole_learnt_train.h"),
-            os.path.join(REPO, "include", "apg_cpu_mpc.h"), __file__] + _headers()
+            os.path.join(REPO, "include", "apg_cpu_mpc.h"),
+            os.path.join(REPO, "include", "apg_cpu_wing_mpc.h"), __file__] + _headers()
     if (not force and os.path.exists(LIB_CPU)
             and os.path.getmtime(LIB_CPU) >= max(os.path.getmtime(d) for d in deps)):
         return LIB_CPU

@@ -1,5 +1,5 @@
-"""Drop-in for `neural_control.controllers.mpc.MPC` on the quadrotor and the
-cart-pole: the comparator the reference judges its learnt controllers against,
+"""Drop-in for `neural_control.controllers.mpc.MPC` on the quadrotor, the
+cart-pole and the fixed wing: the comparator the reference judges its learnt controllers against,
 batched.
 
     mpc = MPC(horizon=10, dt=0.1, dynamics="flightmare")
@@ -56,28 +56,66 @@ step on the module's six live parameters plus its residual); `params` is then
 None - the module has no parameter struct.
 `evaluate_cartpole.Evaluator(MPC(...), env)` flies whole batches of episodes
 with the solver inside the closed-loop kernel
-(functional.cartpole_mpc_closed_loop)."""
+(functional.cartpole_mpc_closed_loop).
+
+The fixed wing (scripts/evaluate_fixed_wing.py:232-243):
+
+    mpc = MPC(horizon=10, dt=0.05, dynamics="fixed_wing_3D")
+    action = mpc.predict_actions(current_state, target)        # [1, 4]
+
+Kept from the reference (_initParamsFixedWing_3D, mpc.py:135-150): the action
+box [0, 1], an action cost on the three control surfaces only, around 0.5 (its
+_Q_u = diag(0, 10, 10, 10): the thrust is free), the FixedWingDynamics model
+with `modified_params`, the warm start by shifting, and the call surface
+(state, target point).  What differs:
+  * the cost is the TRAINING loss on the training reference (fixed_wing_mpc_loss
+    against WingDataset._compute_target_pos: rows p0 + n (12 dt) (k + 1) towards
+    the target, every row with its cost), so that the MPC optimum and a policy's
+    loss are the same quantity (functional.wing_policy_optimality_gap); the
+    reference's NLP (preprocess_fixed_wing, mpc.py:383-414) spaces its points
+    by the current speed, |v| dt per step, weights the position with 1000 and
+    the surfaces with 10 (here 10 and 0.1, the training loss's) and drops the
+    last stage's state cost;
+  * one horizon, 10, with the model's dt equal to the plant's (the reference's
+    evaluation uses horizon 20 at dt 0.1 on a plant stepped at 0.05);
+  * the solver is the same first-order single shooting (apg_wing_mpc_solve),
+    from u = (0.25, 0.5, 0.5, 0.5);
+  * no `learnt_model`: planning through a LearntFixedWingDynamics module is not
+    built.
+`evaluate_fixed_wing.FixedWingEvaluator(MPC(...), FixedWingDynamics())` flies
+whole batches of target lists with the solver inside the closed-loop kernel
+(functional.wing_mpc_closed_loop): plant = the evaluator's environment, model =
+this object's parameters.  Other fixed-wing names of the reference
+("fixed_wing", "fixed_wing_2D") are not implemented."""
 import numpy as np
 import torch
 
 from .. import functional as F
 from ..dynamics.cartpole_dynamics import CartpoleDynamics, LearntCartpoleDynamics
+from ..dynamics.fixed_wing_dynamics import FixedWingDynamics
 from ..dynamics.quad_dynamics_flightmare import FlightmareDynamics
 
-DYNAMICS = ("flightmare", "cartpole")
+DYNAMICS = ("flightmare", "cartpole", "fixed_wing_3D")
 
 
 class MPC:
 
     def __init__(self, horizon=10, dt=0.1, dynamics="flightmare", modified_params={},
                  iters=10, beta=None, alpha_thrust=None, alpha_rate=None, alpha=None,
-                 device=None, learnt_model=None, **kwargs):
+                 alpha_surface=None, device=None, learnt_model=None, **kwargs):
         if dynamics not in DYNAMICS:
             raise NotImplementedError(
                 f"MPC dynamics {dynamics!r}: implemented here: {', '.join(DYNAMICS)} "
-                "(the quadrotor and the cart-pole; no fixed-wing MPC)")
+                "(the quadrotor, the cart-pole and the 3D fixed wing)")
         if horizon not in (5, 10):
             raise ValueError("the batched MPC is built for horizon 5 or 10")
+        if dynamics == "fixed_wing_3D":
+            if horizon != 10:
+                raise ValueError("the batched fixed-wing MPC is built for horizon 10")
+            if learnt_model is not None:
+                raise NotImplementedError(
+                    "learnt_model: planning through a LearntFixedWingDynamics module is "
+                    "not built (dynamics='flightmare' and 'cartpole' take one)")
         if learnt_model is not None:
             cart_module = isinstance(learnt_model, LearntCartpoleDynamics)
             if cart_module != (dynamics == "cartpole"):
@@ -99,6 +137,10 @@ class MPC:
         if dynamics == "cartpole":
             self.model = CartpoleDynamics(modified_params)
             self.options = dict(iters=iters, beta=beta, alpha=alpha)
+        elif dynamics == "fixed_wing_3D":
+            self.model = FixedWingDynamics(modified_params)
+            self.options = dict(iters=iters, beta=beta, alpha_thrust=alpha_thrust,
+                                alpha_surface=alpha_surface)
         else:
             self.model = FlightmareDynamics(modified_params=modified_params)
             self.options = dict(iters=iters, beta=beta, alpha_thrust=alpha_thrust,
@@ -116,7 +158,7 @@ class MPC:
 
     def reset(self):
         """Forget the warm start: the next call starts from u = 0.5 (the
-        cart-pole: u = 0)."""
+        cart-pole: u = 0; the fixed wing: (0.25, 0.5, 0.5, 0.5))."""
         self.warm_start = None
         self.last_cost = None
 
@@ -149,7 +191,32 @@ class MPC:
     def predict_actions(self, current_state, ref_states=None):
         if self.dynamics_model == "cartpole":
             return self._predict_cartpole(current_state)
+        if self.dynamics_model == "fixed_wing_3D":
+            return self._predict_wing(current_state, ref_states)
         return self._predict_quad(current_state, ref_states)
+
+    def _predict_wing(self, current_state, target):
+        """current_state [12] + target [3] (numpy) -> np.ndarray [1,4] like the
+        reference; [B,12] + [B,3] tensors -> tensor [B,4].  The reference rows
+        are built here (functional.wing_mpc_reference); the warm start lives in
+        the object and is shifted per call."""
+        numpy_in = not torch.is_tensor(current_state)
+        dev = torch.device(self.device or
+                           ("cuda" if numpy_in else current_state.device))
+        s = torch.as_tensor(np.asarray(current_state, dtype=np.float32) if numpy_in
+                            else current_state).to(dev, torch.float32)
+        t = torch.as_tensor(np.asarray(target, dtype=np.float32) if numpy_in
+                            else target).to(dev, torch.float32)
+        if s.dim() == 1:
+            s, t = s[None], t[None]
+        if s.dim() != 2 or s.shape[1] != 12 or t.shape != (s.shape[0], 3):
+            raise ValueError("state [B,12] and target [B,3] expected")
+        ref = F.wing_mpc_reference(s, t, self.dt, self.horizon)
+        res = F.wing_mpc_solve(s, ref, self.dt, self.params,
+                               u0=self._shifted_warm_start(s.shape[0]), **self.options)
+        self.warm_start, self.last_cost = res["u"], res["cost"]
+        action = res["u"][:, 0]
+        return action.cpu().numpy() if numpy_in else action
 
     def _predict_quad(self, current_state, ref_states):
         """current_state [12] + ref_states [H,9] (numpy, rows as

@@ -34,6 +34,7 @@
 #include "static_dispatch.h"
 #include "wing_learnt_math.h"
 #include "wing_math.h"
+#include "wing_mpc_math.h"
 #include "wing_rollout_math.h"
 
 using namespace apg;
@@ -1278,6 +1279,75 @@ int apg_cartpole_learnt_mpc_closed_loop_cpu(const float *state0, float dt,
   return cart_mpc_loop_twin(state0, dt, plant, plant_learnt, CartMpcLearnt{c, rows.data()},
                             *opt, B, H, max_steps, mode, thresh_div, burn_in,
                             CartLoopOut{steps, upright, vel_sum, vel_sq, states, actions, cost});
+}
+
+}  // extern "C"
+
+// ------------------------------------------------ shooting MPC, fixed wing
+// apg_cpu_wing_mpc.h: the solver and the flight of wing_mpc_math.h looped over
+// the batch; the forward sweep's stash is a local array in place of the LDS
+extern "C" {
+
+int apg_wing_mpc_solve_cpu(const float *state0, const float *ref, float dt,
+                           const ApgWingParams *model, const ApgWingLossWeights *weights,
+                           const ApgWingMpcOptions *opt, int B, int H, float *u,
+                           float *cost_out, float *cost_trace) {
+  if (const char *e = wing_mpc_check(model, weights, opt, B, H)) return fail("%s", e);
+  if (B == 0) return APG_OK;
+  if (!state0 || !ref || !u || !cost_out) return fail("NULL buffer");
+  constexpr int kH = 10;
+  const WingConst c = make_const(*model, dt);
+  const size_t Bs = (size_t)B;
+  float pre[kH][12];
+  for (size_t b = 0; b < Bs; ++b) {
+    float s0[12], ul[kH][4];
+    for (int i = 0; i < 12; ++i) s0[i] = state0[i * Bs + b];
+    for (int k = 0; k < kH; ++k)
+      for (int j = 0; j < 4; ++j) ul[k][j] = u[((size_t)k * 4 + j) * Bs + b];
+    cost_out[b] = wing_mpc_solve<kH>(
+        s0,
+        [&](int k, float (&rp)[3]) {
+          for (int i = 0; i < 3; ++i) rp[i] = ref[((size_t)k * 3 + i) * Bs + b];
+        },
+        ul, c, *weights, *opt, [&](int k, int i) -> float & { return pre[k][i]; },
+        [&](int i, float J) {
+          if (cost_trace) cost_trace[(size_t)i * Bs + b] = J;
+        });
+    for (int k = 0; k < kH; ++k)
+      for (int j = 0; j < 4; ++j) u[((size_t)k * 4 + j) * Bs + b] = ul[k][j];
+  }
+  return APG_OK;
+}
+
+int apg_wing_mpc_closed_loop_cpu(const float *targets, int n_targets, const float *state0,
+                                 float dt, const ApgWingParams *plant,
+                                 const ApgWingParams *model, const ApgWingLossWeights *weights,
+                                 const ApgWingMpcOptions *opt, int B, int H, int max_steps,
+                                 float thresh_div, float thresh_stable, int test_time,
+                                 float *div_linear, float *div_pass, float *div_fail,
+                                 int *steps, float *drone, float *seen, float *cost) {
+  if (const char *e = wing_mpc_check(model, weights, opt, B, H)) return fail("%s", e);
+  if (const char *e = wing_mpc_check_flight(plant, n_targets, max_steps)) return fail("%s", e);
+  if (B == 0) return APG_OK;
+  if (!targets || !div_linear || !div_pass || !div_fail || !steps) return fail("NULL buffer");
+  constexpr int kH = 10;
+  const WingConst cp = make_const(*plant, dt), cm = make_const(*model, dt);
+  const WingFlightRule rule{thresh_div, thresh_stable, 11.5f, n_targets, test_time ? 1 : 0,
+                            max_steps};
+  const size_t Bs = (size_t)B;
+  float pre[kH][12];
+  for (size_t b = 0; b < Bs; ++b)
+    steps[b] = wing_mpc_flight<kH>(
+        state0 != nullptr, [&](int i) { return state0[i * Bs + b]; },
+        [&](int ti, float (&t)[3]) {
+          for (int j = 0; j < 3; ++j) t[j] = targets[((size_t)ti * 3 + j) * Bs + b];
+        },
+        [&](float (&s)[12], const float (&a)[4]) { wing_step<true>(s, a, cp); }, cm, *weights,
+        *opt, rule,
+        WingMpcFlightLog{div_linear, div_pass, div_fail, drone, seen, cost, Bs, b},
+        [&](int k, int i) -> float & { return pre[k][i]; }, [](bool alive) { return alive; },
+        true);
+  return APG_OK;
 }
 
 }  // extern "C"

@@ -15,7 +15,11 @@ Same names, arguments and statistics as the reference evaluator:
     `np.random.seed` makes both evaluators fly the same flights, and returns
     (mean, std) of the per-flight mean target error, or the per-flight means
     with return_dists.
-There is no renderer and no MPC baseline here (out of scope)."""
+A controller that is an `MPC(dynamics="fixed_wing_3D")` (controllers/mpc.py; the
+baseline of scripts/evaluate_fixed_wing.py:232-243) is flown the same way with
+the solver inside the kernel (apg_wing_mpc_closed_loop): plant = the
+environment's parameters, model = the MPC's own; there is no self play with it.
+There is no renderer here (out of scope)."""
 import numpy as np
 import torch
 
@@ -41,7 +45,8 @@ class FixedWingEvaluator:
 
     def __init__(self, controller, env, dt=0.01, horizon=1, render=0,
                  thresh_div=10, thresh_stable=0.8, test_time=0, **kwargs):
-        """controller: a FixedWingNetWrapper; env: the FixedWingDynamics the
+        """controller: a FixedWingNetWrapper, or an MPC(dynamics="fixed_wing_3D")
+        (then env must be an analytic FixedWingDynamics); env: the FixedWingDynamics the
         reference's SimpleWingEnv steps with (or an object with `.dynamics`);
         its `.params` are used - or, after train_dynamics() (scripts/
         train_fixed_wing.py:42-43), a LearntFixedWingDynamics module: the kernel
@@ -57,6 +62,12 @@ class FixedWingEvaluator:
         if self.learnt is None and isinstance(self.dynamics, torch.nn.Module):
             raise TypeError(
                 f"no closed-loop kernel steps through {type(self.dynamics).__name__}")
+        self.mpc = getattr(controller, "dynamics_model", None) == "fixed_wing_3D"
+        if self.mpc and self.learnt is not None:
+            raise TypeError(
+                "the fixed-wing MPC closed loop flies the analytic FixedWingDynamics only "
+                "(got a LearntFixedWingDynamics environment)")
+        self.last_flights = None
         self.dt = dt
         self.horizon = horizon
         self.thresh_div = thresh_div
@@ -67,6 +78,17 @@ class FixedWingEvaluator:
     # ------------------------------------------------------------- one launch
     def _closed_loop(self, targets, max_steps, want_trajectory):
         c = self.controller
+        if self.mpc:
+            if abs(c.dt - self.dt) > 1e-9:
+                raise ValueError(f"the MPC's model dt ({c.dt}) must equal the "
+                                 f"evaluator's dt ({self.dt})")
+            dev = torch.device(c.device or "cuda")
+            targets = torch.as_tensor(np.asarray(targets), dtype=torch.float32)
+            return F.wing_mpc_closed_loop(
+                targets.to(dev), self.dt, self.dynamics.params, model_params=c.params,
+                max_steps=max_steps, thresh_div=self.thresh_div,
+                thresh_stable=self.thresh_stable, test_time=int(bool(self.test_time)),
+                want_trajectory=want_trajectory, **c.options)
         d = c.dataset
         dev = next(c.net.parameters()).device
         targets = torch.as_tensor(np.asarray(targets), dtype=torch.float32)
@@ -118,9 +140,13 @@ class FixedWingEvaluator:
         """One launch for all flights + the self play that goes with it."""
         # the per-step rows (31 floats x max_steps per flight) only when they
         # are returned or feed the self play
-        collecting = getattr(self.controller.dataset, "num_self_play", 0) > 0
-        out = self._closed_loop(targets, max_steps, return_traj or collecting)
-        self._self_play(out)
+        if self.mpc:             # (an MPC has no data set: no self play)
+            out = self._closed_loop(targets, max_steps, return_traj)
+        else:
+            collecting = getattr(self.controller.dataset, "num_self_play", 0) > 0
+            out = self._closed_loop(targets, max_steps, return_traj or collecting)
+            self._self_play(out)
+        self.last_flights = out
         return out
 
     def fly_to_point(self, target_points, max_steps=1000, do_avg_act=0,

@@ -2291,6 +2291,146 @@ def wing_mlp_closed_loop(net, targets, dt, params, mean, std, data_dt=0.05,
     return out
 
 
+# ------------------------------------------ batched shooting MPC, fixed wing
+WING_MPC_DEFAULTS = dict(iters=10, beta=0.5, alpha_thrust=0.03, alpha_surface=0.03)
+WING_MPC_START = (0.25, 0.5, 0.5, 0.5)
+
+
+def wing_mpc_options(iters=None, beta=None, alpha_thrust=None, alpha_surface=None):
+    """ApgWingMpcOptions (include/apg.h); None = the default of WING_MPC_DEFAULTS."""
+    given = dict(iters=iters, beta=beta, alpha_thrust=alpha_thrust,
+                 alpha_surface=alpha_surface)
+    o = {k: WING_MPC_DEFAULTS[k] if v is None else v for k, v in given.items()}
+    return _capi.ApgWingMpcOptions(int(o["iters"]), float(o["beta"]),
+                                   float(o["alpha_thrust"]), float(o["alpha_surface"]))
+
+
+def wing_mpc_reference(state0, target, dt, horizon=10):
+    """The reference rows [B,H,3] a fixed-wing policy is trained on and the
+    closed loop builds per control step: p0 + n (12 dt) (k + 1), n the unit vector
+    from the position p0 of state0 [B,12] to target [B,3]
+    (WingDataset._compute_target_pos, neural_control/dataset.py:309-320)."""
+    p0 = state0[:, :3]
+    rel = target - p0
+    # term by term, in the closed-loop kernel's order: the rows are its rows, bit
+    # for bit (the root through float64: correctly rounded like the kernel's sqrtf,
+    # which a float32 torch.sqrt is not on every backend)
+    n2 = rel[:, :1] * rel[:, :1] + rel[:, 1:2] * rel[:, 1:2] + rel[:, 2:] * rel[:, 2:]
+    nv = rel / torch.sqrt(n2.double()).to(rel.dtype) * (12 * dt)
+    k = torch.arange(1, horizon + 1, dtype=state0.dtype, device=state0.device)
+    return p0[:, None] + nv[:, None] * k[None, :, None]
+
+
+def wing_mpc_solve(state0, ref, dt, params, u0=None, weights=None, iters=None, beta=None,
+                   alpha_thrust=None, alpha_surface=None, want_trace=False):
+    """One shooting-MPC solve per trajectory in one launch (apg_wing_mpc_solve):
+    `iters` iterations of projected heavy-ball descent on fixed_wing_mpc_loss of
+    the 10-step unroll of the model `params` from state0 [B,12] against the
+    positions ref [B,10,3], actions boxed to [0, 1].  u0 [B,10,4]: the start
+    (None: (0.25, 0.5, 0.5, 0.5) in every row); it is not written.  Returns
+    dict(u [B,10,4], cost [B] = the cost of u, trace [iters+1,B] with want_trace:
+    the cost before every iteration and at the end, else None)."""
+    if ref.dim() != 3 or state0.dim() != 2:
+        raise ValueError("state0 [B,12] and ref [B,H,3] expected")
+    B, H, C = ref.shape
+    if state0.shape != (B, 12) or C != 3 or (u0 is not None and tuple(u0.shape) != (B, H, 4)):
+        raise ValueError("inconsistent MPC shapes: state0 [B,12], ref [B,H,3], u0 [B,H,4]")
+    dev = state0.device
+    s = _f32c(state0).t().contiguous()
+    r = _f32c(ref).permute(1, 2, 0).contiguous()
+    if u0 is None:
+        u = torch.tensor(WING_MPC_START, dtype=torch.float32, device=dev)
+        u = u[None, :, None].expand(H, 4, B).contiguous()
+    else:
+        u = _f32c(u0).permute(1, 2, 0).contiguous()
+        if u.data_ptr() == u0.data_ptr():
+            u = u.clone()           # in: start, out: solution
+    require_device(s, r, u)
+    opt = wing_mpc_options(iters, beta, alpha_thrust, alpha_surface)
+    weights = weights or wing_loss_weights()
+    cost = torch.empty(B, dtype=torch.float32, device=dev)
+    trace = (torch.empty(opt.iters + 1, B, dtype=torch.float32, device=dev)
+             if want_trace else None)
+    check(lib().apg_wing_mpc_solve(
+        ptr(s), ptr(r), float(dt), ctypes.byref(params), ctypes.byref(weights),
+        ctypes.byref(opt), B, H, ptr(u), ptr(cost), ptr(trace), stream_of(s)),
+        "apg_wing_mpc_solve")
+    return dict(u=u.permute(2, 0, 1).contiguous(), cost=cost, trace=trace)
+
+
+def wing_mpc_closed_loop(targets, dt, params, model_params=None, state0=None, weights=None,
+                         max_steps=1000, thresh_div=10.0, thresh_stable=0.8, test_time=0,
+                         want_trajectory=False, **options):
+    """wing_mlp_closed_loop with the policy replaced by the shooting MPC: per
+    control step "shift the warm start, build the reference rows from the state
+    the controller sees and the current target, solve, apply u[0]", every flight
+    of the batch in one launch (apg_wing_mpc_closed_loop).  `params` steps the
+    flight; `model_params` is what the solver plans with (None: `params` - the
+    nominal case; other parameters: the model-mismatch experiment).  options:
+    iters, beta, alpha_thrust, alpha_surface.  Returns the dict
+    wing_mlp_closed_loop returns, plus cost [T,B]: the solver's cost at every
+    control step."""
+    if targets.dim() != 3 or targets.shape[2] != 3:
+        raise ValueError(f"targets [B, n_targets, 3] expected, got {tuple(targets.shape)}")
+    B, n_targets, _ = targets.shape
+    dev = targets.device
+    tg = _f32c(targets).permute(1, 2, 0).contiguous()
+    s0 = None if state0 is None else to_soa(state0)
+    require_device(tg, s0)
+    opt = wing_mpc_options(**options)
+    weights = weights or wing_loss_weights()
+    model = params if model_params is None else model_params
+    T = int(max_steps)
+    new = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+    div_linear, div_pass, div_fail, cost = new(T, B), new(T, B), new(T, B), new(T, B)
+    steps = torch.zeros(B, dtype=torch.int32, device=dev)
+    drone = new(T, 16, B) if want_trajectory else None
+    seen = new(T, 15, B) if want_trajectory else None
+    check(lib().apg_wing_mpc_closed_loop(
+        ptr(tg), n_targets, ptr(s0), float(dt), ctypes.byref(params), ctypes.byref(model),
+        ctypes.byref(weights), ctypes.byref(opt), B, 10, T, float(thresh_div),
+        float(thresh_stable), int(test_time), ptr(div_linear), ptr(div_pass), ptr(div_fail),
+        steps.data_ptr(), ptr(drone), ptr(seen), ptr(cost), stream_of(tg)),
+        "apg_wing_mpc_closed_loop")
+    out = dict(div_linear=div_linear, div_pass=div_pass, div_fail=div_fail, steps=steps,
+               cost=cost)
+    if want_trajectory:
+        out.update(drone=drone, seen=seen)
+    return out
+
+
+def wing_policy_actions(net, mean, std, state0, ref):
+    """The action plan [B,10,4] a fixed-wing policy commits to from state0
+    [B,12] on the reference rows ref [B,10,3]: for a `Net(9, 1, 3, 40,
+    conv=False)`, sigmoid(net(normed, ref[:, -1] - p0)) with normed = ((state0 -
+    mean) / std)[:, 3:] (WingDataset.prepare_data; mean / std: the data set's 12
+    normalisation values).  The module's own forward is the policy here - the
+    object under judgement, evaluated once."""
+    if net.fc_out.weight.shape[0] != 40:
+        raise ValueError("Net(9, 1, 3, 40, conv=False) expected")
+    s = _f32c(state0)
+    mean = torch.as_tensor(mean, dtype=torch.float32, device=s.device)
+    std = torch.as_tensor(std, dtype=torch.float32, device=s.device)
+    with torch.no_grad():
+        normed = ((s - mean) / std)[:, 3:]
+        in_ref = _f32c(ref)[:, -1] - s[:, :3]
+        return torch.sigmoid(net(normed, in_ref)).reshape(-1, 10, 4).contiguous()
+
+
+def wing_policy_optimality_gap(net, mean, std, state0, ref, dt, params, iters=50):
+    """How far is a fixed-wing policy from what the optimiser reaches on the same
+    reference rows, the same cost and the same model?  Per trajectory: the cost
+    of the policy's action plan (wing_policy_actions), the MPC cost after
+    `iters` iterations started AT that plan, and the MPC cost after `iters`
+    iterations from the cold start.  Returns dict(policy [B], mpc_from_policy
+    [B], mpc [B], actions [B,10,4])."""
+    acts = wing_policy_actions(net, mean, std, state0, ref)
+    policy = wing_mpc_solve(state0, ref, dt, params, u0=acts, iters=0)["cost"]
+    warm = wing_mpc_solve(state0, ref, dt, params, u0=acts, iters=iters)["cost"]
+    cold = wing_mpc_solve(state0, ref, dt, params, iters=iters)["cost"]
+    return dict(policy=policy, mpc_from_policy=warm, mpc=cold, actions=acts)
+
+
 CARTPOLE_MODES = {"balance": 0, "swingup": 1}
 
 

@@ -1551,6 +1551,56 @@ int apg_cartpole_learnt_mpc_closed_loop(const float *state0, float dt,
                                         double *vel_sq, float *states, float *actions,
                                         float *cost, apg_stream_t stream);
 
+/* ---------------------------------------------- fixed wing, shooting MPC --- */
+/* Batched shooting MPC for the fixed wing - the comparator of the reference's
+ * fixed-wing evaluation (scripts/evaluate_fixed_wing.py:232-243: MPC(...,
+ * dynamics="fixed_wing_3D")), by the method of apg_quad_mpc_solve: single
+ * shooting with projected heavy-ball descent, one trajectory per lane
+ * (csrc/wing_mpc_math.h).  Kept from the reference
+ * (neural_control/controllers/mpc.py:135-150 _initParamsFixedWing_3D): the
+ * action box [0, 1], an action cost on the three control surfaces only (its
+ * _Q_u = diag(0, 10, 10, 10)), the model (the step of apg_wing_step_fwd), the
+ * warm start by shifting.  The cost is the training loss on the training
+ * reference (apg_wing_rollout_fwd_bwd's fixed_wing_mpc_loss):
+ *   J = pos sum_k |p_{k+1} - ref_k|^2 + action sum_k sum_{j=1..3} (u_kj - 1/2)^2
+ *   u <- clamp(u - m, 0, 1),  m <- beta m + alpha_c dJ/du   (alpha_thrust for
+ *   column 0, alpha_surface for columns 1..3; m = 0 at the start of a solve; a
+ *   fixed number of iterations)
+ * Reference defaults: iters 10, beta 0.5, alpha_thrust = alpha_surface = 0.03
+ * (DESIGN.md 7 has the float64 sweep behind them). */
+typedef struct ApgWingMpcOptions {
+  int iters;
+  float beta, alpha_thrust, alpha_surface;
+} ApgWingMpcOptions;
+
+/* One solve per trajectory, SoA only: state0 [12][B]; ref [H][3][B] the
+ * positions the states AFTER steps 0..H-1 are held against; u [H][4][B] in:
+ * the start, out: the solution; cost_out [B] = J(u); cost_trace [iters + 1][B]
+ * or NULL: row i = J before iteration i, row iters = cost_out.  H = 10. */
+int apg_wing_mpc_solve(const float *state0, const float *ref, float dt,
+                       const ApgWingParams *model, const ApgWingLossWeights *weights,
+                       const ApgWingMpcOptions *opt, int B, int H, float *u, float *cost_out,
+                       float *cost_trace, apg_stream_t stream);
+
+/* apg_wing_mlp_closed_loop with the policy replaced by "shift the warm start
+ * (rows move up, the last one is repeated; not at step 0, kept through a
+ * reset), solve from the state the controller sees, apply u[0]" (first step:
+ * from u = (0.25, 0.5, 0.5, 0.5)): the same flight rule, the same outputs and
+ * shapes, plus cost [T][B] or NULL (cost_out of every solve).  The reference
+ * rows of a solve are ref_k = obs_pos + n (12 dt) (k + 1), n the unit vector from
+ * obs_pos to the current target (WingDataset._compute_target_pos with the data
+ * set's dt equal to dt): what a policy is trained on.  `plant` steps the
+ * flight, `model` is what the solver plans with (the plant's parameters for the
+ * nominal case, others for the model-mismatch experiment).  H = 10,
+ * n_targets >= 1, max_steps >= 1. */
+int apg_wing_mpc_closed_loop(const float *targets, int n_targets, const float *state0,
+                             float dt, const ApgWingParams *plant, const ApgWingParams *model,
+                             const ApgWingLossWeights *weights, const ApgWingMpcOptions *opt,
+                             int B, int H, int max_steps, float thresh_div,
+                             float thresh_stable, int test_time, float *div_linear,
+                             float *div_pass, float *div_fail, int *steps, float *drone,
+                             float *seen, float *cost, apg_stream_t stream);
+
 /* ------------------------------------------------------- launch chain --- */
 /* A chain of deferred-loss rollout launches run as TWO overlapping lanes.
  * Launched one `after` the other through the entry points above, kernel i+1

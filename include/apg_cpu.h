@@ -117,4 +117,6 @@ const char *apg_cpu_last_error_string(void);
 #include "apg_cpu_learnt.h"
 /* the shooting MPC's twins (apg_quad_mpc_*_cpu) */
 #include "apg_cpu_mpc.h"
+/* the fixed-wing shooting MPC's twins (apg_wing_mpc_*_cpu) */
+#include "apg_cpu_wing_mpc.h"
 #endif /* APG_CPU_H_ */
