@@ -77,6 +77,23 @@ class ApgQuadFlight(ctypes.Structure):
                     "div", "steps", "drone", "actions", "start_states")]
 
 
+class ApgCartpoleFlight(ctypes.Structure):
+    """include/apg.h: starts, rule and log of a closed-loop cart-pole flight."""
+    _fields_ = [("state0", ctypes.c_void_p), ("max_steps", ctypes.c_int),
+                ("mode", ctypes.c_int), ("thresh_div", ctypes.c_float),
+                ("burn_in", ctypes.c_int)] + [(n, ctypes.c_void_p) for n in (
+                    "steps", "upright", "vel_sum", "vel_sq", "states", "actions")]
+
+
+class ApgWingFlight(ctypes.Structure):
+    """include/apg.h: targets, start, rule and log of a closed-loop fixed-wing flight."""
+    _fields_ = [("targets", ctypes.c_void_p), ("state0", ctypes.c_void_p),
+                ("n_targets", ctypes.c_int), ("max_steps", ctypes.c_int),
+                ("thresh_div", ctypes.c_float), ("thresh_stable", ctypes.c_float),
+                ("test_time", ctypes.c_int)] + [(n, ctypes.c_void_p) for n in (
+                    "div_linear", "div_pass", "div_fail", "steps", "drone", "seen")]
+
+
 class ApgQuadMpcOptions(ctypes.Structure):
     """include/apg.h: the shooting MPC's iteration count and step rule."""
     _fields_ = [("iters", ctypes.c_int), ("beta", ctypes.c_float),
@@ -416,11 +433,10 @@ SIGNATURES = {
         _P, _P, _P, _P, ctypes.POINTER(ApgWingPolicyGrads), _P, _P,
         ctypes.POINTER(ApgWingSgdUpdate), _P],
     "apg_wing_mlp_closed_loop": [
-        _P, _I, _P, _F, ctypes.POINTER(ApgWingParams), ctypes.POINTER(ctypes.c_float),
-        ctypes.POINTER(ApgLearntResidual),
+        ctypes.POINTER(ApgWingFlight), _F, ctypes.POINTER(ApgWingParams),
+        ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ApgLearntResidual),
         ctypes.POINTER(ApgWingPolicy), ctypes.POINTER(ctypes.c_float),
-        ctypes.POINTER(ctypes.c_float), _F, _I, _I, _I, _F, _F, _I, _P, _P, _P,
-        _P, _P, _P, _P, _P],
+        ctypes.POINTER(ctypes.c_float), _F, _I, _I, _P, _P],
     "apg_planes_gemm_workspace_floats": [_I, _I, _I, _I],
     "apg_planes_gemm_default_wgs": [_I, _I, _I, _I],
     "apg_planes_gemm_multi_workspace_floats": [ctypes.POINTER(ApgGemmProblem), _I],
@@ -453,8 +469,8 @@ SIGNATURES = {
                                  _I, _I, _I, _P, _P],
     "apg_cartpole_policy_workspace_floats": [],
     "apg_cartpole_mlp_closed_loop": [
-        _P, _F, ctypes.POINTER(ApgCartpoleParams), ctypes.POINTER(ApgCartpolePolicy),
-        _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+        ctypes.POINTER(ApgCartpoleFlight), _F, ctypes.POINTER(ApgCartpoleParams),
+        ctypes.POINTER(ApgCartpolePolicy), _I, _P, _P],
     "apg_cartpole_mlp_train_step_workspace_floats": [_I, _I],
     "apg_cartpole_mlp_train_step": [
         _P, _P, _F, ctypes.POINTER(ApgCartpoleParams), ctypes.POINTER(ApgCartpolePolicy),
@@ -478,8 +494,8 @@ SIGNATURES = {
         _I, _I, _P, _P, ctypes.POINTER(ApgCartpolePolicyGrads), _P, _P,
         ctypes.POINTER(ApgCartpoleSgdUpdate), _P],
     "apg_cartpole_learnt_mlp_closed_loop": [
-        _P, _F, ctypes.POINTER(ApgCartpoleLearnt), ctypes.POINTER(ApgCartpolePolicy),
-        _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+        ctypes.POINTER(ApgCartpoleFlight), _F, ctypes.POINTER(ApgCartpoleLearnt),
+        ctypes.POINTER(ApgCartpolePolicy), _I, _P, _P],
     "apg_quad_mpc_solve": [
         _P, _P, _I, _F, ctypes.POINTER(ApgQuadParams),
         ctypes.POINTER(ApgQuadLossWeights), ctypes.POINTER(ApgQuadMpcOptions), _I, _I,
@@ -504,23 +520,23 @@ SIGNATURES = {
         _P, _P, _F, ctypes.POINTER(ApgCartpoleParams),
         ctypes.POINTER(ApgCartpoleMpcOptions), _I, _I, _P, _P, _P, _P],
     "apg_cartpole_mpc_closed_loop": [
-        _P, _F, ctypes.POINTER(ApgCartpoleParams), ctypes.POINTER(ApgCartpoleLearnt),
-        ctypes.POINTER(ApgCartpoleParams), ctypes.POINTER(ApgCartpoleMpcOptions),
-        _I, _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+        ctypes.POINTER(ApgCartpoleFlight), _F, ctypes.POINTER(ApgCartpoleParams),
+        ctypes.POINTER(ApgCartpoleLearnt), ctypes.POINTER(ApgCartpoleParams),
+        ctypes.POINTER(ApgCartpoleMpcOptions), _I, _I, _P, _P],
     "apg_cartpole_learnt_mpc_solve": [
         _P, _P, _F, ctypes.POINTER(ApgCartpoleLearnt),
         ctypes.POINTER(ApgCartpoleMpcOptions), _I, _I, _P, _P, _P, _P],
     "apg_cartpole_learnt_mpc_closed_loop": [
-        _P, _F, ctypes.POINTER(ApgCartpoleParams), ctypes.POINTER(ApgCartpoleLearnt),
-        ctypes.POINTER(ApgCartpoleLearnt), ctypes.POINTER(ApgCartpoleMpcOptions),
-        _I, _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+        ctypes.POINTER(ApgCartpoleFlight), _F, ctypes.POINTER(ApgCartpoleParams),
+        ctypes.POINTER(ApgCartpoleLearnt), ctypes.POINTER(ApgCartpoleLearnt),
+        ctypes.POINTER(ApgCartpoleMpcOptions), _I, _I, _P, _P],
     "apg_wing_mpc_solve": [
         _P, _P, _F, ctypes.POINTER(ApgWingParams), ctypes.POINTER(ApgWingLossWeights),
         ctypes.POINTER(ApgWingMpcOptions), _I, _I, _P, _P, _P, _P],
     "apg_wing_mpc_closed_loop": [
-        _P, _I, _P, _F, ctypes.POINTER(ApgWingParams), ctypes.POINTER(ApgWingParams),
-        ctypes.POINTER(ApgWingLossWeights), ctypes.POINTER(ApgWingMpcOptions), _I, _I, _I,
-        _F, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+        ctypes.POINTER(ApgWingFlight), _F, ctypes.POINTER(ApgWingParams),
+        ctypes.POINTER(ApgWingParams), ctypes.POINTER(ApgWingLossWeights),
+        ctypes.POINTER(ApgWingMpcOptions), _I, _I, _P, _P],
     "apg_launch_chain_prepare": [_P],
     "apg_launch_chain_flush": [_P],
     "apg_launch_chain_set_lane_priority": [_I],

@@ -168,76 +168,53 @@ class MPC:
         w = self.warm_start
         return torch.cat((w[:, 1:], w[:, -1:]), 1)
 
-    def _predict_cartpole(self, current_state):
-        """current_state [4] (numpy) -> np.ndarray [1,1], what the reference's
-        Evaluator wraps in torch.tensor([...]); a tensor [B,4] -> tensor [B,1]."""
+    def predict_actions(self, current_state, ref_states=None):
+        """The first action of this call's solve.  numpy in - a state [S] and,
+        for the quadrotor, ref_states [H,9] (rows as `preprocess_quad` lays them
+        out: columns 0:3 position, 6:9 velocity), for the fixed wing the target
+        [3], for the cart-pole nothing - gives np.ndarray [1,A] like the
+        reference (what its Evaluator wraps in torch.tensor([...])); tensors
+        with a leading batch dimension give a tensor [B,A].  The warm start
+        lives in the object and is shifted per call."""
         numpy_in = not torch.is_tensor(current_state)
         dev = torch.device(self.device or
                            ("cuda" if numpy_in else current_state.device))
-        s = torch.as_tensor(np.asarray(current_state, dtype=np.float32) if numpy_in
-                            else current_state).to(dev, torch.float32)
+
+        def on_device(x):
+            return torch.as_tensor(np.asarray(x, dtype=np.float32) if numpy_in
+                                   else x).to(dev, torch.float32)
+        s = on_device(current_state)
+        r = None if self.dynamics_model == "cartpole" else on_device(ref_states)
         if s.dim() == 1:
-            s = s[None]
-        if s.dim() != 2 or s.shape[1] != 4:
-            raise ValueError(f"state [4] or [B,4] expected, got {tuple(s.shape)}")
-        planner = {} if self.learnt_model is None else dict(learnt=self.learnt_model)
-        res = F.cartpole_mpc_solve(s, self.dt, self.params,
-                                   u0=self._shifted_warm_start(s.shape[0]),
-                                   horizon=self.horizon, **self.options, **planner)
+            s, r = s[None], None if r is None else r[None]
+        solve = {"cartpole": self._solve_cartpole, "fixed_wing_3D": self._solve_wing,
+                 "flightmare": self._solve_quad}[self.dynamics_model]
+        res = solve(s, r)
         self.warm_start, self.last_cost = res["u"], res["cost"]
         action = res["u"][:, 0]
         return action.cpu().numpy() if numpy_in else action
 
-    def predict_actions(self, current_state, ref_states=None):
-        if self.dynamics_model == "cartpole":
-            return self._predict_cartpole(current_state)
-        if self.dynamics_model == "fixed_wing_3D":
-            return self._predict_wing(current_state, ref_states)
-        return self._predict_quad(current_state, ref_states)
+    def _planner(self):
+        return {} if self.learnt_model is None else dict(learnt=self.learnt_model)
 
-    def _predict_wing(self, current_state, target):
-        """current_state [12] + target [3] (numpy) -> np.ndarray [1,4] like the
-        reference; [B,12] + [B,3] tensors -> tensor [B,4].  The reference rows
-        are built here (functional.wing_mpc_reference); the warm start lives in
-        the object and is shifted per call."""
-        numpy_in = not torch.is_tensor(current_state)
-        dev = torch.device(self.device or
-                           ("cuda" if numpy_in else current_state.device))
-        s = torch.as_tensor(np.asarray(current_state, dtype=np.float32) if numpy_in
-                            else current_state).to(dev, torch.float32)
-        t = torch.as_tensor(np.asarray(target, dtype=np.float32) if numpy_in
-                            else target).to(dev, torch.float32)
-        if s.dim() == 1:
-            s, t = s[None], t[None]
+    def _solve_cartpole(self, s, _):
+        if s.dim() != 2 or s.shape[1] != 4:
+            raise ValueError(f"state [4] or [B,4] expected, got {tuple(s.shape)}")
+        return F.cartpole_mpc_solve(s, self.dt, self.params,
+                                    u0=self._shifted_warm_start(s.shape[0]),
+                                    horizon=self.horizon, **self.options, **self._planner())
+
+    def _solve_wing(self, s, t):
+        """The reference rows are built here (functional.wing_mpc_reference)."""
         if s.dim() != 2 or s.shape[1] != 12 or t.shape != (s.shape[0], 3):
             raise ValueError("state [B,12] and target [B,3] expected")
         ref = F.wing_mpc_reference(s, t, self.dt, self.horizon)
-        res = F.wing_mpc_solve(s, ref, self.dt, self.params,
-                               u0=self._shifted_warm_start(s.shape[0]), **self.options)
-        self.warm_start, self.last_cost = res["u"], res["cost"]
-        action = res["u"][:, 0]
-        return action.cpu().numpy() if numpy_in else action
+        return F.wing_mpc_solve(s, ref, self.dt, self.params,
+                                u0=self._shifted_warm_start(s.shape[0]), **self.options)
 
-    def _predict_quad(self, current_state, ref_states):
-        """current_state [12] + ref_states [H,9] (numpy, rows as
-        `preprocess_quad` lays them out: columns 0:3 position, 6:9 velocity) ->
-        np.ndarray [1,4] like the reference; [B,12] + [B,H,9] tensors -> tensor
-        [B,4].  The warm start lives in the object and is shifted per call."""
-        numpy_in = not torch.is_tensor(current_state)
-        dev = torch.device(self.device or
-                           ("cuda" if numpy_in else current_state.device))
-        s = torch.as_tensor(np.asarray(current_state, dtype=np.float32) if numpy_in
-                            else current_state).to(dev, torch.float32)
-        r = torch.as_tensor(np.asarray(ref_states, dtype=np.float32) if numpy_in
-                            else ref_states).to(dev, torch.float32)
-        if s.dim() == 1:
-            s, r = s[None], r[None]
+    def _solve_quad(self, s, r):
         if r.shape[1:] != (self.horizon, 9) or s.shape != (r.shape[0], 12):
             raise ValueError(f"state [B,12] and reference rows [B,{self.horizon},9] expected")
-        planner = {} if self.learnt_model is None else dict(learnt=self.learnt_model)
-        res = F.quad_mpc_solve(s, r, self.dt, self.params,
-                               u0=self._shifted_warm_start(s.shape[0]), **self.options,
-                               **planner)
-        self.warm_start, self.last_cost = res["u"], res["cost"]
-        action = res["u"][:, 0]
-        return action.cpu().numpy() if numpy_in else action
+        return F.quad_mpc_solve(s, r, self.dt, self.params,
+                                u0=self._shifted_warm_start(s.shape[0]), **self.options,
+                                **self._planner())

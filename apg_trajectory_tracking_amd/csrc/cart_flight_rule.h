@@ -5,6 +5,8 @@
 // flight stops, the upright flag and the fp64 sums.  Restated from
 // scripts/evaluate_cartpole.py:79-318 and neural_control/environments/
 // cartpole_env.py:57-82, as cart_closed_loop_kernel (mlp_cartpole.hip) has it.
+// The argument rules of an ApgCartpoleFlight (cart_flight_check) are stated
+// here for every entry point, mlp_cartpole.hip's included.
 #pragma once
 #include <math.h>
 
@@ -61,10 +63,14 @@ struct CartFlightRule {
   }
 };
 
-// argument rules of the closed-loop entry points; NULL: fine
-inline const char *cart_flight_check(int B, int max_steps, int mode) {
-  if (B < 1 || max_steps < 1) return "B and max_steps must be >= 1";
-  if (mode != APG_CARTPOLE_BALANCE && mode != APG_CARTPOLE_SWINGUP) return "unknown mode";
+// Argument rules of an ApgCartpoleFlight, shared by the four device entry
+// points and the host twins; NULL: fine, and `rule` is filled in
+inline const char *cart_flight_check(const ApgCartpoleFlight *f, int B, CartFlightRule *rule) {
+  if (!f) return "flight is NULL";
+  if (B < 1 || f->max_steps < 1) return "B and max_steps must be >= 1";
+  if (f->mode != APG_CARTPOLE_BALANCE && f->mode != APG_CARTPOLE_SWINGUP) return "unknown mode";
+  if (!f->state0 || !f->steps || !f->upright || !f->vel_sum || !f->vel_sq) return "NULL buffer";
+  *rule = CartFlightRule{f->max_steps, f->mode, f->burn_in, f->thresh_div};
   return nullptr;
 }
 

@@ -224,21 +224,18 @@ int cart_mpc_solve_launch(const char *name, const float *state0, const float *u0
 
 // The closed loop behind both entry points, Args / Model as above.
 template <class Args, class Model>
-int cart_mpc_loop_launch(const char *name, const float *state0, float dt,
+int cart_mpc_loop_launch(const char *name, const ApgCartpoleFlight *flight, float dt,
                          const ApgCartpoleParams *plant, const ApgCartpoleLearnt *plant_learnt,
                          const Model *model, const ApgCartpoleMpcOptions *opt, int B, int H,
-                         int max_steps, int mode, float thresh_div, int burn_in, int *steps,
-                         int *upright, double *vel_sum, double *vel_sq, float *states,
-                         float *actions, float *cost, apg_stream_t stream) {
+                         float *cost, apg_stream_t stream) {
+  Args A = {};
   if (const char *e = cart_mpc_check(model, opt, H)) return fail_arg(e);
   if (!plant && !plant_learnt) return fail_arg("plant is NULL");
   if (const char *e = cart_mpc_check_learnt(plant_learnt)) return fail_arg(e);
-  if (const char *e = cart_flight_check(B, max_steps, mode)) return fail_arg(e);
-  if (!state0 || !steps || !upright || !vel_sum || !vel_sq) return fail_arg("NULL buffer");
-  Args A = {};
-  A.state0 = state0, A.steps = steps, A.upright = upright;
-  A.vel_sum = vel_sum, A.vel_sq = vel_sq;
-  A.log = {states, actions, cost, 0, 0};
+  if (const char *e = cart_flight_check(flight, B, &A.rule)) return fail_arg(e);
+  A.state0 = flight->state0, A.steps = flight->steps, A.upright = flight->upright;
+  A.vel_sum = flight->vel_sum, A.vel_sq = flight->vel_sq;
+  A.log = {flight->states, flight->actions, cost, 0, 0};
   if (plant_learnt) {
     A.m = *plant_learnt;
     A.cp.dt = dt;          // (the rest is built in the kernel from the tensors)
@@ -247,7 +244,6 @@ int cart_mpc_loop_launch(const char *name, const float *state0, float dt,
   }
   set_model(A, *model, dt);
   A.o = *opt, A.B = B;
-  A.rule = CartFlightRule{max_steps, mode, burn_in, thresh_div};
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((B + kCartMpcThreads - 1) / kCartMpcThreads), block(kCartMpcThreads);
   with_horizon(H, [&](auto h) {
@@ -279,16 +275,14 @@ int apg_cartpole_mpc_solve(const float *state0, const float *u0, float dt,
                                                  opt, B, H, u, cost_out, cost_trace, stream);
 }
 
-int apg_cartpole_mpc_closed_loop(const float *state0, float dt, const ApgCartpoleParams *plant,
+int apg_cartpole_mpc_closed_loop(const ApgCartpoleFlight *flight, float dt,
+                                 const ApgCartpoleParams *plant,
                                  const ApgCartpoleLearnt *plant_learnt,
                                  const ApgCartpoleParams *model,
-                                 const ApgCartpoleMpcOptions *opt, int B, int H, int max_steps,
-                                 int mode, float thresh_div, int burn_in, int *steps,
-                                 int *upright, double *vel_sum, double *vel_sq, float *states,
-                                 float *actions, float *cost, apg_stream_t stream) {
-  return cart_mpc_loop_launch<CartMpcLoopArgs>(
-      "cartpole_mpc_closed_loop", state0, dt, plant, plant_learnt, model, opt, B, H, max_steps,
-      mode, thresh_div, burn_in, steps, upright, vel_sum, vel_sq, states, actions, cost, stream);
+                                 const ApgCartpoleMpcOptions *opt, int B, int H,
+                                 float *cost, apg_stream_t stream) {
+  return cart_mpc_loop_launch<CartMpcLoopArgs>("cartpole_mpc_closed_loop", flight, dt, plant,
+                                               plant_learnt, model, opt, B, H, cost, stream);
 }
 
 int apg_cartpole_learnt_mpc_solve(const float *state0, const float *u0, float dt,
@@ -300,19 +294,15 @@ int apg_cartpole_learnt_mpc_solve(const float *state0, const float *u0, float dt
                                                        cost_trace, stream);
 }
 
-int apg_cartpole_learnt_mpc_closed_loop(const float *state0, float dt,
+int apg_cartpole_learnt_mpc_closed_loop(const ApgCartpoleFlight *flight, float dt,
                                         const ApgCartpoleParams *plant,
                                         const ApgCartpoleLearnt *plant_learnt,
                                         const ApgCartpoleLearnt *model,
                                         const ApgCartpoleMpcOptions *opt, int B, int H,
-                                        int max_steps, int mode, float thresh_div, int burn_in,
-                                        int *steps, int *upright, double *vel_sum,
-                                        double *vel_sq, float *states, float *actions,
                                         float *cost, apg_stream_t stream) {
-  return cart_mpc_loop_launch<CartLearntMpcLoopArgs>(
-      "cartpole_learnt_mpc_closed_loop", state0, dt, plant, plant_learnt, model, opt, B, H,
-      max_steps, mode, thresh_div, burn_in, steps, upright, vel_sum, vel_sq, states, actions,
-      cost, stream);
+  return cart_mpc_loop_launch<CartLearntMpcLoopArgs>("cartpole_learnt_mpc_closed_loop", flight,
+                                                     dt, plant, plant_learnt, model, opt, B, H,
+                                                     cost, stream);
 }
 
 }  // extern "C"

@@ -1166,24 +1166,18 @@ int cart_mpc_solve_twin(const float *state0, const float *u0, const Model &c,
   return APG_OK;
 }
 
-struct CartLoopOut {
-  int *steps, *upright;
-  double *vel_sum, *vel_sq;
-  float *states, *actions, *cost;
-};
-
 template <int H, class Model>
-void cart_mpc_loop_batch(const float *state0, const CartConst &cp, const float *rows,
+void cart_mpc_loop_batch(const ApgCartpoleFlight &out, const CartConst &cp, const float *rows,
                          const Model &cm, const ApgCartpoleMpcOptions &o,
-                         const CartFlightRule &rule, int B, const CartLoopOut &out) {
+                         const CartFlightRule &rule, int B, float *cost) {
   const size_t Bs = (size_t)B;
   for (size_t b = 0; b < Bs; ++b) {
     float s0[4];
-    for (int i = 0; i < 4; ++i) s0[i] = state0[i * Bs + b];
+    for (int i = 0; i < 4; ++i) s0[i] = out.state0[i * Bs + b];
     const CartFlightBook f = cart_mpc_flight<H>(
         s0, [&](float (&s)[4], float a) { cart_learnt_step(s, a, cp, rows); },
         [](bool alive) { return alive; }, cm, o, rule,
-        CartMpcFlightLog{out.states, out.actions, out.cost, Bs, b}, true);
+        CartMpcFlightLog{out.states, out.actions, cost, Bs, b}, true);
     out.steps[b] = f.steps, out.upright[b] = f.upright ? 1 : 0;
     out.vel_sum[b] = f.vel_sum, out.vel_sq[b] = f.vel_sq;
   }
@@ -1192,15 +1186,14 @@ void cart_mpc_loop_batch(const float *state0, const CartConst &cp, const float *
 // the closed loop behind both twins, after the model's own check: the plant's
 // checks and setup, then the flights on the model `cm`
 template <class Model>
-int cart_mpc_loop_twin(const float *state0, float dt, const ApgCartpoleParams *plant,
-                       const ApgCartpoleLearnt *plant_learnt, const Model &cm,
-                       const ApgCartpoleMpcOptions &o, int B, int H, int max_steps, int mode,
-                       float thresh_div, int burn_in, const CartLoopOut &out) {
+int cart_mpc_loop_twin(const ApgCartpoleFlight *flight, float dt,
+                       const ApgCartpoleParams *plant, const ApgCartpoleLearnt *plant_learnt,
+                       const Model &cm, const ApgCartpoleMpcOptions &o, int B, int H,
+                       float *cost) {
+  CartFlightRule rule;
   if (!plant && !plant_learnt) return fail("plant is NULL");
   if (const char *e = cart_mpc_check_learnt(plant_learnt)) return fail("%s", e);
-  if (const char *e = cart_flight_check(B, max_steps, mode)) return fail("%s", e);
-  if (!state0 || !out.steps || !out.upright || !out.vel_sum || !out.vel_sq)
-    return fail("NULL buffer");
+  if (const char *e = cart_flight_check(flight, B, &rule)) return fail("%s", e);
   CartConst cp;
   std::vector<float> rows;
   if (plant_learnt) {
@@ -1210,11 +1203,10 @@ int cart_mpc_loop_twin(const float *state0, float dt, const ApgCartpoleParams *p
     cp = make_const(*plant, dt);
   }
   const float *r = plant_learnt ? rows.data() : nullptr;   // NULL: cart_step alone
-  const CartFlightRule rule{max_steps, mode, burn_in, thresh_div};
   if (H == 5)
-    cart_mpc_loop_batch<5>(state0, cp, r, cm, o, rule, B, out);
+    cart_mpc_loop_batch<5>(*flight, cp, r, cm, o, rule, B, cost);
   else
-    cart_mpc_loop_batch<10>(state0, cp, r, cm, o, rule, B, out);
+    cart_mpc_loop_batch<10>(*flight, cp, r, cm, o, rule, B, cost);
   return APG_OK;
 }
 
@@ -1232,20 +1224,15 @@ int apg_cartpole_mpc_solve_cpu(const float *state0, const float *u0, float dt,
                              u, cost_out, cost_trace);
 }
 
-int apg_cartpole_mpc_closed_loop_cpu(const float *state0, float dt,
+int apg_cartpole_mpc_closed_loop_cpu(const ApgCartpoleFlight *flight, float dt,
                                      const ApgCartpoleParams *plant,
                                      const ApgCartpoleLearnt *plant_learnt,
                                      const ApgCartpoleParams *model,
                                      const ApgCartpoleMpcOptions *opt, int B, int H,
-                                     int max_steps, int mode, float thresh_div, int burn_in,
-                                     int *steps, int *upright, double *vel_sum,
-                                     double *vel_sq, float *states, float *actions,
                                      float *cost) {
   if (const char *e = cart_mpc_check(model, opt, H)) return fail("%s", e);
-  return cart_mpc_loop_twin(state0, dt, plant, plant_learnt,
-                            CartMpcAnalytic{make_const(*model, dt)}, *opt, B, H, max_steps,
-                            mode, thresh_div, burn_in,
-                            CartLoopOut{steps, upright, vel_sum, vel_sq, states, actions, cost});
+  return cart_mpc_loop_twin(flight, dt, plant, plant_learnt,
+                            CartMpcAnalytic{make_const(*model, dt)}, *opt, B, H, cost);
 }
 
 int apg_cartpole_learnt_mpc_solve_cpu(const float *state0, const float *u0, float dt,
@@ -1262,23 +1249,19 @@ int apg_cartpole_learnt_mpc_solve_cpu(const float *state0, const float *u0, floa
                              cost_out, cost_trace);
 }
 
-int apg_cartpole_learnt_mpc_closed_loop_cpu(const float *state0, float dt,
+int apg_cartpole_learnt_mpc_closed_loop_cpu(const ApgCartpoleFlight *flight, float dt,
                                             const ApgCartpoleParams *plant,
                                             const ApgCartpoleLearnt *plant_learnt,
                                             const ApgCartpoleLearnt *model,
                                             const ApgCartpoleMpcOptions *opt, int B, int H,
-                                            int max_steps, int mode, float thresh_div,
-                                            int burn_in, int *steps, int *upright,
-                                            double *vel_sum, double *vel_sq, float *states,
-                                            float *actions, float *cost) {
+                                            float *cost) {
   if (const char *e = cart_mpc_check(model, opt, H)) return fail("%s", e);
   CartLearntParams p;
   CartConst c;
   std::vector<float> rows;
   learnt_setup(*model, dt, p, c, rows);
-  return cart_mpc_loop_twin(state0, dt, plant, plant_learnt, CartMpcLearnt{c, rows.data()},
-                            *opt, B, H, max_steps, mode, thresh_div, burn_in,
-                            CartLoopOut{steps, upright, vel_sum, vel_sq, states, actions, cost});
+  return cart_mpc_loop_twin(flight, dt, plant, plant_learnt, CartMpcLearnt{c, rows.data()},
+                            *opt, B, H, cost);
 }
 
 }  // extern "C"
@@ -1319,32 +1302,28 @@ int apg_wing_mpc_solve_cpu(const float *state0, const float *ref, float dt,
   return APG_OK;
 }
 
-int apg_wing_mpc_closed_loop_cpu(const float *targets, int n_targets, const float *state0,
-                                 float dt, const ApgWingParams *plant,
-                                 const ApgWingParams *model, const ApgWingLossWeights *weights,
-                                 const ApgWingMpcOptions *opt, int B, int H, int max_steps,
-                                 float thresh_div, float thresh_stable, int test_time,
-                                 float *div_linear, float *div_pass, float *div_fail,
-                                 int *steps, float *drone, float *seen, float *cost) {
+int apg_wing_mpc_closed_loop_cpu(const ApgWingFlight *flight, float dt,
+                                 const ApgWingParams *plant, const ApgWingParams *model,
+                                 const ApgWingLossWeights *weights,
+                                 const ApgWingMpcOptions *opt, int B, int H, float *cost) {
+  WingFlightRule rule;
   if (const char *e = wing_mpc_check(model, weights, opt, B, H)) return fail("%s", e);
-  if (const char *e = wing_mpc_check_flight(plant, n_targets, max_steps)) return fail("%s", e);
+  if (const char *e = wing_mpc_check_flight(plant, flight, B, &rule)) return fail("%s", e);
   if (B == 0) return APG_OK;
-  if (!targets || !div_linear || !div_pass || !div_fail || !steps) return fail("NULL buffer");
   constexpr int kH = 10;
   const WingConst cp = make_const(*plant, dt), cm = make_const(*model, dt);
-  const WingFlightRule rule{thresh_div, thresh_stable, 11.5f, n_targets, test_time ? 1 : 0,
-                            max_steps};
+  const ApgWingFlight &f = *flight;
   const size_t Bs = (size_t)B;
   float pre[kH][12];
   for (size_t b = 0; b < Bs; ++b)
-    steps[b] = wing_mpc_flight<kH>(
-        state0 != nullptr, [&](int i) { return state0[i * Bs + b]; },
+    f.steps[b] = wing_mpc_flight<kH>(
+        f.state0 != nullptr, [&](int i) { return f.state0[i * Bs + b]; },
         [&](int ti, float (&t)[3]) {
-          for (int j = 0; j < 3; ++j) t[j] = targets[((size_t)ti * 3 + j) * Bs + b];
+          for (int j = 0; j < 3; ++j) t[j] = f.targets[((size_t)ti * 3 + j) * Bs + b];
         },
         [&](float (&s)[12], const float (&a)[4]) { wing_step<true>(s, a, cp); }, cm, *weights,
         *opt, rule,
-        WingMpcFlightLog{div_linear, div_pass, div_fail, drone, seen, cost, Bs, b},
+        WingMpcFlightLog{f.div_linear, f.div_pass, f.div_fail, f.drone, f.seen, cost, Bs, b},
         [&](int k, int i) -> float & { return pre[k][i]; }, [](bool alive) { return alive; },
         true);
   return APG_OK;

@@ -36,6 +36,7 @@
 #include <type_traits>
 
 #include "apg_device.h"
+#include "cart_flight_rule.h"
 #include "cartpole_learnt_math.h"
 #include "cartpole_math.h"
 #include "policy_mfma.h"
@@ -280,11 +281,9 @@ __global__ __launch_bounds__(kMaxWaves * 64) void cart_closed_loop_kernel(
 
 // argument checks and the two launches of both entry points; `learnt` NULL:
 // the analytic environment on `params`
-int closed_loop(const float *state0, float dt, const ApgCartpoleParams *params,
+int closed_loop(const ApgCartpoleFlight *flight, float dt, const ApgCartpoleParams *params,
                 const ApgCartpoleLearnt *learnt, const ApgCartpolePolicy *policy, int B,
-                int max_steps, int mode, float thresh_div, int burn_in, int *steps,
-                int *upright, double *vel_sum, double *vel_sq, float *states,
-                float *actions, float *workspace, apg_stream_t stream) {
+                float *workspace, apg_stream_t stream) {
   if (!(params || learnt) || !policy) {
     set_error("%s / policy is NULL", learnt ? "model" : "params");
     return APG_ERR_ARG;
@@ -298,25 +297,24 @@ int closed_loop(const float *state0, float dt, const ApgCartpoleParams *params,
     set_error("policy weight pointer is NULL");
     return APG_ERR_ARG;
   }
-  if (B <= 0 || max_steps <= 0) {
-    set_error("B and max_steps must be >= 1 (got %d, %d)", B, max_steps);
+  CartFlightRule rule;
+  if (const char *e = cart_flight_check(flight, B, &rule)) {
+    set_error("%s", e);
     return APG_ERR_ARG;
   }
-  if (mode != APG_CARTPOLE_BALANCE && mode != APG_CARTPOLE_SWINGUP) {
-    set_error("unknown mode %d", mode);
-    return APG_ERR_ARG;
-  }
-  if ((long long)B * 4 * 4 * (long long)max_steps >= (1ll << 32) - 64) {
+  // this loop's own rules: plane offsets are 32-bit, the tables need a workspace
+  if ((long long)B * 4 * 4 * (long long)rule.T >= (1ll << 32) - 64) {
     set_error("B x max_steps too large for 32-bit plane offsets; split the batch");
     return APG_ERR_ARG;
   }
-  if (!state0 || !steps || !upright || !vel_sum || !vel_sq || !workspace) {
+  if (!workspace) {
     set_error("NULL buffer");
     return APG_ERR_ARG;
   }
   CartLearntLoopArgs A = {};
-  A.state0 = state0, A.steps = steps, A.upright = upright;
-  A.vel_sum = vel_sum, A.vel_sq = vel_sq, A.states = states, A.actions = actions;
+  A.state0 = flight->state0, A.steps = flight->steps, A.upright = flight->upright;
+  A.vel_sum = flight->vel_sum, A.vel_sq = flight->vel_sq;
+  A.states = flight->states, A.actions = flight->actions;
   A.tables = workspace;
   if (learnt) {
     A.c.dt = dt;          // (the rest is built in the kernel from the tensors)
@@ -324,8 +322,8 @@ int closed_loop(const float *state0, float dt, const ApgCartpoleParams *params,
   } else {
     A.c = make_const(*params, dt);
   }
-  A.thresh_div = thresh_div;
-  A.B = B, A.T = max_steps, A.mode = mode, A.burn_in = burn_in;
+  A.thresh_div = rule.thresh_div;
+  A.B = B, A.T = rule.T, A.mode = rule.mode, A.burn_in = rule.burn_in;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(cart_pack16_kernel, dim3((nBlocks16 * 256 + 255) / 256), dim3(256), 0,
                      st, *policy, workspace);
@@ -351,33 +349,22 @@ extern "C" {
 
 int apg_cartpole_policy_workspace_floats(void) { return kCartLds; }
 
-int apg_cartpole_mlp_closed_loop(const float *state0, float dt,
+int apg_cartpole_mlp_closed_loop(const ApgCartpoleFlight *flight, float dt,
                                  const ApgCartpoleParams *params,
-                                 const ApgCartpolePolicy *policy, int B, int max_steps,
-                                 int mode, float thresh_div, int burn_in, int *steps,
-                                 int *upright, double *vel_sum, double *vel_sq,
-                                 float *states, float *actions, float *workspace,
-                                 apg_stream_t stream) {
-  return closed_loop(state0, dt, params, nullptr, policy, B, max_steps, mode, thresh_div,
-                     burn_in, steps, upright, vel_sum, vel_sq, states, actions, workspace,
-                     stream);
+                                 const ApgCartpolePolicy *policy, int B,
+                                 float *workspace, apg_stream_t stream) {
+  return closed_loop(flight, dt, params, nullptr, policy, B, workspace, stream);
 }
 
-int apg_cartpole_learnt_mlp_closed_loop(const float *state0, float dt,
+int apg_cartpole_learnt_mlp_closed_loop(const ApgCartpoleFlight *flight, float dt,
                                         const ApgCartpoleLearnt *model,
                                         const ApgCartpolePolicy *policy, int B,
-                                        int max_steps, int mode, float thresh_div,
-                                        int burn_in, int *steps, int *upright,
-                                        double *vel_sum, double *vel_sq, float *states,
-                                        float *actions, float *workspace,
-                                        apg_stream_t stream) {
+                                        float *workspace, apg_stream_t stream) {
   if (!model) {
     set_error("model / policy is NULL");
     return APG_ERR_ARG;
   }
-  return closed_loop(state0, dt, nullptr, model, policy, B, max_steps, mode, thresh_div,
-                     burn_in, steps, upright, vel_sum, vel_sq, states, actions, workspace,
-                     stream);
+  return closed_loop(flight, dt, nullptr, model, policy, B, workspace, stream);
 }
 
 }  // extern "C"

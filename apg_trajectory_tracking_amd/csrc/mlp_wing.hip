@@ -24,6 +24,7 @@
 #include "policy_mfma16.h"
 #include "wing_math.h"
 #include "learnt_residual.h"
+#include "wing_flight_rule.h"
 #include "wing_learnt_math.h"
 #include "wing_rollout_math.h"
 
@@ -309,7 +310,7 @@ __global__ __launch_bounds__(kThreads) void wing_closed_loop_kernel(WingLoopArgs
   float s[12], obs[12], line[3], prev[3];
 #pragma unroll
   for (int i = 0; i < 12; ++i) s[i] = Ps0.ld(vb, i * pN);
-  if (!A.state0) s[3] = 11.5f;
+  if (!A.state0) s[3] = kWingDesSpeed;
 #pragma unroll
   for (int i = 0; i < 12; ++i) obs[i] = s[i];
 #pragma unroll
@@ -979,14 +980,11 @@ int apg_wing_policy_bwd(const float *actions, const float *grad_actions,
   return check_launch("wing_policy_bwd");
 }
 
-int apg_wing_mlp_closed_loop(const float *targets, int n_targets, const float *state0,
-                             float dt, const ApgWingParams *params, const float *inertia,
+int apg_wing_mlp_closed_loop(const ApgWingFlight *flight, float dt,
+                             const ApgWingParams *params, const float *inertia,
                              const ApgLearntResidual *learnt, const ApgWingPolicy *policy,
                              const float *mean, const float *std, float data_dt,
-                             int data_horizon, int B, int max_steps, float thresh_div,
-                             float thresh_stable, int test_time, float *div_linear,
-                             float *div_pass, float *div_fail, int *steps, float *drone,
-                             float *seen, float *workspace, apg_stream_t stream) {
+                             int data_horizon, int B, float *workspace, apg_stream_t stream) {
   if (int e = check_wing_policy(policy, B)) return e;
   if ((inertia != nullptr) != (learnt != nullptr)) {
     set_error("learnt environment: `inertia` and `learnt` come together");
@@ -1000,9 +998,16 @@ int apg_wing_mlp_closed_loop(const float *targets, int n_targets, const float *s
     set_error("params / mean / std is NULL");
     return APG_ERR_ARG;
   }
-  if (n_targets < 1 || max_steps < 0 || data_horizon < 1) {
-    set_error("n_targets >= 1, max_steps >= 0, data_horizon >= 1 (got %d, %d, %d)",
-              n_targets, max_steps, data_horizon);
+  WingFlightRule rule;
+  if (const char *e = wing_flight_check(flight, B, &rule)) {
+    set_error("%s", e);
+    return APG_ERR_ARG;
+  }
+  // this loop's own rules: no step is a no-op, plane offsets are 32-bit, the
+  // tables need a workspace
+  const int n_targets = rule.n_targets, max_steps = rule.T;
+  if (max_steps < 0 || data_horizon < 1) {
+    set_error("max_steps >= 0, data_horizon >= 1 (got %d, %d)", max_steps, data_horizon);
     return APG_ERR_ARG;
   }
   const long long widest = 16ll * max_steps > 3ll * n_targets ? 16ll * max_steps
@@ -1012,7 +1017,7 @@ int apg_wing_mlp_closed_loop(const float *targets, int n_targets, const float *s
     return APG_ERR_ARG;
   }
   if (B == 0 || max_steps == 0) return APG_OK;
-  if (!targets || !div_linear || !div_pass || !div_fail || !steps || !workspace) {
+  if (!workspace) {
     set_error("NULL buffer");
     return APG_ERR_ARG;
   }
@@ -1023,17 +1028,19 @@ int apg_wing_mlp_closed_loop(const float *targets, int n_targets, const float *s
     attr.set();
   }
   WingLoopArgs A = {};
-  A.targets = targets, A.state0 = state0, A.div_linear = div_linear;
-  A.div_pass = div_pass, A.div_fail = div_fail, A.steps = steps, A.drone = drone;
-  A.seen = seen, A.tables = workspace;
+  A.targets = flight->targets, A.state0 = flight->state0;
+  A.div_linear = flight->div_linear, A.div_pass = flight->div_pass;
+  A.div_fail = flight->div_fail, A.steps = flight->steps, A.drone = flight->drone;
+  A.seen = flight->seen, A.tables = workspace;
   if (learnt) A.k = make_general_const(*params, dt, inertia);
   else static_cast<WingConst &>(A.k) = make_const(*params, dt);
   for (int j = 0; j < kNS; ++j) A.mean[j] = mean[3 + j], A.std[j] = std[3 + j];
   // `ref_vector * vec_len_per_step * (i + 1)`: the Python double 12 * dt enters
   // the float32 tensor product rounded to float32 (dataset.py:312-319)
   A.vec_len = (float)(12.0 * (double)data_dt), A.horizon = (float)data_horizon;
-  A.thresh_div = thresh_div, A.thresh_stable = thresh_stable, A.des_speed = 11.5f;
-  A.B = B, A.T = max_steps, A.n_targets = n_targets, A.test_time = test_time;
+  A.thresh_div = rule.thresh_div, A.thresh_stable = rule.thresh_stable;
+  A.des_speed = rule.des_speed;
+  A.B = B, A.T = max_steps, A.n_targets = n_targets, A.test_time = flight->test_time;
   PackArgs P;
   P.pol = *policy, P.dst = workspace, P.head_rows = 4;
   hipStream_t st = (hipStream_t)stream;

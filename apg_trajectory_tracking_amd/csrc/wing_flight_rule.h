@@ -10,7 +10,9 @@
 // Shared by wing_mpc_closed_loop_kernel (wing_mpc.hip, one flight per lane) and
 // its host twin (cpu_twins.hip).  wing_closed_loop_kernel (mlp_wing.hip) has
 // the same rule written inline around its MFMA policy, 32 flights per wave;
-// oracle.torch_port.wing_closed_loop is its restatement.
+// oracle.torch_port.wing_closed_loop is its restatement.  The argument rules of
+// an ApgWingFlight (wing_flight_check) and the reset speed are stated here for
+// all three.
 #pragma once
 #include <math.h>
 
@@ -19,10 +21,27 @@
 namespace apg {
 namespace {
 
+// the speed of SimpleWingEnv.zero_reset and of a flight put back onto its line
+constexpr float kWingDesSpeed = 11.5f;
+
 struct WingFlightRule {
   float thresh_div, thresh_stable, des_speed;
   int n_targets, test_time, T;
 };
+
+// Argument rules of an ApgWingFlight, shared by the two device entry points and
+// the host twin; NULL: fine, and `rule` is filled in.  What max_steps may be is
+// the entry point's own rule (include/apg.h).
+inline const char *wing_flight_check(const ApgWingFlight *f, int B, WingFlightRule *rule) {
+  if (!f) return "flight is NULL";
+  if (f->n_targets < 1) return "n_targets must be >= 1";
+  if (B > 0 && f->max_steps > 0 &&
+      (!f->targets || !f->div_linear || !f->div_pass || !f->div_fail || !f->steps))
+    return "NULL buffer";
+  *rule = WingFlightRule{f->thresh_div, f->thresh_stable, kWingDesSpeed, f->n_targets,
+                         f->test_time ? 1 : 0, f->max_steps};
+  return nullptr;
+}
 
 // a + ab (ab . (p - a)) / |ab|^2, and a itself for a degenerate line
 __host__ __device__ __forceinline__ void wing_project_to_line(const float (&a)[3],
@@ -57,13 +76,13 @@ struct WingFlightStep {
   float div, d_pass, d_fail;
 };
 
-// state0: the start, or NULL for zero_reset (zeros, u = 11.5); load(i): its
+// state0: the start, or NULL for zero_reset (zeros, u = kWingDesSpeed); load(i): its
 // component i
 template <class Load>
 __host__ __device__ __forceinline__ void wing_flight_start(WingFlightBook &f, bool given,
                                                            Load &&load, bool live) {
 #pragma unroll
-  for (int i = 0; i < 12; ++i) f.s[i] = given ? load(i) : (i == 3 ? 11.5f : 0.f);
+  for (int i = 0; i < 12; ++i) f.s[i] = given ? load(i) : (i == 3 ? kWingDesSpeed : 0.f);
 #pragma unroll
   for (int i = 0; i < 12; ++i) f.obs[i] = f.s[i];
 #pragma unroll

@@ -132,25 +132,20 @@ int apg_wing_mpc_solve(const float *state0, const float *ref, float dt,
   return check_launch("wing_mpc_solve");
 }
 
-int apg_wing_mpc_closed_loop(const float *targets, int n_targets, const float *state0,
-                             float dt, const ApgWingParams *plant, const ApgWingParams *model,
-                             const ApgWingLossWeights *weights, const ApgWingMpcOptions *opt,
-                             int B, int H, int max_steps, float thresh_div,
-                             float thresh_stable, int test_time, float *div_linear,
-                             float *div_pass, float *div_fail, int *steps, float *drone,
-                             float *seen, float *cost, apg_stream_t stream) {
-  if (const char *e = wing_mpc_check(model, weights, opt, B, H)) return fail_arg(e);
-  if (const char *e = wing_mpc_check_flight(plant, n_targets, max_steps)) return fail_arg(e);
-  if (B == 0) return APG_OK;
-  if (!targets || !div_linear || !div_pass || !div_fail || !steps)
-    return fail_arg("NULL buffer");
+int apg_wing_mpc_closed_loop(const ApgWingFlight *flight, float dt,
+                             const ApgWingParams *plant, const ApgWingParams *model,
+                             const ApgWingLossWeights *weights,
+                             const ApgWingMpcOptions *opt, int B, int H,
+                             float *cost, apg_stream_t stream) {
   WingMpcLoopArgs A;
-  A.targets = targets, A.state0 = state0, A.steps = steps;
-  A.log = {div_linear, div_pass, div_fail, drone, seen, cost, 0, 0};
+  if (const char *e = wing_mpc_check(model, weights, opt, B, H)) return fail_arg(e);
+  if (const char *e = wing_mpc_check_flight(plant, flight, B, &A.rule)) return fail_arg(e);
+  if (B == 0) return APG_OK;
+  A.targets = flight->targets, A.state0 = flight->state0, A.steps = flight->steps;
+  A.log = {flight->div_linear, flight->div_pass, flight->div_fail, flight->drone,
+           flight->seen, cost, 0, 0};
   A.cp = make_const(*plant, dt), A.cm = make_const(*model, dt);
   A.w = *weights, A.o = *opt, A.B = B;
-  A.rule = WingFlightRule{thresh_div, thresh_stable, 11.5f, n_targets, test_time ? 1 : 0,
-                          max_steps};
   const dim3 grid((B + kWingMpcThreads - 1) / kWingMpcThreads), block(kWingMpcThreads);
   hipLaunchKernelGGL(wing_mpc_closed_loop_kernel<kWingMpcH>, grid, block, 0,
                      (hipStream_t)stream, A);

@@ -254,10 +254,13 @@ inline const char *wing_mpc_check(const ApgWingParams *model, const ApgWingLossW
   return nullptr;
 }
 
-inline const char *wing_mpc_check_flight(const ApgWingParams *plant, int n_targets, int T) {
+// the closed loop's plant and flight (wing_flight_check, and this loop's own
+// rule: at least one step); NULL: fine, and `rule` is filled in
+inline const char *wing_mpc_check_flight(const ApgWingParams *plant, const ApgWingFlight *f,
+                                         int B, WingFlightRule *rule) {
   if (!plant) return "plant is NULL";
-  if (n_targets < 1) return "n_targets must be >= 1";
-  if (T < 1) return "max_steps must be >= 1";
+  if (const char *e = wing_flight_check(f, B, rule)) return e;
+  if (f->max_steps < 1) return "max_steps must be >= 1";
   return nullptr;
 }
 

@@ -2009,6 +2009,62 @@ class _QuadFlight:
         self.ref = ctypes.byref(self.flight)
 
 
+class _WingFlight:
+    """What the two fixed-wing closed-loop wrappers share: the [n][3][B]
+    targets `tg`, the [12][B] start `s0` (None: zero_reset), T, the
+    zero-initialised outputs, the ApgWingFlight naming them (`ref`: by
+    reference) and the result dict `out`."""
+
+    def __init__(self, targets, state0, max_steps, thresh_div, thresh_stable, test_time,
+                 want_trajectory):
+        if targets.dim() != 3 or targets.shape[2] != 3:
+            raise ValueError(f"targets [B, n_targets, 3] expected, got {tuple(targets.shape)}")
+        self.B, n_targets, _ = targets.shape
+        B, dev = self.B, targets.device
+        self.tg = _f32c(targets).permute(1, 2, 0).contiguous()
+        self.s0 = None if state0 is None else to_soa(state0)
+        self.T = T = int(max_steps)
+        self.new = new = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+        self.out = dict(div_linear=new(T, B), div_pass=new(T, B), div_fail=new(T, B),
+                        steps=torch.zeros(B, dtype=torch.int32, device=dev))
+        if want_trajectory:
+            self.out.update(drone=new(T, 16, B), seen=new(T, 15, B))
+        self.flight = _capi.ApgWingFlight(
+            targets=ptr(self.tg), state0=ptr(self.s0), n_targets=n_targets, max_steps=T,
+            thresh_div=float(thresh_div), thresh_stable=float(thresh_stable),
+            test_time=int(test_time), **{k: ptr(v) for k, v in self.out.items()})
+        self.ref = ctypes.byref(self.flight)
+
+
+class _CartpoleFlight:
+    """What the two cart-pole closed-loop wrappers share: the checked mode, the
+    [4][B] starts `s0`, T, the zero-initialised outputs, the ApgCartpoleFlight
+    naming them (`ref`: by reference) and the result dict `out`."""
+
+    def __init__(self, state0, max_steps, mode, thresh_div, burn_in, want_trajectory):
+        m = CARTPOLE_MODES.get(mode, mode)
+        if m not in (0, 1):
+            raise ValueError(f"mode must be 'balance' or 'swingup', got {mode!r}")
+        if state0.dim() != 2 or state0.shape[1] != 4 or state0.shape[0] < 1:
+            raise ValueError(f"state0 [B, 4] expected, got {tuple(state0.shape)}")
+        self.B, self.T = B, T = state0.shape[0], int(max_steps)
+        if T < 1:
+            raise ValueError(f"max_steps must be >= 1, got {T}")
+        dev = state0.device
+        self.s0 = _f32c(state0).t().contiguous()
+        self.new = new = lambda *shape, dtype=torch.float32: torch.zeros(
+            shape, dtype=dtype, device=dev)
+        self.out = dict(steps=new(B, dtype=torch.int32), upright=new(B, dtype=torch.int32),
+                        vel_sum=new(B, dtype=torch.float64),
+                        vel_sq=new(B, dtype=torch.float64))
+        if want_trajectory:
+            self.out.update(states=new(T, 4, B), actions=new(T, B))
+        self.flight = _capi.ApgCartpoleFlight(
+            state0=ptr(self.s0), max_steps=T, mode=m, thresh_div=float(thresh_div),
+            burn_in=int(burn_in), **{k: ptr(v) for k, v in self.out.items()})
+        self.ref = ctypes.byref(self.flight)
+
+
 def quad_mlp_closed_loop(net, traj, dt, params, max_steps=251, thresh_div=1.0,
                          thresh_stable=1.0, test_time=0, want_trajectory=False,
                          learnt=None):
@@ -2043,12 +2099,16 @@ def quad_mlp_closed_loop(net, traj, dt, params, max_steps=251, thresh_div=1.0,
 MPC_DEFAULTS = dict(iters=10, beta=0.5, alpha_thrust=1.0 / 300.0, alpha_rate=1.0 / 10.0)
 
 
+def _mpc_options(struct, defaults, **given):
+    """An Apg*MpcOptions (include/apg.h) by field name; None = the default."""
+    o = {k: defaults[k] if v is None else v for k, v in given.items()}
+    return struct(**{k: int(v) if k == "iters" else float(v) for k, v in o.items()})
+
+
 def quad_mpc_options(iters=None, beta=None, alpha_thrust=None, alpha_rate=None):
-    """ApgQuadMpcOptions (include/apg.h); None = the default of MPC_DEFAULTS."""
-    given = dict(iters=iters, beta=beta, alpha_thrust=alpha_thrust, alpha_rate=alpha_rate)
-    o = {k: MPC_DEFAULTS[k] if v is None else v for k, v in given.items()}
-    return _capi.ApgQuadMpcOptions(int(o["iters"]), float(o["beta"]),
-                                   float(o["alpha_thrust"]), float(o["alpha_rate"]))
+    """ApgQuadMpcOptions; None = the default of MPC_DEFAULTS."""
+    return _mpc_options(_capi.ApgQuadMpcOptions, MPC_DEFAULTS, iters=iters, beta=beta,
+                        alpha_thrust=alpha_thrust, alpha_rate=alpha_rate)
 
 
 def quad_mpc_solve(state0, ref, dt, params, u0=None, weights=None, iters=10, beta=None,
@@ -2232,10 +2292,8 @@ def wing_mlp_closed_loop(net, targets, dt, params, mean, std, data_dt=0.05,
     not read, plus the residual network), one device-to-host read of its 50
     physical numbers per call."""
     _guard_policy_inputs("closed-loop evaluation", targets=targets)
-    B, n_targets, _ = targets.shape
-    dev = targets.device
-    tg = _f32c(targets).permute(1, 2, 0).contiguous()
-    s0 = None if state0 is None else to_soa(state0)
+    fl = _WingFlight(targets, state0, max_steps, thresh_div, thresh_stable, test_time,
+                     want_trajectory)
     names = ("w_s", "b_s", "w_r", "b_r", "w_1", "b_1", "w_2", "b_2", "w_3",
              "b_3", "w_out", "b_out")
     vals = (net.states_in.weight, net.states_in.bias, net.ref_in.weight,
@@ -2247,20 +2305,12 @@ def wing_mlp_closed_loop(net, targets, dt, params, mean, std, data_dt=0.05,
             or pw["w_1"].shape != (64, 128) or pw["w_out"].shape[1] != 64
             or pw["w_out"].shape[0] < 4):
         raise ValueError("closed loop needs Net(9, 1, 3, 4*k, conv=False)")
-    require_device(tg, *pw.values())
-    if s0 is not None:
-        require_device(s0)
+    require_device(fl.tg, fl.s0, *pw.values())
     pol = _capi.ApgWingPolicy(**{k: ptr(v) for k, v in pw.items()})
     f12 = ctypes.c_float * 12
     mean = f12(*[float(v) for v in mean])
     std = f12(*[float(v) for v in std])
-    T = int(max_steps)
-    new = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
-    div_linear, div_pass, div_fail = new(T, B), new(T, B), new(T, B)
-    steps = torch.zeros(B, dtype=torch.int32, device=dev)
-    drone = new(T, 16, B) if want_trajectory else None
-    seen = new(T, 15, B) if want_trajectory else None
-    ws = new(lib().apg_wing_policy_workspace_floats())
+    ws = fl.new(lib().apg_wing_policy_workspace_floats())
     I9 = model = None
     if learnt is not None:
         host = torch.cat((learnt._theta().detach().reshape(-1).float(),
@@ -2277,18 +2327,12 @@ def wing_mlp_closed_loop(net, targets, dt, params, mean, std, data_dt=0.05,
             raise ValueError("closed loop expects the 16 -> 64 -> 12 residual network")
         model = _capi.ApgLearntResidual(None, *[t.data_ptr() for t in res])
     check(lib().apg_wing_mlp_closed_loop(
-        ptr(tg), n_targets, ptr(s0), float(dt), ctypes.byref(params), I9,
+        fl.ref, float(dt), ctypes.byref(params), I9,
         None if model is None else ctypes.byref(model),
-        ctypes.byref(pol), mean, std, float(data_dt), int(data_horizon), B, T,
-        float(thresh_div), float(thresh_stable), int(test_time),
-        ptr(div_linear), ptr(div_pass), ptr(div_fail), steps.data_ptr(),
-        ptr(drone), ptr(seen), ptr(ws), stream_of(tg)),
+        ctypes.byref(pol), mean, std, float(data_dt), int(data_horizon), fl.B,
+        ptr(ws), stream_of(fl.tg)),
         "apg_wing_mlp_closed_loop")
-    out = dict(div_linear=div_linear, div_pass=div_pass, div_fail=div_fail,
-               steps=steps)
-    if want_trajectory:
-        out.update(drone=drone, seen=seen)
-    return out
+    return fl.out
 
 
 # ------------------------------------------ batched shooting MPC, fixed wing
@@ -2297,12 +2341,9 @@ WING_MPC_START = (0.25, 0.5, 0.5, 0.5)
 
 
 def wing_mpc_options(iters=None, beta=None, alpha_thrust=None, alpha_surface=None):
-    """ApgWingMpcOptions (include/apg.h); None = the default of WING_MPC_DEFAULTS."""
-    given = dict(iters=iters, beta=beta, alpha_thrust=alpha_thrust,
-                 alpha_surface=alpha_surface)
-    o = {k: WING_MPC_DEFAULTS[k] if v is None else v for k, v in given.items()}
-    return _capi.ApgWingMpcOptions(int(o["iters"]), float(o["beta"]),
-                                   float(o["alpha_thrust"]), float(o["alpha_surface"]))
+    """ApgWingMpcOptions; None = the default of WING_MPC_DEFAULTS."""
+    return _mpc_options(_capi.ApgWingMpcOptions, WING_MPC_DEFAULTS, iters=iters, beta=beta,
+                        alpha_thrust=alpha_thrust, alpha_surface=alpha_surface)
 
 
 def wing_mpc_reference(state0, target, dt, horizon=10):
@@ -2370,33 +2411,18 @@ def wing_mpc_closed_loop(targets, dt, params, model_params=None, state0=None, we
     iters, beta, alpha_thrust, alpha_surface.  Returns the dict
     wing_mlp_closed_loop returns, plus cost [T,B]: the solver's cost at every
     control step."""
-    if targets.dim() != 3 or targets.shape[2] != 3:
-        raise ValueError(f"targets [B, n_targets, 3] expected, got {tuple(targets.shape)}")
-    B, n_targets, _ = targets.shape
-    dev = targets.device
-    tg = _f32c(targets).permute(1, 2, 0).contiguous()
-    s0 = None if state0 is None else to_soa(state0)
-    require_device(tg, s0)
+    fl = _WingFlight(targets, state0, max_steps, thresh_div, thresh_stable, test_time,
+                     want_trajectory)
+    require_device(fl.tg, fl.s0)
     opt = wing_mpc_options(**options)
     weights = weights or wing_loss_weights()
     model = params if model_params is None else model_params
-    T = int(max_steps)
-    new = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
-    div_linear, div_pass, div_fail, cost = new(T, B), new(T, B), new(T, B), new(T, B)
-    steps = torch.zeros(B, dtype=torch.int32, device=dev)
-    drone = new(T, 16, B) if want_trajectory else None
-    seen = new(T, 15, B) if want_trajectory else None
+    cost = fl.new(fl.T, fl.B)
     check(lib().apg_wing_mpc_closed_loop(
-        ptr(tg), n_targets, ptr(s0), float(dt), ctypes.byref(params), ctypes.byref(model),
-        ctypes.byref(weights), ctypes.byref(opt), B, 10, T, float(thresh_div),
-        float(thresh_stable), int(test_time), ptr(div_linear), ptr(div_pass), ptr(div_fail),
-        steps.data_ptr(), ptr(drone), ptr(seen), ptr(cost), stream_of(tg)),
+        fl.ref, float(dt), ctypes.byref(params), ctypes.byref(model), ctypes.byref(weights),
+        ctypes.byref(opt), fl.B, 10, ptr(cost), stream_of(fl.tg)),
         "apg_wing_mpc_closed_loop")
-    out = dict(div_linear=div_linear, div_pass=div_pass, div_fail=div_fail, steps=steps,
-               cost=cost)
-    if want_trajectory:
-        out.update(drone=drone, seen=seen)
-    return out
+    return dict(fl.out, cost=cost)
 
 
 def wing_policy_actions(net, mean, std, state0, ref):
@@ -2449,15 +2475,7 @@ def cartpole_mlp_closed_loop(net, state0, dt, params, max_steps=250,
     episode's last step are zero.
     learnt: a LearntCartpoleDynamics module - the environment steps through
     its forward (apg_cartpole_learnt_mlp_closed_loop; `params` is not read)."""
-    m = CARTPOLE_MODES.get(mode, mode)
-    if m not in (0, 1):
-        raise ValueError(f"mode must be 'balance' or 'swingup', got {mode!r}")
-    if state0.dim() != 2 or state0.shape[1] != 4 or state0.shape[0] < 1:
-        raise ValueError(f"state0 [B, 4] expected, got {tuple(state0.shape)}")
-    B, T = state0.shape[0], int(max_steps)
-    if T < 1:
-        raise ValueError(f"max_steps must be >= 1, got {T}")
-    dev = state0.device
+    fl = _CartpoleFlight(state0, max_steps, mode, thresh_div, burn_in, want_trajectory)
     layers = (net.fc0, net.fc1, net.fc2, net.fc3, net.fc_out)
     shapes = ((32, 4), (64, 32), (64, 64), (32, 64))
     if (any(tuple(l.weight.shape) != s for l, s in zip(layers, shapes))
@@ -2466,35 +2484,20 @@ def cartpole_mlp_closed_loop(net, state0, dt, params, max_steps=250,
     pw = []
     for l in layers:
         pw += [_f32c(l.weight), _f32c(l.bias)]
-    s_in = _f32c(state0)
-    require_device(s_in, *pw)
-    s0 = to_soa(s_in)
+    require_device(fl.s0, *pw)
     _guard_policy_inputs("cart-pole closed loop", state0=state0)
     pol = _capi.ApgCartpolePolicy(*[ptr(t) for t in pw])
-    steps = torch.zeros(B, dtype=torch.int32, device=dev)
-    upright = torch.zeros(B, dtype=torch.int32, device=dev)
-    vel_sum = torch.zeros(B, dtype=torch.float64, device=dev)
-    vel_sq = torch.zeros(B, dtype=torch.float64, device=dev)
-    states = actions = None
-    if want_trajectory:
-        states = torch.zeros(T, 4, B, dtype=torch.float32, device=dev)
-        actions = torch.zeros(T, B, dtype=torch.float32, device=dev)
     ws = torch.empty(lib().apg_cartpole_policy_workspace_floats(),
-                     dtype=torch.float32, device=dev)
+                     dtype=torch.float32, device=state0.device)
     if learnt is None:
         name, env = "apg_cartpole_mlp_closed_loop", params
     else:
         name = "apg_cartpole_learnt_mlp_closed_loop"
         env = _cartpole_learnt_model(_cartpole_learnt_tensors(learnt))
     check(getattr(lib(), name)(
-        ptr(s0), float(dt), ctypes.byref(env), ctypes.byref(pol), B, T, m,
-        float(thresh_div), int(burn_in), steps.data_ptr(), upright.data_ptr(),
-        vel_sum.data_ptr(), vel_sq.data_ptr(), ptr(states), ptr(actions),
-        ptr(ws), stream_of(s0)), name)
-    out = dict(steps=steps, upright=upright, vel_sum=vel_sum, vel_sq=vel_sq)
-    if want_trajectory:
-        out.update(states=states, actions=actions)
-    return out
+        fl.ref, float(dt), ctypes.byref(env), ctypes.byref(pol), fl.B, ptr(ws),
+        stream_of(fl.s0)), name)
+    return fl.out
 
 
 # ------------------------------------------- batched shooting MPC, cart-pole
@@ -2502,11 +2505,9 @@ CARTPOLE_MPC_DEFAULTS = dict(iters=10, beta=0.5, alpha=5e-4)
 
 
 def cartpole_mpc_options(iters=None, beta=None, alpha=None):
-    """ApgCartpoleMpcOptions (include/apg.h); None = the default of
-    CARTPOLE_MPC_DEFAULTS."""
-    given = dict(iters=iters, beta=beta, alpha=alpha)
-    o = {k: CARTPOLE_MPC_DEFAULTS[k] if v is None else v for k, v in given.items()}
-    return _capi.ApgCartpoleMpcOptions(int(o["iters"]), float(o["beta"]), float(o["alpha"]))
+    """ApgCartpoleMpcOptions; None = the default of CARTPOLE_MPC_DEFAULTS."""
+    return _mpc_options(_capi.ApgCartpoleMpcOptions, CARTPOLE_MPC_DEFAULTS, iters=iters,
+                        beta=beta, alpha=alpha)
 
 
 def cartpole_mpc_solve(state0, dt, params, u0=None, horizon=10, iters=None, beta=None,
@@ -2567,14 +2568,7 @@ def cartpole_mpc_closed_loop(state0, dt, params, model_params=None, learnt=None,
     solver's cost at every control step."""
     horizon = int(options.pop("horizon", 10))
     opt = cartpole_mpc_options(**options)
-    m = CARTPOLE_MODES.get(mode, mode)
-    if m not in (0, 1):
-        raise ValueError(f"mode must be 'balance' or 'swingup', got {mode!r}")
-    if state0.dim() != 2 or state0.shape[1] != 4 or state0.shape[0] < 1:
-        raise ValueError(f"state0 [B, 4] expected, got {tuple(state0.shape)}")
-    B, T = state0.shape[0], int(max_steps)
-    if T < 1:
-        raise ValueError(f"max_steps must be >= 1, got {T}")
+    fl = _CartpoleFlight(state0, max_steps, mode, thresh_div, burn_in, want_trajectory)
     if model_learnt is not None:
         name = "apg_cartpole_learnt_mpc_closed_loop"
         model_tensors = _cartpole_learnt_tensors(model_learnt)
@@ -2584,18 +2578,8 @@ def cartpole_mpc_closed_loop(state0, dt, params, model_params=None, learnt=None,
         model = params if model_params is None else model_params
         if model is None:
             raise ValueError("model_params is required when the plant is a learnt module")
-    dev = state0.device
-    s0 = _f32c(state0).t().contiguous()
-    require_device(s0)
-    steps = torch.zeros(B, dtype=torch.int32, device=dev)
-    upright = torch.zeros(B, dtype=torch.int32, device=dev)
-    vel_sum = torch.zeros(B, dtype=torch.float64, device=dev)
-    vel_sq = torch.zeros(B, dtype=torch.float64, device=dev)
-    cost = torch.zeros(T, B, dtype=torch.float32, device=dev)
-    states = actions = None
-    if want_trajectory:
-        states = torch.zeros(T, 4, B, dtype=torch.float32, device=dev)
-        actions = torch.zeros(T, B, dtype=torch.float32, device=dev)
+    require_device(fl.s0)
+    cost = fl.new(fl.T, fl.B)
     env = None
     if learnt is None and params is None:
         raise ValueError("params (or a learnt plant module) is required")
@@ -2603,14 +2587,10 @@ def cartpole_mpc_closed_loop(state0, dt, params, model_params=None, learnt=None,
         tensors = _cartpole_learnt_tensors(learnt)       # (kept alive to the launch)
         env = ctypes.byref(_cartpole_learnt_model(tensors))
     check(getattr(lib(), name)(
-        ptr(s0), float(dt), None if learnt is not None else ctypes.byref(params), env,
-        ctypes.byref(model), ctypes.byref(opt), B, horizon, T, m, float(thresh_div),
-        int(burn_in), steps.data_ptr(), upright.data_ptr(), vel_sum.data_ptr(),
-        vel_sq.data_ptr(), ptr(states), ptr(actions), ptr(cost), stream_of(s0)), name)
-    out = dict(steps=steps, upright=upright, vel_sum=vel_sum, vel_sq=vel_sq, cost=cost)
-    if want_trajectory:
-        out.update(states=states, actions=actions)
-    return out
+        fl.ref, float(dt), None if learnt is not None else ctypes.byref(params), env,
+        ctypes.byref(model), ctypes.byref(opt), fl.B, horizon, ptr(cost), stream_of(fl.s0)),
+        name)
+    return dict(fl.out, cost=cost)
 
 
 def cartpole_policy_optimality_gap(net, state0, dt, params, iters=50, learnt=None):

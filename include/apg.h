@@ -980,15 +980,34 @@ int apg_wing_policy_bwd(const float *actions, const float *grad_actions,
  * SimpleWingEnv.step (neural_control/environments/wing_env.py:44-57, dt),
  * project_to_line (neural_control/trajectory/q_funcs.py:6-18), the target
  * switch, and on divergence the break (test_time) or the reset onto the line
- * at 11.5 m/s.  targets [n_targets][3][B]; state0 [12][B] or NULL (zero_reset:
+ * at 11.5 m/s.  ApgWingFlight = the targets, the start, the rule's numbers and
+ * the log: targets [n_targets][3][B]; state0 [12][B] or NULL (zero_reset:
  * zeros, u = 11.5).  Outputs, all SoA: div_linear [T][B] (div_to_linear),
  * div_pass [T][B] / div_fail [T][B] = the values fly_to_point appends to
  * div_target when a target is passed / on divergence at that step (-1: none;
  * the caller appends thresh_div for a run with steps == max_steps), steps [B]
- * = len(drone_traj); optional drone [T][16][B] (state after the step, action)
- * and seen [T][15][B] (state the policy saw - after a reset still the last
- * simulated one, as in the reference - and its target).
- * workspace: apg_wing_policy_workspace_floats().
+ * = len(drone_traj); optional (NULL to skip) drone [T][16][B] (state after the
+ * step, action) and seen [T][15][B] (state the policy saw - after a reset still
+ * the last simulated one, as in the reference - and its target).  T = max_steps. */
+typedef struct ApgWingFlight {
+  const float *targets;
+  const float *state0;
+  int n_targets, max_steps;
+  float thresh_div, thresh_stable;
+  int test_time;
+  float *div_linear, *div_pass, *div_fail;
+  int *steps;
+  float *drone, *seen;
+} ApgWingFlight;
+/* Argument rules.  Shared (csrc/wing_flight_rule.h, wing_flight_check): flight
+ * non-NULL; n_targets >= 1; with B > 0 and max_steps > 0: targets, div_linear,
+ * div_pass, div_fail and steps non-NULL.  Per entry point:
+ *                              max_steps      B == 0   B x max_steps     workspace
+ *   apg_wing_mlp_closed_loop   >= 0, 0: no-op no-op    32-bit offsets    needed
+ *   apg_wing_mpc_closed_loop   >= 1           no-op    any               none
+ *   (and its _cpu twin) */
+
+/* The MLP controller: workspace: apg_wing_policy_workspace_floats().
  * The environment: inertia and learnt both NULL = SimpleWingEnv on `params`;
  * else a LEARNT one (LearntFixedWingDynamics.forward,
  * neural_control/dynamics/fixed_wing_dynamics.py:270-326 - what
@@ -997,17 +1016,12 @@ int apg_wing_policy_bwd(const float *actions, const float *grad_actions,
  * module's parameters, `inertia` = its 3x3 parameter `I` (HOST array of 9,
  * row-major, used in full, as apg_wing_learnt_step_fwd), `learnt` = the residual
  * network on [state, action] (linear_at is not read). */
-int apg_wing_mlp_closed_loop(const float *targets, int n_targets,
-                             const float *state0, float dt,
+int apg_wing_mlp_closed_loop(const ApgWingFlight *flight, float dt,
                              const ApgWingParams *params, const float *inertia,
                              const ApgLearntResidual *learnt,
                              const ApgWingPolicy *policy, const float *mean,
                              const float *std, float data_dt, int data_horizon,
-                             int B, int max_steps, float thresh_div,
-                             float thresh_stable, int test_time,
-                             float *div_linear, float *div_pass, float *div_fail,
-                             int *steps, float *drone, float *seen,
-                             float *workspace, apg_stream_t stream);
+                             int B, float *workspace, apg_stream_t stream);
 
 /* Weights of fixed_wing_mpc_loss, neural_control/drone_loss.py:72-82
  * (reference values: pos 10, action 0.1). */
@@ -1270,24 +1284,40 @@ enum { APG_CARTPOLE_BALANCE = 0, APG_CARTPOLE_SWINGUP = 1 };
  * (dt, params) and CartPoleEnv._step's theta wrap (neural_control/
  * environments/cartpole_env.py:57-82).  From the second step on the cart
  * position entering a step is 0 (the policy zeroes it in the environment's
- * own state array in the reference).  state0 [4][B] (SoA).
+ * own state array in the reference).
+ * ApgCartpoleFlight = the starts, the rule's numbers and the log: state0 [4][B]
+ * (SoA).
  * Balance: |x_dot| is recorded every step; the episode stops after the first
  * step whose theta is not inside (-thresh_div, thresh_div).  Swing-up: never
  * stops; |x_dot| is recorded for steps i > burn_in, where theta > 1 clears
  * the upright flag.  Outputs [B]: steps = steps taken (balance: success + 1),
  * upright = 1 unless cleared (balance: 1 iff the episode never failed),
  * vel_sum / vel_sq = sum / sum of squares (fp64) of the recorded values;
- * optional states [T][4][B] (state after each step) and actions [T][B].
- * Rows of steps not taken are not written.  B >= 1, max_steps >= 1.
- * workspace: apg_cartpole_policy_workspace_floats(). */
+ * optional (NULL to skip) states [T][4][B] (state after each step) and actions
+ * [T][B], T = max_steps.  Rows of steps not taken are not written. */
+typedef struct ApgCartpoleFlight {
+  const float *state0;
+  int max_steps, mode;          /* APG_CARTPOLE_BALANCE | APG_CARTPOLE_SWINGUP */
+  float thresh_div;
+  int burn_in;
+  int *steps, *upright;
+  double *vel_sum, *vel_sq;
+  float *states, *actions;
+} ApgCartpoleFlight;
+/* Argument rules.  Shared (csrc/cart_flight_rule.h, cart_flight_check): flight
+ * non-NULL; B >= 1 and max_steps >= 1; a known mode; state0, steps, upright,
+ * vel_sum and vel_sq non-NULL.  Per entry point:
+ *                                          B x max_steps     workspace
+ *   apg_cartpole_[learnt_]mlp_closed_loop  32-bit offsets    needed
+ *   apg_cartpole_[learnt_]mpc_closed_loop  any               none
+ *   (and their _cpu twins) */
+
+/* The MLP controller.  workspace: apg_cartpole_policy_workspace_floats(). */
 int apg_cartpole_policy_workspace_floats(void);
-int apg_cartpole_mlp_closed_loop(const float *state0, float dt,
+int apg_cartpole_mlp_closed_loop(const ApgCartpoleFlight *flight, float dt,
                                  const ApgCartpoleParams *params,
-                                 const ApgCartpolePolicy *policy, int B, int max_steps,
-                                 int mode, float thresh_div, int burn_in, int *steps,
-                                 int *upright, double *vel_sum, double *vel_sq,
-                                 float *states, float *actions, float *workspace,
-                                 apg_stream_t stream);
+                                 const ApgCartpolePolicy *policy, int B,
+                                 float *workspace, apg_stream_t stream);
 
 /* The controller step of the cart-pole in one call: the controller branch of
  * TrainCartpole.run_epoch (scripts/train_cartpole.py:127-155) with
@@ -1459,14 +1489,10 @@ int apg_cartpole_learnt_mlp_train_step(const float *in_state, const float *state
  * forward (the residual reads the pre-step state, whose cart position is 0
  * from the second step on, and the raw action), then the theta wrap.  The
  * residual must be given. */
-int apg_cartpole_learnt_mlp_closed_loop(const float *state0, float dt,
+int apg_cartpole_learnt_mlp_closed_loop(const ApgCartpoleFlight *flight, float dt,
                                         const ApgCartpoleLearnt *model,
                                         const ApgCartpolePolicy *policy, int B,
-                                        int max_steps, int mode, float thresh_div,
-                                        int burn_in, int *steps, int *upright,
-                                        double *vel_sum, double *vel_sq, float *states,
-                                        float *actions, float *workspace,
-                                        apg_stream_t stream);
+                                        float *workspace, apg_stream_t stream);
 
 /* ------------------------------------------------ cartpole, shooting MPC --- */
 /* Batched shooting MPC for the cart-pole - the comparator of the reference's
@@ -1515,13 +1541,12 @@ int apg_cartpole_mpc_solve(const float *state0, const float *u0, float dt,
  * experiment.  The cart position is NOT zeroed between steps (that is
  * Net.forward's side effect in the network controller's loop).  H = 5 or 10,
  * B >= 1, max_steps >= 1. */
-int apg_cartpole_mpc_closed_loop(const float *state0, float dt, const ApgCartpoleParams *plant,
+int apg_cartpole_mpc_closed_loop(const ApgCartpoleFlight *flight, float dt,
+                                 const ApgCartpoleParams *plant,
                                  const ApgCartpoleLearnt *plant_learnt,
                                  const ApgCartpoleParams *model,
-                                 const ApgCartpoleMpcOptions *opt, int B, int H, int max_steps,
-                                 int mode, float thresh_div, int burn_in, int *steps,
-                                 int *upright, double *vel_sum, double *vel_sq, float *states,
-                                 float *actions, float *cost, apg_stream_t stream);
+                                 const ApgCartpoleMpcOptions *opt, int B, int H,
+                                 float *cost, apg_stream_t stream);
 
 /* The same solver planning through the LEARNT simulator - the role of the
  * reference's LearntDynamicsMPC (neural_control/dynamics/learnt_dynamics.py:
@@ -1541,14 +1566,11 @@ int apg_cartpole_learnt_mpc_solve(const float *state0, const float *u0, float dt
                                   const ApgCartpoleLearnt *model,
                                   const ApgCartpoleMpcOptions *opt, int B, int H, float *u,
                                   float *cost_out, float *cost_trace, apg_stream_t stream);
-int apg_cartpole_learnt_mpc_closed_loop(const float *state0, float dt,
+int apg_cartpole_learnt_mpc_closed_loop(const ApgCartpoleFlight *flight, float dt,
                                         const ApgCartpoleParams *plant,
                                         const ApgCartpoleLearnt *plant_learnt,
                                         const ApgCartpoleLearnt *model,
                                         const ApgCartpoleMpcOptions *opt, int B, int H,
-                                        int max_steps, int mode, float thresh_div, int burn_in,
-                                        int *steps, int *upright, double *vel_sum,
-                                        double *vel_sq, float *states, float *actions,
                                         float *cost, apg_stream_t stream);
 
 /* ---------------------------------------------- fixed wing, shooting MPC --- */
@@ -1593,13 +1615,11 @@ int apg_wing_mpc_solve(const float *state0, const float *ref, float dt,
  * flight, `model` is what the solver plans with (the plant's parameters for the
  * nominal case, others for the model-mismatch experiment).  H = 10,
  * n_targets >= 1, max_steps >= 1. */
-int apg_wing_mpc_closed_loop(const float *targets, int n_targets, const float *state0,
-                             float dt, const ApgWingParams *plant, const ApgWingParams *model,
-                             const ApgWingLossWeights *weights, const ApgWingMpcOptions *opt,
-                             int B, int H, int max_steps, float thresh_div,
-                             float thresh_stable, int test_time, float *div_linear,
-                             float *div_pass, float *div_fail, int *steps, float *drone,
-                             float *seen, float *cost, apg_stream_t stream);
+int apg_wing_mpc_closed_loop(const ApgWingFlight *flight, float dt,
+                             const ApgWingParams *plant, const ApgWingParams *model,
+                             const ApgWingLossWeights *weights,
+                             const ApgWingMpcOptions *opt, int B, int H,
+                             float *cost, apg_stream_t stream);
 
 /* ------------------------------------------------------- launch chain --- */
 /* A chain of deferred-loss rollout launches run as TWO overlapping lanes.

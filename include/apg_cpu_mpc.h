@@ -55,14 +55,11 @@ int apg_cartpole_mpc_solve_cpu(const float *state0, const float *u0, float dt,
                                const ApgCartpoleParams *model,
                                const ApgCartpoleMpcOptions *opt, int B, int H, float *u,
                                float *cost_out, float *cost_trace);
-int apg_cartpole_mpc_closed_loop_cpu(const float *state0, float dt,
+int apg_cartpole_mpc_closed_loop_cpu(const ApgCartpoleFlight *flight, float dt,
                                      const ApgCartpoleParams *plant,
                                      const ApgCartpoleLearnt *plant_learnt,
                                      const ApgCartpoleParams *model,
                                      const ApgCartpoleMpcOptions *opt, int B, int H,
-                                     int max_steps, int mode, float thresh_div, int burn_in,
-                                     int *steps, int *upright, double *vel_sum,
-                                     double *vel_sq, float *states, float *actions,
                                      float *cost);
 
 /* The learnt-model solver (apg_cartpole_learnt_mpc_solve,
@@ -72,15 +69,12 @@ int apg_cartpole_learnt_mpc_solve_cpu(const float *state0, const float *u0, floa
                                       const ApgCartpoleLearnt *model,
                                       const ApgCartpoleMpcOptions *opt, int B, int H, float *u,
                                       float *cost_out, float *cost_trace);
-int apg_cartpole_learnt_mpc_closed_loop_cpu(const float *state0, float dt,
+int apg_cartpole_learnt_mpc_closed_loop_cpu(const ApgCartpoleFlight *flight, float dt,
                                             const ApgCartpoleParams *plant,
                                             const ApgCartpoleLearnt *plant_learnt,
                                             const ApgCartpoleLearnt *model,
                                             const ApgCartpoleMpcOptions *opt, int B, int H,
-                                            int max_steps, int mode, float thresh_div,
-                                            int burn_in, int *steps, int *upright,
-                                            double *vel_sum, double *vel_sq, float *states,
-                                            float *actions, float *cost);
+                                            float *cost);
 
 #ifdef __cplusplus
 }

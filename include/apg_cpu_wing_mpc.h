@@ -20,13 +20,10 @@ int apg_wing_mpc_solve_cpu(const float *state0, const float *ref, float dt,
                            const ApgWingParams *model, const ApgWingLossWeights *weights,
                            const ApgWingMpcOptions *opt, int B, int H, float *u,
                            float *cost_out, float *cost_trace);
-int apg_wing_mpc_closed_loop_cpu(const float *targets, int n_targets, const float *state0,
-                                 float dt, const ApgWingParams *plant,
-                                 const ApgWingParams *model, const ApgWingLossWeights *weights,
-                                 const ApgWingMpcOptions *opt, int B, int H, int max_steps,
-                                 float thresh_div, float thresh_stable, int test_time,
-                                 float *div_linear, float *div_pass, float *div_fail,
-                                 int *steps, float *drone, float *seen, float *cost);
+int apg_wing_mpc_closed_loop_cpu(const ApgWingFlight *flight, float dt,
+                                 const ApgWingParams *plant, const ApgWingParams *model,
+                                 const ApgWingLossWeights *weights,
+                                 const ApgWingMpcOptions *opt, int B, int H, float *cost);
 
 #ifdef __cplusplus
 }

@@ -232,7 +232,7 @@ def twins():
     PO = ctypes.POINTER(_capi.ApgCartpoleMpcOptions)
     lib.apg_cartpole_learnt_mpc_solve_cpu.argtypes = [P, P, F, PL, PO, I, I, P, P, P]
     lib.apg_cartpole_learnt_mpc_closed_loop_cpu.argtypes = [
-        P, F, PP, PL, PL, PO, I, I, I, I, F, I, P, P, P, P, P, P, P]
+        ctypes.POINTER(_capi.ApgCartpoleFlight), F, PP, PL, PL, PO, I, I, P]
     return lib
 
 
@@ -279,12 +279,16 @@ def twin_closed_loop(tw, state0, dt, iters, max_steps, model, plant=None, plant_
     hm = None if model is None else HostModel(model)
     fn = (tw.apg_cartpole_mpc_closed_loop_cpu if model is None
           else tw.apg_cartpole_learnt_mpc_closed_loop_cpu)
-    rc = fn(s.data_ptr(), dt, None if hp else ctypes.byref(R.params(plant_params)),
+    from apg_trajectory_tracking_amd import _capi
+    flight = _capi.ApgCartpoleFlight(
+        state0=s.data_ptr(), max_steps=T, mode={"balance": 0, "swingup": 1}[mode],
+        thresh_div=thresh_div, burn_in=burn_in, steps=steps.data_ptr(),
+        upright=upright.data_ptr(), vel_sum=vs.data_ptr(), vel_sq=vq.data_ptr(),
+        states=states.data_ptr(), actions=actions.data_ptr())
+    rc = fn(ctypes.byref(flight), dt, None if hp else ctypes.byref(R.params(plant_params)),
             ctypes.byref(hp.struct) if hp else None,
             ctypes.byref(hm.struct) if hm else ctypes.byref(R.params(model_params)),
-            ctypes.byref(R.options(iters)), B, horizon, T, {"balance": 0, "swingup": 1}[mode],
-            thresh_div, burn_in, steps.data_ptr(), upright.data_ptr(), vs.data_ptr(),
-            vq.data_ptr(), states.data_ptr(), actions.data_ptr(), cost_.data_ptr())
+            ctypes.byref(R.options(iters)), B, horizon, cost_.data_ptr())
     assert rc == 0, tw.apg_cpu_last_error_string()
     return R.from_device_layout(dict(steps=steps, upright=upright, vel_sum=vs, vel_sq=vq,
                                      states=states, actions=actions, cost=cost_))

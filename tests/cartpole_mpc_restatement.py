@@ -282,8 +282,8 @@ def twins():
     PO = ctypes.POINTER(_capi.ApgCartpoleMpcOptions)
     lib.apg_cartpole_mpc_solve_cpu.argtypes = [P, P, F, PP, PO, I, I, P, P, P]
     lib.apg_cartpole_mpc_closed_loop_cpu.argtypes = [
-        P, F, PP, ctypes.POINTER(_capi.ApgCartpoleLearnt), PP, PO, I, I, I, I, F, I,
-        P, P, P, P, P, P, P]
+        ctypes.POINTER(_capi.ApgCartpoleFlight), F, PP, ctypes.POINTER(_capi.ApgCartpoleLearnt),
+        PP, PO, I, I, P]
     lib.apg_cpu_last_error_string.restype = ctypes.c_char_p
     return lib
 
@@ -314,19 +314,25 @@ def twin_solve(tw, state0, u0, dt, iters, modified_params=None, horizon=H, opt=N
 
 
 def twin_closed_loop(tw, state0, dt, iters, max_steps, mode, thresh_div=0.21, burn_in=50,
-                     plant_params=None, model_params=None, horizon=H):
-    """apg_cartpole_mpc_closed_loop_cpu -> the dict `closed_loop` returns ([B, ...])."""
+                     plant_params=None, model_params=None, horizon=H, want_trajectory=True):
+    """apg_cartpole_mpc_closed_loop_cpu -> the dict `closed_loop` returns ([B, ...]).
+    want_trajectory False: states / actions are passed as NULL (and come back zero)."""
     B, T = state0.shape[0], max_steps
     s = state0.float().t().contiguous()
     steps, upright = torch.zeros(B, dtype=torch.int32), torch.zeros(B, dtype=torch.int32)
     vs, vq = torch.zeros(B, dtype=torch.float64), torch.zeros(B, dtype=torch.float64)
     states, actions, cost_ = torch.zeros(T, 4, B), torch.zeros(T, B), torch.zeros(T, B)
+    from apg_trajectory_tracking_amd import _capi
+    flight = _capi.ApgCartpoleFlight(
+        state0=s.data_ptr(), max_steps=T, mode={"balance": 0, "swingup": 1}[mode],
+        thresh_div=thresh_div, burn_in=burn_in, steps=steps.data_ptr(),
+        upright=upright.data_ptr(), vel_sum=vs.data_ptr(), vel_sq=vq.data_ptr(),
+        states=states.data_ptr() if want_trajectory else None,
+        actions=actions.data_ptr() if want_trajectory else None)
     rc = tw.apg_cartpole_mpc_closed_loop_cpu(
-        s.data_ptr(), dt, ctypes.byref(params(plant_params)), None,
-        ctypes.byref(params(model_params)), ctypes.byref(options(iters)), B, horizon, T,
-        {"balance": 0, "swingup": 1}[mode], thresh_div, burn_in, steps.data_ptr(),
-        upright.data_ptr(), vs.data_ptr(), vq.data_ptr(), states.data_ptr(),
-        actions.data_ptr(), cost_.data_ptr())
+        ctypes.byref(flight), dt, ctypes.byref(params(plant_params)), None,
+        ctypes.byref(params(model_params)), ctypes.byref(options(iters)), B, horizon,
+        cost_.data_ptr())
     assert rc == 0, tw.apg_cpu_last_error_string()
     return from_device_layout(dict(steps=steps, upright=upright, vel_sum=vs, vel_sq=vq,
                                    states=states, actions=actions, cost=cost_))

@@ -237,12 +237,16 @@ def test_new_entry_point_checks_arguments_before_launch():
     pol = _capi.ApgCartpolePolicy(*([1] * 10))
     buf = ctypes.c_void_p(1)
 
-    def call(policy=pol, B=4, T=10, mode=0, state0=buf, steps=buf, params=p):
+    def call(policy=pol, B=4, T=10, mode=0, state0=buf, steps=buf, params=p, flight=True):
+        fl = _capi.ApgCartpoleFlight(
+            state0=state0, max_steps=T, mode=mode, thresh_div=0.2, burn_in=50, steps=steps,
+            upright=buf, vel_sum=buf, vel_sq=buf, states=None, actions=None)
         return lib.apg_cartpole_mlp_closed_loop(
-            state0, 0.05, None if params is None else ctypes.byref(params),
-            None if policy is None else ctypes.byref(policy), B, T, mode, 0.2,
-            50, steps, buf, buf, buf, None, None, buf, None)
+            ctypes.byref(fl) if flight else None, 0.05,
+            None if params is None else ctypes.byref(params),
+            None if policy is None else ctypes.byref(policy), B, buf, None)
     assert lib.apg_cartpole_policy_workspace_floats() > 0
+    assert call(flight=False) == -1 and b"flight is NULL" in lib.apg_last_error_string()
     assert call(policy=None) == -1
     assert call(policy=_capi.ApgCartpolePolicy(*([1] * 9 + [0]))) == -1
     assert b"NULL" in lib.apg_last_error_string()

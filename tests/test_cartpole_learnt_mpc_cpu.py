@@ -318,13 +318,18 @@ def test_twin_argument_errors(tw):
     vs, vq = torch.zeros(8, dtype=torch.float64), torch.zeros(8, dtype=torch.float64)
     p = R.params()
 
+    def flight(T=3, mode=0, state0=s.data_ptr()):
+        return _capi.ApgCartpoleFlight(
+            state0=state0, max_steps=T, mode=mode, thresh_div=0.21, burn_in=0,
+            steps=steps.data_ptr(), upright=upright.data_ptr(), vel_sum=vs.data_ptr(),
+            vel_sq=vq.data_ptr(), states=None, actions=None)
+
     def loop(H=10, model=ok, plant=p, plant_learnt=None, B=8, T=3, mode=0, opt=None):
         return tw.apg_cartpole_learnt_mpc_closed_loop_cpu(
-            s.data_ptr(), DT, None if plant is None else ctypes.byref(plant),
+            ctypes.byref(flight(T, mode)), DT, None if plant is None else ctypes.byref(plant),
             None if plant_learnt is None else ctypes.byref(plant_learnt),
             None if model is None else ctypes.byref(model),
-            ctypes.byref(opt or R.options(1)), B, H, T, mode, 0.21, 0, steps.data_ptr(),
-            upright.data_ptr(), vs.data_ptr(), vq.data_ptr(), None, None, None)
+            ctypes.byref(opt or R.options(1)), B, H, None)
     assert loop() == 0 and int(steps.min()) >= 1
     assert loop(plant=None, plant_learnt=ok) == 0
     assert loop(model=None) == -1 and b"model is NULL" in err()
@@ -348,8 +353,8 @@ def test_twin_argument_errors(tw):
                                              7, None, None, None, None) == -1
     assert b"H must be 5 or 10" in lib.apg_last_error_string()
     assert lib.apg_cartpole_learnt_mpc_closed_loop(
-        1, DT, None, None, ctypes.byref(ok), ctypes.byref(o1), 8, 10, 3, 0, 0.21, 0, 1, 1, 1, 1,
-        None, None, None, None) == -1
+        ctypes.byref(flight(state0=1)), DT, None, None, ctypes.byref(ok), ctypes.byref(o1), 8,
+        10, None, None) == -1
     assert b"plant is NULL" in lib.apg_last_error_string()
 
 

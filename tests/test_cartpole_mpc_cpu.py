@@ -150,13 +150,18 @@ def check_balance(got, mismatch, what):
     # void unless no flight grazes the threshold and both outcomes occur
     assert f64["margin"] > 1e-3
     assert early >= 0.10 and full >= 0.50
-    assert torch.equal(got["steps"], steps)
+    same_balance_flights(got, f32, f64, what)
+    return f64
+
+
+def same_balance_flights(got, f32, f64, what):
+    """Every output of a balance loop, by name, against its restatement."""
+    assert torch.equal(got["steps"], f64["steps"])
     assert torch.equal(got["upright"], f64["upright"])
     for k in ("states", "actions", "cost"):
         assert_no_worse_than_fp32(N(got[k]), N(f32[k]), N(f64[k]), f"{what} {k}")
     np.testing.assert_allclose(N(got["vel_sum"]), N(f64["vel_sum"]), rtol=1e-4, atol=1e-5)
     np.testing.assert_allclose(N(got["vel_sq"]), N(f64["vel_sq"]), rtol=1e-4, atol=1e-5)
-    return f64
 
 
 def test_balance_loop_twin_vs_the_restated_loop(tw):
@@ -179,6 +184,35 @@ def test_balance_loop_twin_model_mismatch(tw):
     swapped = R.twin_closed_loop(tw, s0, DT, 10, 60, "balance", 0.21, 0,
                                  model_params=R.MISMATCH)
     assert np.abs(N(swapped["states"]) - N(got["states"])).max() > 1e-3
+
+
+def test_every_field_of_the_flight_struct_is_the_one_it_is_named(tw):
+    """ApgCartpoleFlight through the twin on the smallest case whose outputs all
+    differ from each other: B = 3, H = 5, T = 4, balance; flight 0 starts beyond
+    thresh_div (one step, not upright), flight 1 at theta = 0.19 falling outwards
+    (stops early), flight 2 stays up - so steps = (1, <4, 4) is not upright = (0,
+    0, 1), and with |x_dot| away from 0 and 1 vel_sum is not vel_sq.  Each output
+    is held by name against the float64 restatement at the tolerances of the
+    balance tests above; a same-typed neighbour swapped in the struct, in the
+    ctypes mirror or in a forwarding layer fails one of them.  Flown again with
+    states / actions NULL, the other outputs keep their bits."""
+    s0 = torch.tensor([[0.1, 0.4, 0.30, 0.2],
+                       [-0.2, -0.5, 0.19, 3.0],
+                       [0.05, 0.3, 0.02, -0.1]])
+    flown = dict(iters=10, max_steps=4, mode="balance", thresh_div=0.21, burn_in=0, horizon=5)
+    f64, f32 = (R.closed_loop(dt, s0, DT, **flown) for dt in (F64, F32))
+    print("float64 restatement: steps", f64["steps"].tolist(), "upright",
+          f64["upright"].tolist(), "margin %.4f" % f64["margin"])
+    assert f64["margin"] > 1e-3                     # clear of thresh_div
+    assert f64["steps"][0] == 1 and f64["steps"][1] < 4 and f64["steps"][2] == 4
+    assert f64["upright"].tolist() == [False, False, True]
+    got = R.twin_closed_loop(tw, s0, DT, **flown)
+    same_balance_flights(got, f32, f64, "flight struct")
+    assert not np.allclose(N(got["vel_sum"]), N(got["vel_sq"]), rtol=1e-2)
+    bare = R.twin_closed_loop(tw, s0, DT, want_trajectory=False, **flown)
+    for k in ("steps", "upright", "vel_sum", "vel_sq", "cost"):
+        assert torch.equal(bare[k], got[k]), k
+    assert not bare["states"].any() and not bare["actions"].any()
 
 
 def check_swingup(got, what):

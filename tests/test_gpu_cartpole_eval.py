@@ -318,11 +318,15 @@ def _cart_abi(env, mode, s0, dev, skip=()):
     else:
         name = "apg_cartpole_learnt_mlp_closed_loop"
         model = F._cartpole_learnt_model(F._cartpole_learnt_tensors(learnt))
+    flight = _capi.ApgCartpoleFlight(
+        state0=soa.data_ptr(), max_steps=T, mode=F.CARTPOLE_MODES[mode],
+        thresh_div=BALANCE_THRESH, burn_in=10, steps=ints["steps"][CART_GUARD:].data_ptr(),
+        upright=ints["upright"][CART_GUARD:].data_ptr(),
+        vel_sum=sums["vel_sum"][CART_GUARD:].data_ptr(),
+        vel_sq=sums["vel_sq"][CART_GUARD:].data_ptr(), states=at("states"),
+        actions=at("actions"))
     _capi.check(getattr(lib, name)(
-        soa.data_ptr(), DT, ctypes.byref(model), ctypes.byref(pol), B, T,
-        F.CARTPOLE_MODES[mode], BALANCE_THRESH, 10, ints["steps"][CART_GUARD:].data_ptr(),
-        ints["upright"][CART_GUARD:].data_ptr(), sums["vel_sum"][CART_GUARD:].data_ptr(),
-        sums["vel_sq"][CART_GUARD:].data_ptr(), at("states"), at("actions"), ws.data_ptr(),
+        ctypes.byref(flight), DT, ctypes.byref(model), ctypes.byref(pol), B, ws.data_ptr(),
         _capi.stream_of(soa)), name)
     torch.cuda.synchronize(dev)
     for k, buf in full.items():

@@ -136,13 +136,17 @@ def _abi_flight(case, kind, dev, skip=()):
         model = _capi.ApgLearntResidual(None, *[t.data_ptr() for t in res])
     lib = _capi.lib()
     ws = torch.zeros(lib.apg_wing_policy_workspace_floats(), device=dev)
+    flight = _capi.ApgWingFlight(
+        targets=tg.data_ptr(), state0=None if s0 is None else s0.data_ptr(), n_targets=n_t,
+        max_steps=T, thresh_div=case.thresh_div, thresh_stable=case.thresh_stable,
+        test_time=case.test_time, div_linear=at("div_linear"), div_pass=at("div_pass"),
+        div_fail=at("div_fail"), steps=steps[GUARD:].data_ptr(), drone=at("drone"),
+        seen=at("seen"))
     code = lib.apg_wing_mlp_closed_loop(
-        tg.data_ptr(), n_t, None if s0 is None else s0.data_ptr(), d["dt"], ctypes.byref(params),
+        ctypes.byref(flight), d["dt"], ctypes.byref(params),
         I9, None if model is None else ctypes.byref(model), ctypes.byref(pol),
-        f12(*d["mean"].tolist()), f12(*d["std"].tolist()), d["data_dt"], d["data_horizon"], B, T,
-        case.thresh_div, case.thresh_stable, case.test_time, at("div_linear"), at("div_pass"),
-        at("div_fail"), steps[GUARD:].data_ptr(), at("drone"), at("seen"), ws.data_ptr(),
-        _capi.stream_of(tg))
+        f12(*d["mean"].tolist()), f12(*d["std"].tolist()), d["data_dt"], d["data_horizon"], B,
+        ws.data_ptr(), _capi.stream_of(tg))
     _capi.check(code, kind)
     torch.cuda.synchronize(dev)
     return full, steps

@@ -39,6 +39,28 @@ def test_struct_sizes_match_header():
     assert ctypes.sizeof(_capi.ApgWingParams) == 41 * 4
     assert ctypes.sizeof(_capi.ApgCartpoleParams) == 6 * 4
     assert ctypes.sizeof(_capi.ApgDeferredLoss) == 24
+    assert ctypes.sizeof(_capi.ApgCartpoleFlight) == 72
+    assert ctypes.sizeof(_capi.ApgWingFlight) == 88
+
+
+def test_host_twins_refuse_a_null_flight():
+    """The twins take the flight struct where apg.h says they do: a NULL one is
+    APG_ERR_ARG, named, before anything is read through it."""
+    import cartpole_mpc_restatement as cart
+    import wing_mpc_restatement as wing
+    from apg_trajectory_tracking_amd import functional as F
+    tw = cart.twins()
+    p = cart.params()
+    assert tw.apg_cartpole_mpc_closed_loop_cpu(
+        None, 0.05, ctypes.byref(p), None, ctypes.byref(p), ctypes.byref(cart.options(1)),
+        4, 10, None) == -1
+    assert b"flight is NULL" in tw.apg_cpu_last_error_string()
+    tw = wing.twins()
+    p = wing.params()
+    assert tw.apg_wing_mpc_closed_loop_cpu(
+        None, 0.05, ctypes.byref(p), ctypes.byref(p), ctypes.byref(F.wing_loss_weights()),
+        ctypes.byref(wing.options(1)), 4, 10, None) == -1
+    assert b"flight is NULL" in tw.apg_cpu_last_error_string()
 
 
 def test_argument_errors_without_a_gpu():

@@ -127,6 +127,12 @@ def check_loop(got, case, what):
     if case in ("nominal", "mismatch"):      # the flights are what they are meant to be:
         assert int(f64["steps"][32:40].max()) < int(f64["steps"][40:].min())   # lanes end early
         assert bool((f64["seen"][:8, -1, 12] == 30.0).all())                   # targets switch
+    same_flights(got, f32, f64, what)
+    return f64
+
+
+def same_flights(got, f32, f64, what):
+    """Every output of a closed loop, by name, against its restatement."""
     assert torch.equal(f32["steps"], f64["steps"])
     assert torch.equal(got["steps"].long(), f64["steps"])
     for k in ("div_pass", "div_fail"):
@@ -137,7 +143,6 @@ def check_loop(got, case, what):
                                   N(f64[key][:, :, cols]), f"{what} {name}")
     for key in ("div_linear", "div_pass", "div_fail", "cost"):
         assert_no_worse_than_fp32(N(got[key]), N(f32[key]), N(f64[key]), f"{what} {key}")
-    return f64
 
 
 def twin_loop(tw, case):
@@ -313,6 +318,41 @@ def test_evaluator_routes_an_mpc_controller_to_the_mpc_closed_loop(tw, monkeypat
     assert seen["options"] == dict(iters=10, beta=None, alpha_thrust=None, alpha_surface=None)
 
 
+def test_every_field_of_the_flight_struct_is_the_one_it_is_named(tw):
+    """ApgWingFlight through the twin on the smallest case whose outputs all
+    differ from each other: B = 3, two targets, T = 4, test_time = 1, thresh_div
+    = 0.3.  Flight 0 passes a first target at x = 1 after two steps and flies on
+    to the second (an entry in div_pass only); flight 1's target lies 8 m to the
+    side: flying off at 11.5 m/s along x it leaves the line by more than 0.3 at
+    its second step and ends there (an entry in div_fail only, steps = 2); flight
+    2 flies its four steps with neither.  Each output is held by name against the
+    float64 restatement at the tolerances of the loop tests above; a same-typed
+    neighbour swapped in the struct, in the ctypes mirror or in a forwarding layer
+    fails one of them.  Flown again with drone / seen NULL, the other outputs
+    keep their bits."""
+    targets = torch.tensor([[[1.0, 0.05, 0.05], [30.0, 0.5, -0.5]],
+                            [[20.0, 8.0, 0.0], [20.0, 8.0, 0.0]],
+                            [[20.0, 0.5, 0.5], [20.0, 0.5, 0.5]]])
+    flown = dict(iters=10, T=4, thresh_div=0.3, thresh_stable=R.THRESH_STABLE, test_time=1)
+    with R.few_threads():
+        f64, f32 = (R.closed_loop(dt, targets, DT, **flown) for dt in (F64, F32))
+    print("float64 restatement: steps", f64["steps"].tolist(), "margin %.3e"
+          % float(f64["margin"].min()))
+    assert float(f64["margin"].min()) > 1e-3        # clear of every threshold
+    assert f64["steps"].tolist() == [4, 2, 4]
+    flown_rows = torch.arange(4)[None] < f64["steps"][:, None]      # (rows not flown: zero)
+    passed = ((f64["div_pass"] >= 0) & flown_rows).sum(1)
+    failed = ((f64["div_fail"] >= 0) & flown_rows).sum(1)
+    assert passed.tolist() == [1, 0, 0] and failed.tolist() == [0, 1, 0]
+    assert bool((f64["seen"][0, -1, 12:] == targets[0, 1].double()).all())   # target switch
+    got = R.twin_closed_loop(tw, targets, DT, **flown)
+    same_flights(got, f32, f64, "flight struct")
+    bare = R.twin_closed_loop(tw, targets, DT, want_trajectory=False, **flown)
+    for k in ("div_linear", "div_pass", "div_fail", "steps", "cost"):
+        assert torch.equal(bare[k], got[k]), k
+    assert not bare["drone"].any() and not bare["seen"].any()
+
+
 # ------------------------------------------------------------ ABI, resources
 def test_twin_argument_errors_and_abi(tw):
     from apg_trajectory_tracking_amd import _capi, functional as F
@@ -350,14 +390,19 @@ def test_twin_argument_errors_and_abi(tw):
     logs = [torch.zeros(T, B) for _ in range(3)]
     steps = torch.zeros(B, dtype=torch.int32)
 
-    def loop(n=2, T=T, H=10, plant=p, steps=steps, B=B):
+    def loop(n=2, T=T, H=10, plant=p, steps=steps, B=B, flight=True):
+        fl = _capi.ApgWingFlight(
+            targets=tg.data_ptr(), state0=None, n_targets=n, max_steps=T, thresh_div=10.0,
+            thresh_stable=0.8, test_time=0, div_linear=logs[0].data_ptr(),
+            div_pass=logs[1].data_ptr(), div_fail=logs[2].data_ptr(),
+            steps=None if steps is None else steps.data_ptr(), drone=None, seen=None)
         return tw.apg_wing_mpc_closed_loop_cpu(
-            tg.data_ptr(), n, None, DT, None if plant is None else ctypes.byref(plant),
-            ctypes.byref(p), ctypes.byref(w), ctypes.byref(R.options(1)), B, H, T, 10.0, 0.8, 0,
-            *[t.data_ptr() for t in logs], None if steps is None else steps.data_ptr(),
-            None, None, None)
+            ctypes.byref(fl) if flight else None, DT,
+            None if plant is None else ctypes.byref(plant), ctypes.byref(p), ctypes.byref(w),
+            ctypes.byref(R.options(1)), B, H, None)
     assert loop() == 0 and steps.tolist() == [T] * B   # drone, seen, cost NULL: writes dropped
     assert loop(B=0) == 0
+    assert loop(flight=False) == -1 and b"flight is NULL" in err()
     assert loop(n=0) == -1 and b"n_targets must be >= 1" in err()
     assert loop(T=0) == -1 and b"max_steps must be >= 1" in err()
     assert loop(H=5) == -1 and b"H must be 10" in err()

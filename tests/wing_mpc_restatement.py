@@ -313,7 +313,7 @@ def twins():
     WW, WO = ctypes.POINTER(_capi.ApgWingLossWeights), ctypes.POINTER(_capi.ApgWingMpcOptions)
     lib.apg_wing_mpc_solve_cpu.argtypes = [P, P, F, WP, WW, WO, I, I, P, P, P]
     lib.apg_wing_mpc_closed_loop_cpu.argtypes = [
-        P, I, P, F, WP, WP, WW, WO, I, I, I, F, F, I, P, P, P, P, P, P, P]
+        ctypes.POINTER(_capi.ApgWingFlight), F, WP, WP, WW, WO, I, I, P]
     lib.apg_cpu_last_error_string.restype = ctypes.c_char_p
     return lib
 
@@ -358,8 +358,9 @@ def from_device_layout(out):
 
 
 def twin_closed_loop(tw, targets, dt, iters, T, thresh_div, thresh_stable, test_time,
-                     plant_params=None, model_params=None, state0=None):
-    """apg_wing_mpc_closed_loop_cpu -> the logs as `closed_loop` returns them."""
+                     plant_params=None, model_params=None, state0=None, want_trajectory=True):
+    """apg_wing_mpc_closed_loop_cpu -> the logs as `closed_loop` returns them.
+    want_trajectory False: drone / seen are passed as NULL (and come back zero)."""
     from apg_trajectory_tracking_amd import functional as F
     B, n, _ = targets.shape
     tg = targets.float().permute(1, 2, 0).contiguous()
@@ -367,13 +368,19 @@ def twin_closed_loop(tw, targets, dt, iters, T, thresh_div, thresh_stable, test_
     new = lambda *shape: torch.zeros(shape)
     out = dict(div_linear=new(T, B), div_pass=new(T, B), div_fail=new(T, B), cost=new(T, B),
                steps=torch.zeros(B, dtype=torch.int32), drone=new(T, 16, B), seen=new(T, 15, B))
+    from apg_trajectory_tracking_amd import _capi
+    flight = _capi.ApgWingFlight(
+        targets=tg.data_ptr(), state0=None if s0 is None else s0.data_ptr(), n_targets=n,
+        max_steps=T, thresh_div=thresh_div, thresh_stable=thresh_stable,
+        test_time=int(test_time), div_linear=out["div_linear"].data_ptr(),
+        div_pass=out["div_pass"].data_ptr(), div_fail=out["div_fail"].data_ptr(),
+        steps=out["steps"].data_ptr(),
+        drone=out["drone"].data_ptr() if want_trajectory else None,
+        seen=out["seen"].data_ptr() if want_trajectory else None)
     rc = tw.apg_wing_mpc_closed_loop_cpu(
-        tg.data_ptr(), n, None if s0 is None else s0.data_ptr(), dt,
-        ctypes.byref(params(plant_params)), ctypes.byref(params(model_params)),
-        ctypes.byref(F.wing_loss_weights()), ctypes.byref(options(iters)), B, H, T,
-        thresh_div, thresh_stable, int(test_time), out["div_linear"].data_ptr(),
-        out["div_pass"].data_ptr(), out["div_fail"].data_ptr(), out["steps"].data_ptr(),
-        out["drone"].data_ptr(), out["seen"].data_ptr(), out["cost"].data_ptr())
+        ctypes.byref(flight), dt, ctypes.byref(params(plant_params)),
+        ctypes.byref(params(model_params)), ctypes.byref(F.wing_loss_weights()),
+        ctypes.byref(options(iters)), B, H, out["cost"].data_ptr())
     assert rc == 0, tw.apg_cpu_last_error_string()
     return from_device_layout(out)
 
